@@ -8,11 +8,17 @@ N = 1: one "step" is one V(2,2) cycle of the hot path on a resident right-hand s
 2-D Laplacian 16384^2 fp64, weighted-Jacobi smoother; the cycle descends to an 8 x 8 direct solve as the
 reference's 2-D drivers do, 2DPotMatrixVcycle.py:95).  `value` is fine-grid MLUPS = grid points x fine-level sweeps
 per cycle x cycles / wall time of the whole cycles (all levels, transfers and the coarse solve included), so it is a
-lower bound on the fine smoother's own rate, which `roofline` reports from HIP events around the fine-level passes
-alone.  The same line also carries the red-black pass (`roofline_rb`, north_star's target kernel), the
-reference-faithful cycle (V(4,4) below the top level, MGCMTSolver.py:320), the red-black cycle, the one-GPU time of
-the multi-GPU configuration (`strong_scaling_base`), the cycle on the Mehrstellen operator, the reference's default
-lexicographic Gauss-Seidel cycle at 4096^2 (`cycle_gauss_seidel_lexicographic`) and the CPU baselines.
+lower bound on the fine smoother's own rate.  A plain run sets up, warms up, times the --steps cycles and prints
+the line; nothing else.  With --full the same line also carries `roofline` (HIP events around the fine-level passes
+alone), the red-black pass (`roofline_rb`, north_star's target kernel), the residual reduction of the timed cycle,
+the reference-faithful cycle (V(4,4) below the top level, MGCMTSolver.py:320), the red-black cycle, the one-GPU time
+of the multi-GPU configuration (`strong_scaling_base`), the cycle on the Mehrstellen operator, the reference's default
+lexicographic Gauss-Seidel cycle at 4096^2 (`cycle_gauss_seidel_lexicographic`) and the CPU baselines
+(--no-extras, --skip and --no-cpu-baseline trim that list).
+
+--dump-outputs DIR writes what the last timed cycle left in the finest level's iterate v as DIR/v.npy (float64): the
+whole g x g field up to DUMP_SAMPLE points, above that DUMP_SAMPLE entries at fixed seeded indices (sorted, flattened
+row-major).  The inputs are seeded, so two builds run with the same arguments can be compared file by file.
 
 N > 1: BASELINE.json configs[3] — 32768^2, V(2,2) red-black, row strips with RCCL halo exchange (strong scaling:
 the grid is fixed as N grows; multigridcmt_amd/dist_bench.py).
@@ -32,6 +38,8 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
 BYTES_PER_LUP = 24.0           # read v, read f, write v (fp64) per point and sweep
+DUMP_SAMPLE = 1 << 22          # entries of v that --dump-outputs writes at most (32 MiB of fp64)
+DUMP_SEED = 12345
 
 
 def parse(argv=None):
@@ -43,8 +51,14 @@ def parse(argv=None):
     ap.add_argument("--smoother", default=None, choices=["wjacobi", "rb"], help="default: wjacobi on one GPU, rb on several")
     ap.add_argument("--nu", type=int, default=2, help="pre- and post-smoothing sweeps on every level")
     ap.add_argument("--lowest", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline cycle and its roofline record")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline records, the residual history, the other legs and the CPU baselines (a plain run "
+                         "times the headline cycle only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the finest-level iterate after the last timed cycle to DIR/v.npy (float64; a seeded sample "
+                         "above %d points)" % DUMP_SAMPLE)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the headline cycle and its roofline record")
     ap.add_argument("--skip", default="", help="comma-separated extra legs to leave out: other, mehrstellen, lex, 1d, scaling, configs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--force-sharded", action="store_true", help="run the multi-GPU driver even with one rank (testing)")
@@ -240,6 +254,19 @@ def cycle_roofline(plan, args, kind, smoother, omega, n, ms_per_step, reps=20):
             "cycle_compulsory_bytes": cyc, "cycle_compulsory_frac": cyc / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS}
 
 
+def dump_outputs(path, v, g):
+    """DIR/v.npy: the finest-level iterate, whole (g x g) up to DUMP_SAMPLE points, else DUMP_SAMPLE entries at sorted
+    indices drawn from RandomState(DUMP_SEED) (the same indices for the same grid in every run)."""
+    os.makedirs(path, exist_ok=True)
+    v = np.asarray(v, dtype=np.float64)
+    if v.size <= DUMP_SAMPLE:
+        out = v.reshape(g, g)
+    else:
+        idx = np.sort(np.random.RandomState(DUMP_SEED).randint(0, v.size, size=DUMP_SAMPLE, dtype=np.int64))
+        out = v[idx]
+    np.save(os.path.join(path, "v.npy"), np.ascontiguousarray(out))
+
+
 def time_cycles(plan, steps, warmup, cycle):
     for _ in range(warmup):
         cycle()
@@ -260,9 +287,11 @@ def main(argv=None):
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     if args.gpus > 1 or args.force_sharded:
+        if args.dump_outputs is not None:
+            raise SystemExit("--dump-outputs: one-GPU runs only")
         from multigridcmt_amd import dist_bench
         cpu = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             def cpu():
                 try:
                     from oracle import structured
@@ -319,6 +348,12 @@ def main(argv=None):
         "vcycles_per_s": args.steps / elapsed,
         "device": _lib.device_name(0),
     }
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, plan.download(0, _lib.SLOT_V, 0), g)
+    if not args.full:
+        plan.close()
+        print(json.dumps(out))
+        return
     # dominant kernels of the TIMED region: the fine level's two transfer-fused passes (the stand-alone smoother pass,
     # which the cycle does not run, is `roofline_smoother`)
     out["roofline"] = cycle_roofline(plan, args, kind, args.smoother, omega, n, out["ms_per_step"])
@@ -505,7 +540,7 @@ def main(argv=None):
         except Exception as e:
             out["config5_8192_square_well"] = {"value": None, "error": str(e)}
     del f
-    if not args.no_cpu_baseline:
+    if not args.no_cpu_baseline:                   # (--full only: a plain run has returned above)
         out["cpu_baseline"] = cpu_baseline(args, args.smoother)
         if not args.no_extras:
             out["cpu_reference_equivalent"] = cpu_reference_equivalent(128)

@@ -1,14 +1,15 @@
 # per-kernel times of a few V-cycles at 16384^2 (kernel trace + stats)
 set -x
+export OUT=${OUT:?set OUT to the absolute directory the results go to}
 SM=${1:-wjacobi}
 TAG=${2:-p}
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out
+mkdir -p $OUT
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_${TAG}_${SM} -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --smoother $SM > $R/gpurun_out/prof_${TAG}_${SM}.log 2>&1
-tail -2 $R/gpurun_out/prof_${TAG}_${SM}.log
-python3 - $R/gpurun_out/prof_${TAG}_${SM} <<'PY'
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_${SM} -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --smoother $SM > $OUT/prof_${TAG}_${SM}.log 2>&1
+tail -2 $OUT/prof_${TAG}_${SM}.log
+python3 - $OUT/prof_${TAG}_${SM} <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + '/**/*kernel_trace.csv', recursive=True)[0]
 agg = collections.defaultdict(list)

@@ -1,12 +1,13 @@
 # per-kernel times of V(nu,nu) cycles at 16384^2
 set -x
+export OUT=${OUT:?set OUT to the absolute directory the results go to}
 NU=${1:-1}
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out
+mkdir -p $OUT
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_nu$NU -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --nu $NU > $R/gpurun_out/prof_nu$NU.log 2>&1
-python3 - $R/gpurun_out/prof_nu$NU <<'PY'
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_nu$NU -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --nu $NU > $OUT/prof_nu$NU.log 2>&1
+python3 - $OUT/prof_nu$NU <<'PY'
 import csv, glob, sys, collections
 f = glob.glob(sys.argv[1] + '/**/*kernel_trace.csv', recursive=True)[0]
 agg = collections.defaultdict(list)

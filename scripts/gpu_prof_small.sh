@@ -1,8 +1,9 @@
 set -x
+export OUT=${OUT:?set OUT to the absolute directory the results go to}
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-mkdir -p $R/gpurun_out
+mkdir -p $OUT
 cd /tmp
 for sm in wjacobi rb; do
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_small_$sm -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --smoother $sm --grid 1024 > $R/gpurun_out/prof_small_$sm.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_small_$sm -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --smoother $sm --grid 1024 > $OUT/prof_small_$sm.log 2>&1
 done

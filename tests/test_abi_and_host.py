@@ -124,7 +124,7 @@ def test_bench_line_contract(capsys, monkeypatch):
     bind_backend("emu")
     sys.path.insert(0, ROOT)
     import bench
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--grid", "128", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--grid", "128", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"])
     monkeypatch.delenv("RANK", raising=False)
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     bench.main()
@@ -142,6 +142,43 @@ def test_bench_line_contract(capsys, monkeypatch):
     assert len(out["residual_reduction_per_cycle"]) == 10 and out["residual_reduction_per_cycle"][-1] < 1e-3
     assert out["cycle_mehrstellen"]["four_colour"]["ms_per_step"] > 0 and out["cycle_mehrstellen"]["wjacobi"]["value"] > 0
     assert out["cycle_gauss_seidel_lexicographic"]["V22_ms_per_step"] > 0 and out["cycle_gauss_seidel_lexicographic"]["speedup_V22"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(capsys, monkeypatch, tmp_path):
+    """A plain bench run (no --full) prints the headline fields only, and --dump-outputs writes the iterate the timed
+    cycles left: the same field a plan computes from the same right-hand side with warmup + steps cycles."""
+    import json
+    import sys
+    from conftest import ROOT, bind_backend
+    from multigridcmt_amd import _lib, benchdata
+    from multigridcmt_amd.operators import laplacian_operator
+    from multigridcmt_amd.plan import Plan
+    bind_backend("emu")
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--grid", "128", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    monkeypatch.delenv("RANK", raising=False)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    bench.main()
+    line = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1]
+    out = json.loads(line)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert key in out, key
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 128 * 128 * 4 / (out["ms_per_step"] * 1e-3) / 1e6) < 1e-9 * out["value"]
+    for key in ("roofline", "residual_reduction_per_cycle", "cpu_baseline", "cycle_mehrstellen"):
+        assert key not in out, key
+    v = np.load(tmp_path / "v.npy")
+    assert v.dtype == np.float64 and v.shape == (128, 128)
+    p = Plan(laplacian_operator(128, "2d") * (-1.0 / np.pi ** 2), 8, nvec=1)
+    p.set_shifts([0.0])
+    p.upload(0, _lib.SLOT_F, 0, benchdata.rhs(128))
+    p.fill(0, _lib.SLOT_V, 0, 0.0)
+    for _ in range(4):
+        p.vcycle(2, 2, _lib.WJACOBI, omega=2.0 / 3.0, k=1, nu_coarse=2)
+    want = p.download(0, _lib.SLOT_V, 0).reshape(128, 128)
+    p.close()
+    assert np.array_equal(v, want)
 
 
 def test_lexwave_isa_keeps_load_destinations_in_place():

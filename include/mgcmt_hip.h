@@ -138,6 +138,9 @@ int mgcmt_coarse_solve(mgcmt_plan* plan, int level, int k, void* stream);
  * argument was the 0 / 1 Gram-Schmidt switch before, which keeps its meaning). */
 #define MGCMT_CYCLE_GRAM_SCHMIDT 1
 #define MGCMT_CYCLE_ZERO_START 2
+/* State after a cycle: V[level] holds the new iterate and F[l] of every coarser fused level the restricted residual;
+ * the iterates V[l] of the coarser levels are scratch (a level run inside a two-level pass, MGCMT_OPT_TWO_LEVEL, is
+ * never written).  A caller that wants a coarse iterate sets MGCMT_OPT_TWO_LEVEL to 0. */
 int mgcmt_vcycle(mgcmt_plan* plan, int level, int nu1, int nu2, int nu_coarse, int kind, double omega, int k,
                  int cycle_flags, void* stream);
 /* twogrid (:331-371): exact solve of (R A P - mu I) on level+1 */
@@ -344,6 +347,10 @@ typedef enum mgcmt_option {
                                its Cholesky factor R, Q = A R^-1 — what MGCMTProcessor.py:44-50 computes in exact arithmetic),
                                with the column-by-column kernels taking over on the device where the columns' condition
                                number would let the difference (cond^2 eps) show; 0: column by column always */
+  MGCMT_OPT_TWO_LEVEL = 8,  /* default 1: on constant 5-point levels of >= 2^22 points smoothed by weighted Jacobi, the level and its
+                               Galerkin level below run as ONE down-leg and ONE up-leg launch (fused2_kernel.h; 2 sweeps per leg
+                               on the level below, a no-store last down pass on the level itself, no Gram-Schmidt, no strips):
+                               the same arithmetic, the same bits; 2: on every eligible level; 0: never */
   MGCMT_OPT_TAIL = 4        /* default 1: the 2-D levels of at most 32 x 32 points below a cycle's top level, coarse solve
                                included, run as ONE launch (needs MGCMT_OPT_FUSED; not with Gram-Schmidt): a dense product
                                with the tail's matrix — the sub-cycle is linear in its right-hand side for fixed shift,

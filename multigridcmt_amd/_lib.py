@@ -29,6 +29,7 @@ OPT_LEX_CHAIN = 6
 OPT_MGS_BLOCK = 7
 OPT_GRAPH = 2
 OPT_RECOMPUTE = 3
+OPT_TWO_LEVEL = 8
 
 
 class MgcmtError(RuntimeError):

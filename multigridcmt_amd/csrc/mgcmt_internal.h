@@ -110,6 +110,14 @@ void launch_fused(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, K
                   double omega, int multicolour, int nsweep, int mode, int npre, long row_lo, long row_hi, long last_row, int k,
                   long rows_override = 0, long out_lo = 0, long out_hi = -1, long out_lo2 = 0, long out_hi2 = 0);
 
+// two-level fused passes (fused2_kernel.h, kernels_fused2_op5.hip): a constant 5-point level (op0, nr x nc, weighted
+// Jacobi) and its Galerkin coarsening (op1, nine_const, cnr x cnc) in one launch; level l+2 has c2nc columns.
+// up = 0: nf sweeps from v (zero_in: v is zero) -> residual -> F[l+1] (f1) -> 2 sweeps of level l+1 from zero ->
+// residual -> F[l+2] (c2).  up = 1: level l+1 recomputes its 2 pre-sweeps from zero, adds P V[l+2] (c2), 2 sweeps;
+// level l recomputes nf pre-sweeps from v, adds P of that, 2 sweeps -> vout.  V[l+1] is neither read nor written.
+void launch_fused2(hipStream_t s, int up, int nf, int zero_in, const KOp& op0, const KOp& op1, long nr, long nc, long cnr, long cnc,
+                   long c2nc, KVec v, KVec f, KVec vout, KVec f1, KVec c2, const double* shifts, double omega, int k, long rows_override);
+
 // vector algebra; scalar results / inputs live in device memory so nothing syncs with the host
 void launch_fill(hipStream_t s, double* p, long n, double value);
 // y += (alpha_scale * alpha_dev[0] / (den_dev ? den_dev[0] : 1)) * x ;  x /= (use_sqrt ? sqrt(s_dev[0]) : s_dev[0])

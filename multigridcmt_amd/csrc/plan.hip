@@ -582,6 +582,76 @@ int up_leg(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, hipStrea
   return smooth_impl(p, l, kind, nu, omega, k, s);
 }
 
+// ---- two-level passes (fused2_kernel.h) ---------------------------------------------------------
+
+// sweeps of the last down-leg pass of a fused level smoothed nu times (the passes before it take pass_sweeps each)
+int last_pass_sweeps(const mgcmt_plan* p, int l, int kind, int nu) {
+  int left = nu;
+  while (left > pass_sweeps(p, l, kind, left)) left -= pass_sweeps(p, l, kind, left);
+  return left;
+}
+
+// Level l and l+1 run as ONE down-leg and ONE up-leg launch: a constant 5-point level with weighted Jacobi, its
+// nine_const Galerkin coarsening below, both whole (no strip), level l+1 above the tail / coarse solve, 2 sweeps per
+// leg on level l+1, at least 2 post-sweeps on level l, and level l's last down pass a no-store (recompute) pass.  No
+// Gram-Schmidt (level l+1's would run between the two up passes).  Otherwise the cycle runs today's passes.
+bool two_level_ok(const mgcmt_plan* p, int l, int bottom, int kind, int nu, int nu_up, int nu_coarse, int gram_schmidt) {
+  if (p->two_level == 0 || gram_schmidt || kind != MGCMT_WJACOBI || p->comm || p->dim != 2) return false;
+  if (l + 1 >= bottom || nu < 1 || nu_up < 2 || nu_coarse != 2) return false;
+  if (!fused_level(p, l, kind) || !fused_level(p, l + 1, kind)) return false;
+  const Level &L0 = p->levels[l], &L1 = p->levels[l + 1], &L2 = p->levels[l + 2];
+  if (!L0.dA.k.five_point || L0.dA.k.one_d || !L1.dA.k.nine_const) return false;
+  for (const Level* L : {&L0, &L1, &L2})
+    if (L->nr != L->gr || L->r0 != 0) return false;
+  if (L1.gr * 2 != L0.gr || L1.gc * 2 != L0.gc || L2.gr * 2 != L1.gr || L2.gc * 2 != L1.gc) return false;
+  const int nf = last_pass_sweeps(p, l, kind, nu);
+  if (!p->use_recompute || nf > fused_max_recompute(L0.dA.k, 0, pass_sweeps(p, l, kind, nu_up))) return false;
+  // 1: where the fine level is bandwidth-bound (the recompute threshold); 2: on every eligible level (tests)
+  return p->two_level == 2 || p->interior(l) >= (1L << 22);
+}
+
+int two_level_launch(mgcmt_plan* p, int l, int up, int nf, bool zero_in, double omega, int k, hipStream_t s) {
+  const Level &L0 = p->levels[l], &L1 = p->levels[l + 1], &L2 = p->levels[l + 2];
+  launch_fused2(s, up, nf, zero_in ? 1 : 0, L0.dA.k, L1.dA.k, L0.gr, L0.gc, L1.gr, L1.gc, L2.gc, p->kvec(l, MGCMT_SLOT_V),
+                p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->kvec(l + 1, MGCMT_SLOT_F),
+                p->kvec(l + 2, up ? MGCMT_SLOT_V : MGCMT_SLOT_F), p->d_shifts, omega, k, p->fused_rows);
+  return post_launch();
+}
+
+// down legs of levels l and l+1: level l's passes but the last, then the two-level pass (F[l+1], F[l+2] written, V[l]
+// and V[l+1] not).  nf: out — level l's sweeps the up pass recomputes; still_zero: out — V[l] is still "zero, uncleared"
+int two_level_down(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, bool zero_in, hipStream_t s, int* nf, bool* still_zero) {
+  for (int m = l; m <= l + 2; ++m) {
+    MG_TRY(ensure_slot(p, m, MGCMT_SLOT_V));
+    MG_TRY(ensure_slot(p, m, MGCMT_SLOT_F));
+    MG_TRY(ensure_slot(p, m, MGCMT_SLOT_T));
+  }
+  int left = nu, zi = zero_in ? 4 : 0;
+  while (left > pass_sweeps(p, l, kind, left)) {
+    const int n = pass_sweeps(p, l, kind, left);
+    MG_TRY(fused_pass(p, l, kind, n, omega, zi, k, s));
+    zi = 0;
+    left -= n;
+  }
+  MG_TRY(two_level_launch(p, l, 0, left, zi != 0, omega, k, s));
+  *nf = left;
+  *still_zero = zi != 0;
+  return MGCMT_OK;
+}
+
+// up legs of levels l+1 and l: the two-level pass (V[l] -> V', level l+1's correction and smoothing in registers),
+// then level l's remaining post-smoothing passes
+int two_level_up(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, hipStream_t s, int nf, bool still_zero) {
+  MG_TRY(two_level_launch(p, l, 1, nf, still_zero, omega, k, s));
+  std::swap(p->levels[l].base[MGCMT_SLOT_V], p->levels[l].base[MGCMT_SLOT_T]);
+  for (int left = nu - 2; left > 0;) {
+    const int n = pass_sweeps(p, l, kind, left);
+    MG_TRY(fused_pass(p, l, kind, n, omega, 0, k, s));
+    left -= n;
+  }
+  return post_launch();
+}
+
 // ---- Gram-Schmidt -------------------------------------------------------------------------------
 
 int gramschmidt_impl(mgcmt_plan* p, int l, int slot, int k, int modified, hipStream_t s) {
@@ -769,9 +839,17 @@ int vcycle_body(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int k
   const int bottom = lt > 0 ? lt : last;  // the levels level .. bottom-1 run as fused passes / single launches
   std::vector<int> recompute(last + 1, 0);
   std::vector<char> still_zero(last + 1, 0);
+  std::vector<char> paired(last + 1, 0);  // level l and l + 1 run as two-level passes
   for (int l = level; l < bottom; ++l) {
     const int nu_up = l == level ? nu2 : nu_coarse;
     bool sz = false;
+    if (two_level_ok(p, l, bottom, kind, l == level ? nu1 : nu_coarse, nu_up, nu_coarse, gram_schmidt)) {
+      MG_TRY(two_level_down(p, l, kind, l == level ? nu1 : nu_coarse, omega, k, l > level || zero_start, s, &recompute[l], &sz));
+      still_zero[l] = sz;
+      paired[l] = 1;
+      ++l;  // level l + 1's down leg ran inside that launch
+      continue;
+    }
     // the up-leg can only recompute the unstored sweeps if it runs a fused pass itself (>= 1 post-smoothing sweep)
     MG_TRY(down_leg(p, l, kind, l == level ? nu1 : nu_coarse, omega, k, l > level || zero_start, s, nu_up >= 1 ? &recompute[l] : nullptr, &sz, nu_up));
     still_zero[l] = sz;
@@ -779,6 +857,11 @@ int vcycle_body(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int k
   if (lt > 0) MG_TRY(run_tail(p, lt, kind, nu_coarse, omega, k, s));
   else MG_TRY(coarse_solve_impl(p, last, k, s));
   for (int l = bottom - 1; l >= level; --l) {
+    if (l > level && paired[l - 1]) continue;  // runs inside level l - 1's up pass
+    if (paired[l]) {
+      MG_TRY(two_level_up(p, l, kind, l == level ? nu2 : nu_coarse, omega, k, s, recompute[l], still_zero[l] != 0));
+      continue;
+    }
     MG_TRY(up_leg(p, l, kind, l == level ? nu2 : nu_coarse, omega, k, s, recompute[l], still_zero[l] != 0));
     if (gram_schmidt) MG_TRY(gramschmidt_impl(p, l, MGCMT_SLOT_V, k, 1, s));
   }
@@ -1681,6 +1764,11 @@ int mgcmt_plan_set_option(mgcmt_plan* p, int option, int value) {
   if (option == MGCMT_OPT_RECOMPUTE) {
     p->use_recompute = value != 0;
     p->force_recompute = value == 2;
+    p->graphs_invalidate();
+    return MGCMT_OK;
+  }
+  if (option == MGCMT_OPT_TWO_LEVEL) {
+    p->two_level = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
     p->graphs_invalidate();
     return MGCMT_OK;
   }

@@ -89,6 +89,7 @@ struct mgcmt_plan {
     bool valid = false;
   } tailmat;
   bool use_recompute = true;  // down-leg passes skip storing V', up-leg passes recompute it (fused_kernel.h)
+  int two_level = 1;  // pair a 5-point level with its Galerkin level below in one down and one up launch: 1 from 2^22 points, 2 always, 0 never
   bool force_recompute = false;  // ... on every fused level, not only the bandwidth-bound ones (tests)
   // HIP-graph replay of whole cycles (mgcmt_vcycle): the launch sequence of a cycle is fixed by its
   // parameters and by which of the two buffers of every level currently is "V", so it is captured once per

@@ -23,6 +23,18 @@
  *     laplacian(n,"2d") = I(x)L + L(x)I is two (MGCMTStencilMaker.py:23-24).  Galerkin coarse
  *     operators R*A*P (MGCMTSolver.py:318) keep this form with X_m <- R1 X_m P1, Y_m <- R1 Y_m P1,
  *     which the library computes at plan creation.
+ *   - 3-D grids (mgcmt_plan_create3d, ABI 7): a level is g x g x g points with index idx = z*g^2 + y*g + x (x fastest,
+ *     the ordering of kron(A, kron(B, C))), stored as g z-planes of g^2 points with one zero halo plane above and below
+ *     every vector.  The operator is  A = sum_m X_m (x) Y_m (x) Z_m - shift * I  with tridiagonal factors over z, y
+ *     and x; laplacian(n,"3d") = kronsum(kronsum(L, L), L) is three terms (L(x)I(x)I, I(x)L(x)I, I(x)I(x)L).  With
+ *     P = P1 (x) P1 (x) P1 (trilinear interpolation, interpolation(c, f, "3d") = kron(S, kron(S, S))) and
+ *     R = (1/8) P^T = R1 (x) R1 (x) R1 (full weighting), every Galerkin level keeps three-factor terms (27-point
+ *     stencils).  Multicolour Gauss-Seidel uses the colours (z%2, y%2, x%2) in the order (0,0,1), (0,1,0), (1,0,0),
+ *     (1,1,1), (0,0,0), (0,1,1), (1,0,1), (1,1,0): odd coordinate sum first, i.e. red-black on the 7-point fine level.
+ *     On a 3-D plan mgcmt_plan_level_shape reports rows = z-planes (g_l) and cols = points per plane (g_l^2), and
+ *     mgcmt_plan_get_factors takes which = 0 (z), 1 (y) or 2 (x).  Weighted Jacobi and multicolour Gauss-Seidel are the
+ *     3-D smoothers; the entries with no 3-D form (lexicographic smoothers, twogrid, the Rayleigh-quotient family,
+ *     mass operators, sharding, fused-pass and timing entries) return MGCMT_ERR_UNSUPPORTED on a 3-D plan.
  */
 #ifndef MGCMT_HIP_H
 #define MGCMT_HIP_H
@@ -33,7 +45,7 @@
 extern "C" {
 #endif
 
-#define MGCMT_ABI_VERSION 6
+#define MGCMT_ABI_VERSION 7
 #define MGCMT_MAX_TERMS 4
 #define MGCMT_HALO_ROWS 16 /* rows of halo kept above and below every vector of a 2-D level (a 1-D level keeps one: its
                               "row" is the whole vector); how many of them a sharded cycle fills: mgcmt_plan_level_halo */
@@ -89,6 +101,22 @@ int mgcmt_device_name(int device, char* buf, int buflen);
 /* hierarchy: levels, Galerkin factors (R*A*P, MGCMTSolver.py:318), vector storage */
 int mgcmt_plan_create(const mgcmt_plan_desc* desc, mgcmt_plan** out);
 int mgcmt_plan_destroy(mgcmt_plan* plan);
+
+/* A 3-D plan (see "3-D grids" above): one operator sum_m zfac_m (x) yfac_m (x) xfac_m on g^3 points, levels
+ * g^3 -> (g/2)^3 -> ... -> lowest^3 (lowest <= 16: (A - mu I) of the coarsest level is factored directly).  The
+ * plan is used through the same entries as a 2-D one (mgcmt_vcycle, mgcmt_smooth, mgcmt_apply, ...). */
+typedef struct mgcmt_plan3d_desc {
+  int32_t nterms;       /* Kronecker terms of A, 1 .. MGCMT_MAX_TERMS */
+  int32_t nvec;         /* number of simultaneous vectors, >= 1 */
+  int64_t g;            /* fine grid size per direction (power of two) */
+  int64_t lowest;       /* grid size of the direct solve (power of two, 2 .. 16) */
+  const double* zfac;   /* [nterms][3][g] factors over z (slowest index): lower, diag, upper */
+  const double* yfac;   /* [nterms][3][g] factors over y */
+  const double* xfac;   /* [nterms][3][g] factors over x (fastest index) */
+  int32_t device;       /* HIP device ordinal */
+  int32_t reserved;
+} mgcmt_plan3d_desc;
+int mgcmt_plan_create3d(const mgcmt_plan3d_desc* desc, mgcmt_plan** out);
 int mgcmt_plan_num_levels(const mgcmt_plan* plan, int* levels);
 int mgcmt_plan_level_shape(const mgcmt_plan* plan, int level, int64_t* rows, int64_t* cols, int64_t* row_begin);
 /* host copy of a level's factors, [nterms][3][n] with n = global rows (which=0) or cols (which=1) */

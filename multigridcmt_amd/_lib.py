@@ -20,7 +20,7 @@ HALO_ROWS = 16         # 2-D levels (a 1-D level keeps one halo "row"); exchange
 RQ_HISTORY = 4096      # MGCMT_RQ_HISTORY: Rayleigh quotients Plan.rq_line_step can record on the device
 MAX_TERMS = 4
 MAX_VEC = 32
-ABI_VERSION = 6
+ABI_VERSION = 7
 OPT_FUSED = 0
 OPT_FUSED_ROWS = 1
 OPT_TAIL = 4
@@ -49,6 +49,14 @@ class PlanDesc(ctypes.Structure):
 _dp = POINTER(c_double)
 
 
+class Plan3dDesc(ctypes.Structure):
+    """mgcmt_plan3d_desc: a 3-D plan, A = sum_m zfac_m (x) yfac_m (x) xfac_m on g^3 points (idx = z g^2 + y g + x)."""
+    _fields_ = [
+        ("nterms", c_int32), ("nvec", c_int32), ("g", c_int64), ("lowest", c_int64),
+        ("zfac", _dp), ("yfac", _dp), ("xfac", _dp), ("device", c_int32), ("reserved", c_int32),
+    ]
+
+
 class P2POp(ctypes.Structure):
     _fields_ = [("ptr", c_void_p), ("count", c_int64), ("peer", c_int32), ("is_send", c_int32)]
 
@@ -69,6 +77,7 @@ _SIGNATURES = {
     "mgcmt_device_count": (c_int, [POINTER(c_int)]),
     "mgcmt_device_name": (c_int, [c_int, ctypes.c_char_p, c_int]),
     "mgcmt_plan_create": (c_int, [POINTER(PlanDesc), POINTER(c_void_p)]),
+    "mgcmt_plan_create3d": (c_int, [POINTER(Plan3dDesc), POINTER(c_void_p)]),
     "mgcmt_plan_destroy": (c_int, [c_void_p]),
     "mgcmt_plan_num_levels": (c_int, [c_void_p, POINTER(c_int)]),
     "mgcmt_plan_level_shape": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),

@@ -15,7 +15,7 @@ namespace mgcmt {
 namespace {
 
 constexpr int kBandThreads = 256;
-constexpr int kMaxKl = 130;
+constexpr int kMaxKl = 280;  // 2-D coarsest levels up to 128 x 128 (kl 129), 3-D up to 16^3 (kl 273)
 
 __device__ __forceinline__ double& band_at(double* ab, int width, int kl, long r, long c) { return ab[r * width + (c - r + kl)]; }
 

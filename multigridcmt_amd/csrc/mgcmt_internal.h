@@ -47,6 +47,19 @@ struct KOp {
   double t_lo, t_di, t_up, t_last;
 };
 
+// Operator of a 3-D level (kernels_3d.hip):  A = sum_m X_m (x) Y_m (x) Z_m  over z, y, x (shift applied separately).
+// X[m] / Y[m] / Z[m] point at [lower | diag | upper] of n entries each (no halo).  seven: constant 7-point operator
+// (centre c0, one coefficient per direction and side) — the fine level of a scaled / shifted Laplacian.
+struct K3Op {
+  int nterms;
+  long n;  // points per axis
+  const double* X[kMaxTerms];
+  const double* Y[kMaxTerms];
+  const double* Z[kMaxTerms];
+  int seven;
+  double c0, czm, czp, cym, cyp, cxm, cxp;
+};
+
 // A batch of vectors on one level: interior pointer of vector 0, elements between vectors.
 struct KVec {
   double* p;
@@ -221,5 +234,19 @@ void launch_band_solve(hipStream_t s, KBand b, KVec rhs, KVec x, int k);
 // explicit inverse (n <= 1024 unknowns) and the dense solve x = inv * rhs that replaces the substitutions
 void launch_band_invert(hipStream_t s, KBand b, double* inv, long inv_stride, int k);
 void launch_dense_solve(hipStream_t s, long n, const double* inv, long inv_stride, KVec rhs, KVec x, int k);
+
+// 3-D levels (kernels_3d.hip): g^3 points, idx = z g^2 + y g + x; vectors as for the flat kernels (interior pointer, stride)
+void launch3_apply(hipStream_t s, const K3Op& op, KVec src, KVec dst, const double* shifts, int k);
+void launch3_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
+// one multicolour sweep in place: colours (z%2, y%2, x%2) in the order (0,0,1), (0,1,0), (1,0,0), (1,1,1), (0,0,0), (0,1,1),
+// (1,0,1), (1,1,0) (two parity stages on a 7-point operator, which is the same sweep)
+void launch3_mc_sweep(hipStream_t s, const K3Op& op, KVec v, KVec f, const double* shifts, double omega, int k);
+// fc <- R (f - (A - mu) v), vc <- 0 (one pass; the fine residual is not stored)
+void launch3_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k);
+void launch3_restrict(hipStream_t s, const K3Op& fine, KVec src, KVec dst, int k);
+void launch3_prolong(hipStream_t s, long n, KVec e, KVec dst, int accumulate, int k);
+// vout <- one weighted-Jacobi sweep from w = vin + P e (w is not stored)
+void launch3_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
+void launch3_band_assemble(hipStream_t s, const K3Op& op, const double* shifts, KBand b, int k);
 
 }  // namespace mgcmt

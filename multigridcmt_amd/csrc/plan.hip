@@ -21,6 +21,11 @@ int fail(int code, const std::string& msg) {
   g_last_error = msg;
   return code;
 }
+
+int unsupported_3d(const mgcmt_plan* p, const char* what) {
+  if (p && p->dim == 3) return fail(MGCMT_ERR_UNSUPPORTED, std::string(what) + " is not available on a 3-D plan");
+  return MGCMT_OK;
+}
 }  // namespace mgcmt
 
 namespace {
@@ -235,6 +240,66 @@ int upload_op(const HostOp& h, const Level& L, int dim, DevOp* d) {
   return MGCMT_OK;
 }
 
+// a 3-D level's factors on the device, and the constant 7-point form where every factor is Toeplitz and the summed
+// stencil has no entry off the three axes
+int upload_op3(const HostOp& h, int64_t n, DevOp* d) {
+  K3Op& k = d->k3;
+  k = K3Op{};
+  k.nterms = h.nterms;
+  k.n = (long)n;
+  auto up = [&](const Tri& t, const double** dst) -> int {
+    double* q = nullptr;
+    MG_HIP(hipMalloc((void**)&q, t.a.size() * sizeof(double)));
+    d->owned.push_back(q);
+    MG_HIP(hipMemcpy(q, t.a.data(), t.a.size() * sizeof(double), hipMemcpyHostToDevice));
+    *dst = q;
+    return MGCMT_OK;
+  };
+  for (int m = 0; m < h.nterms; ++m) {
+    MG_TRY(up(h.X[m], &k.X[m]));
+    MG_TRY(up(h.Y[m], &k.Y[m]));
+    MG_TRY(up(h.Z[m], &k.Z[m]));
+  }
+  auto toeplitz = [](const Tri& t, double* f) {
+    f[1] = t.di(0);
+    f[0] = t.n > 1 ? t.lo(1) : 0.0;
+    f[2] = t.n > 1 ? t.up(0) : 0.0;
+    for (int64_t i = 0; i < t.n; ++i) {
+      if (t.di(i) != f[1]) return false;
+      if (i > 0 && t.lo(i) != f[0]) return false;
+      if (i + 1 < t.n && t.up(i) != f[2]) return false;
+    }
+    return true;
+  };
+  double c[3][3][3] = {};
+  bool all = h.nterms > 0 && n >= 2;
+  for (int m = 0; m < h.nterms && all; ++m) {
+    double fz[3], fy[3], fx[3];
+    if (!toeplitz(h.X[m], fz) || !toeplitz(h.Y[m], fy) || !toeplitz(h.Z[m], fx)) {
+      all = false;
+      break;
+    }
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b)
+        for (int e = 0; e < 3; ++e) c[a][b][e] += fz[a] * fy[b] * fx[e];
+  }
+  for (int a = 0; a < 3 && all; ++a)
+    for (int b = 0; b < 3; ++b)
+      for (int e = 0; e < 3; ++e)
+        if ((a != 1) + (b != 1) + (e != 1) >= 2 && c[a][b][e] != 0.0) all = false;
+  if (all) {
+    k.seven = 1;
+    k.c0 = c[1][1][1];
+    k.czm = c[0][1][1];
+    k.czp = c[2][1][1];
+    k.cym = c[1][0][1];
+    k.cyp = c[1][2][1];
+    k.cxm = c[1][1][0];
+    k.cxp = c[1][1][2];
+  }
+  return MGCMT_OK;
+}
+
 }  // namespace
 namespace mgcmt {
 int ensure_slot(mgcmt_plan* p, int l, int slot) {
@@ -391,7 +456,10 @@ int lex_wave_check(mgcmt_plan* p) {
   return MGCMT_OK;
 }
 
+int smooth3(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, hipStream_t s);
+
 int smooth_impl(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, hipStream_t s) {
+  if (p->dim == 3) return smooth3(p, l, kind, nu, omega, k, s);
   Level& L = p->levels[l];
   MG_TRY(ensure_slot(p, l, MGCMT_SLOT_V));
   MG_TRY(ensure_slot(p, l, MGCMT_SLOT_F));
@@ -451,6 +519,11 @@ int residual_restrict_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {
   MG_TRY(ensure_slot(p, l, MGCMT_SLOT_T));
   MG_TRY(ensure_slot(p, l + 1, MGCMT_SLOT_V));
   MG_TRY(ensure_slot(p, l + 1, MGCMT_SLOT_F));
+  if (p->dim == 3) {  // one pass: F[l+1] and V[l+1] = 0 written, no fine residual stored
+    launch3_residual_restrict(s, p->levels[l].dA.k3, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l + 1, MGCMT_SLOT_F),
+                              p->kvec(l + 1, MGCMT_SLOT_V), p->d_shifts, k);
+    return post_launch();
+  }
   launch_residual(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, k);
   launch_restrict(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l, MGCMT_SLOT_T), p->kvec(l + 1, MGCMT_SLOT_F), k);
   for (int q = 0; q < k; ++q) launch_fill(s, p->kvec(l + 1, MGCMT_SLOT_V, q).p, p->interior(l + 1), 0.0);
@@ -461,7 +534,8 @@ int prolong_correct_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {
   if (l + 1 >= (int)p->levels.size()) return fail(MGCMT_ERR_INVALID, "no coarser level");
   MG_TRY(ensure_slot(p, l, MGCMT_SLOT_V));
   MG_TRY(ensure_slot(p, l + 1, MGCMT_SLOT_V));
-  launch_prolong(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l + 1, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_V), 1, k);
+  if (p->dim == 3) launch3_prolong(s, p->levels[l].gr, p->kvec(l + 1, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_V), 1, k);
+  else launch_prolong(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l + 1, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_V), 1, k);
   return post_launch();
 }
 
@@ -474,8 +548,9 @@ int ensure_coarse_ready(mgcmt_plan* p, int l, int k, hipStream_t s) {
   MG_TRY(ensure_slot(p, l, MGCMT_SLOT_F));
   BandState& B = L.band;
   const long n = (long)L.nr * L.gc;
-  const int kl = L.nr == 1 ? 1 : (int)L.gc + 1;
-  if (kl > 129) return fail(MGCMT_ERR_UNSUPPORTED, "lowest_level too large for the direct solve (2-D: at most 128)");
+  const int kl = p->dim == 3 ? (int)(L.gc + L.gr + 1) : L.nr == 1 ? 1 : (int)L.gc + 1;
+  if (p->dim == 3 && kl > 273) return fail(MGCMT_ERR_UNSUPPORTED, "lowest_level too large for the direct solve (3-D: at most 16)");
+  if (p->dim != 3 && kl > 129) return fail(MGCMT_ERR_UNSUPPORTED, "lowest_level too large for the direct solve (2-D: at most 128)");
   if (!B.b.ab) {
     B.b.n = n;
     B.b.kl = kl;
@@ -490,7 +565,8 @@ int ensure_coarse_ready(mgcmt_plan* p, int l, int k, hipStream_t s) {
   if (same)
     for (int q = 0; q < k; ++q) same = same && B.shifts[q] == p->h_shifts[q];
   if (!same) {
-    launch_band_assemble(s, p->kgrid(l), L.dA.k, p->d_shifts, B.b, k);
+    if (p->dim == 3) launch3_band_assemble(s, L.dA.k3, p->d_shifts, B.b, k);
+    else launch_band_assemble(s, p->kgrid(l), L.dA.k, p->d_shifts, B.b, k);
     launch_band_factor(s, B.b, k);
     if (B.inv) launch_band_invert(s, B.b, B.inv, n * n, k);
     B.valid = true;
@@ -714,7 +790,8 @@ int ensure_coarse_factor(mgcmt_plan* p, int l, int k, hipStream_t s) {
     for (int q = 0; q < k; ++q) same = same && B.shifts[q] == p->h_shifts[q];
   if (same) return MGCMT_OK;
   if (!B.b.ab) return MGCMT_OK;  // first use: coarse_solve_impl allocates and factors
-  launch_band_assemble(s, p->kgrid(l), L.dA.k, p->d_shifts, B.b, k);
+  if (p->dim == 3) launch3_band_assemble(s, L.dA.k3, p->d_shifts, B.b, k);
+  else launch_band_assemble(s, p->kgrid(l), L.dA.k, p->d_shifts, B.b, k);
   launch_band_factor(s, B.b, k);
   if (B.inv) launch_band_invert(s, B.b, B.inv, (long)B.b.n * B.b.n, k);
   B.valid = true;
@@ -828,8 +905,71 @@ int ensure_tail_for_cycle(mgcmt_plan* p, int level, int nu_coarse, int kind, dou
   return MGCMT_OK;
 }
 
+// ---- 3-D levels (kernels_3d.hip) -----------------------------------------------------------------
+
+int smooth3(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, hipStream_t s) {
+  Level& L = p->levels[l];
+  if (kind == MGCMT_GS_LEX || kind == MGCMT_SOR_LEX)
+    return fail(MGCMT_ERR_UNSUPPORTED, "lexicographic smoothers are not available on 3-D levels (MGCMT_WJACOBI and MGCMT_GS_MC are)");
+  if (kind != MGCMT_WJACOBI && kind != MGCMT_GS_MC) return fail(MGCMT_ERR_INVALID, "unknown smoother kind");
+  MG_TRY(ensure_slot(p, l, MGCMT_SLOT_V));
+  MG_TRY(ensure_slot(p, l, MGCMT_SLOT_F));
+  if (kind == MGCMT_WJACOBI) {
+    MG_TRY(ensure_slot(p, l, MGCMT_SLOT_T));
+    for (int it = 0; it < nu; ++it) {
+      launch3_wjacobi(s, L.dA.k3, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, omega, k);
+      std::swap(L.base[MGCMT_SLOT_V], L.base[MGCMT_SLOT_T]);
+    }
+  } else {
+    for (int it = 0; it < nu; ++it) launch3_mc_sweep(s, L.dA.k3, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->d_shifts, omega, k);
+  }
+  return post_launch();
+}
+
+// prolongation + correction + post-smoothing; with weighted Jacobi the correction rides in the first sweep's pass
+int up_leg3(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, hipStream_t s) {
+  if (kind == MGCMT_WJACOBI && nu >= 1) {
+    Level& L = p->levels[l];
+    MG_TRY(ensure_slot(p, l, MGCMT_SLOT_V));
+    MG_TRY(ensure_slot(p, l, MGCMT_SLOT_F));
+    MG_TRY(ensure_slot(p, l, MGCMT_SLOT_T));
+    MG_TRY(ensure_slot(p, l + 1, MGCMT_SLOT_V));
+    launch3_prolong_jacobi(s, L.dA.k3, p->kvec(l + 1, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T),
+                           p->d_shifts, omega, k);
+    std::swap(L.base[MGCMT_SLOT_V], L.base[MGCMT_SLOT_T]);
+    MG_TRY(post_launch());
+    return smooth3(p, l, kind, nu - 1, omega, k, s);
+  }
+  MG_TRY(prolong_correct_impl(p, l, k, s));
+  return smooth3(p, l, kind, nu, omega, k, s);
+}
+
+// the 3-D V-cycle: per level nu sweeps, one residual + restriction pass (the coarse iterate zero-started), the direct
+// solve on the coarsest level, then prolongation + correction + sweeps (+ modified Gram-Schmidt of the k columns)
+int vcycle3_body(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int kind, double omega, int k, int cycle_flags, hipStream_t s) {
+  if (kind == MGCMT_GS_LEX || kind == MGCMT_SOR_LEX)
+    return fail(MGCMT_ERR_UNSUPPORTED, "lexicographic smoothers are not available on 3-D levels (MGCMT_WJACOBI and MGCMT_GS_MC are)");
+  if (kind != MGCMT_WJACOBI && kind != MGCMT_GS_MC) return fail(MGCMT_ERR_INVALID, "unknown smoother kind");
+  const int last = (int)p->levels.size() - 1;
+  if (cycle_flags & MGCMT_CYCLE_ZERO_START) {
+    MG_TRY(ensure_slot(p, level, MGCMT_SLOT_V));
+    for (int q = 0; q < k; ++q) launch_fill(s, p->kvec(level, MGCMT_SLOT_V, q).p, p->interior(level), 0.0);
+  }
+  for (int l = level; l < last; ++l) {
+    MG_TRY(smooth3(p, l, kind, l == level ? nu1 : nu_coarse, omega, k, s));
+    MG_TRY(residual_restrict_impl(p, l, k, s));
+  }
+  MG_TRY(coarse_solve_impl(p, last, k, s));
+  for (int l = last - 1; l >= level; --l) {
+    MG_TRY(up_leg3(p, l, kind, l == level ? nu2 : nu_coarse, omega, k, s));
+    if (cycle_flags & MGCMT_CYCLE_GRAM_SCHMIDT) MG_TRY(gramschmidt_impl(p, l, MGCMT_SLOT_V, k, 1, s));
+  }
+  return MGCMT_OK;
+}
+
 int vcycle_body(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int kind, double omega, int k, int cycle_flags,
                 hipStream_t s) {
+  if (p->dim == 3) return vcycle3_body(p, level, nu1, nu2, nu_coarse, kind, omega, k, cycle_flags, s);
   const int gram_schmidt = cycle_flags & MGCMT_CYCLE_GRAM_SCHMIDT;
   // MGCMT_CYCLE_ZERO_START: the caller vouches that the iterate on `level` is zero — the first pass takes that as a
   // flag (V is neither cleared nor read; where no fused pass runs, down_leg clears it)
@@ -998,6 +1138,84 @@ int mgcmt_plan_create(const mgcmt_plan_desc* d, mgcmt_plan** out) {
   return MGCMT_OK;
 }
 
+int mgcmt_plan_create3d(const mgcmt_plan3d_desc* d, mgcmt_plan** out) {
+  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!is_pow2(d->g) || !is_pow2(d->lowest) || d->lowest > d->g) return fail(MGCMT_ERR_INVALID, "g and lowest must be powers of two with lowest <= g");
+  if (d->g < 2) return fail(MGCMT_ERR_INVALID, "Length of start vector is not a power of 2");
+  if (d->lowest < 2) return fail(MGCMT_ERR_INVALID, "lowest must be at least 2");
+  if (d->lowest > 16) return fail(MGCMT_ERR_INVALID, "lowest must be at most 16 on a 3-D plan (the coarsest level is solved directly)");
+  if (d->nterms < 1 || d->nterms > kMaxTerms) return fail(MGCMT_ERR_INVALID, "nterms out of range");
+  if (!d->xfac || !d->yfac || !d->zfac) return fail(MGCMT_ERR_INVALID, "missing factor arrays");
+  if (d->nvec < 1 || d->nvec > kMaxVec) return fail(MGCMT_ERR_INVALID, "nvec out of range (1..32)");
+  MG_HIP(hipSetDevice(d->device));
+
+  mgcmt_plan* p = new mgcmt_plan();
+  p->dim = 3;
+  p->nvec = d->nvec;
+  p->device = d->device;
+  p->g = d->g;
+  p->lowest = d->lowest;
+  p->h_shifts.assign(kMaxVec, 0.0);
+  {
+    const char* mb = getenv("MGCMT_MGS_BLOCK_MIN");
+    if (mb && atol(mb) > 1) p->mgs_block_min = atol(mb);
+  }
+  int nlev = 1;
+  for (int64_t s = d->g; s > d->lowest; s >>= 1) ++nlev;
+  p->levels.resize(nlev);
+  auto load = [&](const double* src, int m) {
+    Tri t;
+    t.n = d->g;
+    t.a.assign(src + (size_t)m * 3 * d->g, src + (size_t)(m + 1) * 3 * d->g);
+    return t;
+  };
+  for (int l = 0; l < nlev; ++l) {
+    Level& L = p->levels[l];
+    const int64_t n = d->g >> l;
+    L.gr = L.nr = n;  // z-planes
+    L.gc = n * n;     // points per plane
+    L.r0 = 0;
+    L.halo = 1;       // one zero plane above and below
+    L.stride = ((L.nr + 2 * L.halo) * L.gc + 31) / 32 * 32;
+    HostOp& h = L.hA;
+    h.nterms = d->nterms;
+    h.X.resize(d->nterms);
+    h.Y.resize(d->nterms);
+    h.Z.resize(d->nterms);
+    for (int m = 0; m < d->nterms; ++m) {
+      if (l == 0) {
+        h.X[m] = load(d->zfac, m);
+        h.Y[m] = load(d->yfac, m);
+        h.Z[m] = load(d->xfac, m);
+      } else {  // R A P with P = P1 (x) P1 (x) P1: each factor coarsened on its own (plan.hip: galerkin)
+        const HostOp& f = p->levels[l - 1].hA;
+        h.X[m] = galerkin(f.X[m]);
+        h.Y[m] = galerkin(f.Y[m]);
+        h.Z[m] = galerkin(f.Z[m]);
+      }
+    }
+    const int rc = upload_op3(h, n, &L.dA);
+    if (rc != MGCMT_OK) {
+      mgcmt_plan_destroy(p);
+      return rc;
+    }
+  }
+  hipError_t e = hipMalloc((void**)&p->d_shifts, sizeof(double) * kMaxVec);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->d_zero, sizeof(double) * kMaxVec);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->d_partials, sizeof(double) * (kMaxVec + 1) * 1024 * 2);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->d_mgs, sizeof(double) * mgs_block_words());
+  if (e == hipSuccess) e = hipMalloc((void**)&p->d_scalars, sizeof(double) * 4 * kMaxVec);
+  if (e == hipSuccess) e = hipMemset(p->d_shifts, 0, sizeof(double) * kMaxVec);
+  if (e == hipSuccess) e = hipMemset(p->d_zero, 0, sizeof(double) * kMaxVec);
+  if (e != hipSuccess) {
+    mgcmt_plan_destroy(p);
+    return fail(MGCMT_ERR_HIP, std::string("plan scratch allocation: ") + hipGetErrorString(e));
+  }
+  *out = p;
+  return MGCMT_OK;
+}
+
 int mgcmt_plan_destroy(mgcmt_plan* p) {
   if (!p) return MGCMT_OK;
   comm_release(p);
@@ -1046,7 +1264,8 @@ int mgcmt_plan_get_factors(const mgcmt_plan* p, int op, int l, int which, double
   MG_TRY(check_level(p, l));
   const HostOp& h = op == MGCMT_OP_M ? p->levels[l].hM : p->levels[l].hA;
   if (op == MGCMT_OP_M && !p->has_mass) return fail(MGCMT_ERR_INVALID, "plan has no mass operator");
-  const std::vector<Tri>& f = which == 0 ? h.X : h.Y;
+  if (p->dim == 3 && (which < 0 || which > 2)) return fail(MGCMT_ERR_INVALID, "which must be 0 (z), 1 (y) or 2 (x) on a 3-D plan");
+  const std::vector<Tri>& f = which == 0 ? h.X : (which == 2 && p->dim == 3) ? h.Z : h.Y;
   int64_t need = 0;
   for (const Tri& t : f) need += (int64_t)t.a.size();
   if (!out || capacity < need) return fail(MGCMT_ERR_INVALID, "factor buffer too small");
@@ -1061,7 +1280,7 @@ int mgcmt_plan_get_factors(const mgcmt_plan* p, int op, int l, int which, double
 int mgcmt_plan_level_halo(const mgcmt_plan* p, int l, int* halo_rows, int* exchanged) {
   MG_TRY(check_level(p, l));
   if (halo_rows) *halo_rows = p->levels[l].halo;
-  if (exchanged) *exchanged = exchanged_rows(p, l);
+  if (exchanged) *exchanged = p->dim == 3 ? 0 : exchanged_rows(p, l);  // (a 3-D plan is never sharded)
   return MGCMT_OK;
 }
 
@@ -1230,6 +1449,7 @@ int mgcmt_vcycle(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int 
 }
 
 int mgcmt_twogrid(mgcmt_plan* p, int level, int nu1, int nu2, int kind, double omega, int k, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_twogrid"));
   MG_TRY(check_level(p, level));
   MG_TRY(check_k(p, k));
   if (level + 1 >= (int)p->levels.size()) return fail(MGCMT_ERR_INVALID, "twogrid needs a coarser level");
@@ -1250,6 +1470,10 @@ int mgcmt_apply(mgcmt_plan* p, int op, int l, int src_slot, int src_vec, int dst
   MG_TRY(ensure_slot(p, l, dst_slot));
   const KOp& k = op == MGCMT_OP_M ? p->levels[l].dM.k : p->levels[l].dA.k;
   const double* sh = with_shift ? p->d_shifts + src_vec : p->d_zero;
+  if (p->dim == 3) {
+    launch3_apply(S(stream), p->levels[l].dA.k3, p->kvec(l, src_slot, src_vec), p->kvec(l, dst_slot, dst_vec), sh, 1);
+    return post_launch();
+  }
   launch_apply(S(stream), p->kgrid(l), k, p->kvec(l, src_slot, src_vec), p->kvec(l, dst_slot, dst_vec), sh, 1);
   return post_launch();
 }
@@ -1259,6 +1483,10 @@ int mgcmt_restrict(mgcmt_plan* p, int l, int src_slot, int src_vec, int dst_slot
   MG_TRY(check_vec(p, l + 1, dst_slot, dst_vec));
   MG_TRY(ensure_slot(p, l, src_slot));
   MG_TRY(ensure_slot(p, l + 1, dst_slot));
+  if (p->dim == 3) {
+    launch3_restrict(S(stream), p->levels[l].dA.k3, p->kvec(l, src_slot, src_vec), p->kvec(l + 1, dst_slot, dst_vec), 1);
+    return post_launch();
+  }
   launch_restrict(S(stream), p->kgrid(l), p->kgrid(l + 1), p->kvec(l, src_slot, src_vec), p->kvec(l + 1, dst_slot, dst_vec), 1);
   return post_launch();
 }
@@ -1268,6 +1496,10 @@ int mgcmt_prolong(mgcmt_plan* p, int l, int src_slot, int src_vec, int dst_slot,
   MG_TRY(check_vec(p, l, dst_slot, dst_vec));
   MG_TRY(ensure_slot(p, l + 1, src_slot));
   MG_TRY(ensure_slot(p, l, dst_slot));
+  if (p->dim == 3) {
+    launch3_prolong(S(stream), p->levels[l].gr, p->kvec(l + 1, src_slot, src_vec), p->kvec(l, dst_slot, dst_vec), accumulate, 1);
+    return post_launch();
+  }
   launch_prolong(S(stream), p->kgrid(l), p->kgrid(l + 1), p->kvec(l + 1, src_slot, src_vec), p->kvec(l, dst_slot, dst_vec), accumulate, 1);
   return post_launch();
 }
@@ -1308,6 +1540,7 @@ int mgcmt_gram(mgcmt_plan* p, int l, int nv, const int* slots, const int* vecs, 
 }
 
 int mgcmt_ritz_pair(mgcmt_plan* p, int l, int xs, int xv, int ws, int wv, int ss, int sv, double* out5, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_ritz_pair"));
   MG_TRY(check_vec(p, l, xs, xv));
   MG_TRY(check_vec(p, l, ws, wv));
   MG_TRY(check_vec(p, l, ss, sv));
@@ -1343,6 +1576,7 @@ int mgcmt_ritz_pair(mgcmt_plan* p, int l, int xs, int xv, int ws, int wv, int ss
 }
 
 int mgcmt_rayleigh_residual(mgcmt_plan* p, int l, int slot, int k, double* rq_out, double* res_out, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_rayleigh_residual"));
   MG_TRY(check_vec(p, l, slot, 0));
   MG_TRY(check_k(p, k));
   if (slot == MGCMT_SLOT_W) return fail(MGCMT_ERR_INVALID, "rayleigh_residual uses slot W as its scratch");
@@ -1454,6 +1688,7 @@ static int rq_result(mgcmt_plan* p, double* rho_out, hipStream_t s) {
 }
 
 int mgcmt_rqmin(mgcmt_plan* p, int l, int slot, const int* vecs, int nu, int robust, double* rho_out, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_rqmin"));
   MG_TRY(rqmin_check(p, l, slot, vecs, nu));
   MG_TRY(rqmin_impl(p, l, slot, vecs, nu, robust, S(stream)));
   return rq_result(p, rho_out, S(stream));
@@ -1463,6 +1698,7 @@ int mgcmt_rqmin(mgcmt_plan* p, int l, int slot, const int* vecs, int nu, int rob
 // rqmin with p = w read as it is and not stored, then x' = x + delta w and its gradient.
 int mgcmt_rq_line_step(mgcmt_plan* p, int l, const int* xv, const int* wv, const int* xoutv, const int* gv, const int* tmpv, int robust, int record,
                        void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_rq_line_step"));
   MG_TRY(check_level(p, l));
   if (!xv || !gv) return fail(MGCMT_ERR_INVALID, "rq_line_step: x and g are required");
   if (wv && !xoutv) return fail(MGCMT_ERR_INVALID, "rq_line_step: a step needs a vector for x + delta w");
@@ -1514,6 +1750,7 @@ int mgcmt_rq_line_step(mgcmt_plan* p, int l, const int* xv, const int* wv, const
 }
 
 int mgcmt_rq_history(mgcmt_plan* p, int first, int count, double* out, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_rq_history"));
   if (!p || !out || first < 0 || count < 0 || first + count > MGCMT_RQ_HISTORY) return fail(MGCMT_ERR_INVALID, "rq_history: bad range");
   if (count == 0) return MGCMT_OK;
   if (!p->d_rqhistory) return fail(MGCMT_ERR_INVALID, "rq_history: nothing recorded");
@@ -1538,6 +1775,7 @@ static int rqmg_body(mgcmt_plan* p, int l, int slot, const int* vecs, int nu1, i
 }
 
 int mgcmt_vcycle_rqmg(mgcmt_plan* p, int slot, const int* vecs, int nu1, int nu2, int robust, double* rho_out, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_vcycle_rqmg"));
   if (!p) return fail(MGCMT_ERR_INVALID, "null plan");
   if (nu1 < 0 || nu2 < 0) return fail(MGCMT_ERR_INVALID, "step counts must be >= 0");
   for (int l = 0; l < (int)p->levels.size(); ++l) MG_TRY(rqmin_check(p, l, slot, vecs, nu1));
@@ -1711,10 +1949,12 @@ static int fused_pass_checked(mgcmt_plan* p, int l, int kind, int nsweep, double
 }
 
 int mgcmt_fused_pass(mgcmt_plan* p, int l, int kind, int nsweep, double omega, int mode, int k, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_fused_pass"));
   return fused_pass_checked(p, l, kind, nsweep, omega, mode, k, S(stream), 1);
 }
 
 int mgcmt_time_fused_pass(mgcmt_plan* p, int l, int kind, int nsweep, double omega, int mode, int reps, double* ms_out, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_time_fused_pass"));
   if (!ms_out || reps < 1) return fail(MGCMT_ERR_INVALID, "bad arguments");
   MG_TRY(fused_pass_checked(p, l, kind, nsweep, omega, mode, 1, S(stream), 1));  // (allocations, occupancy query: untimed)
   hipEvent_t a, b;
@@ -1733,6 +1973,7 @@ int mgcmt_time_fused_pass(mgcmt_plan* p, int l, int kind, int nsweep, double ome
 }
 
 int mgcmt_fused_max_sweeps(const mgcmt_plan* p, int l, int kind, int* max_sweeps) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_fused_max_sweeps"));
   MG_TRY(check_level(p, l));
   if (!max_sweeps) return fail(MGCMT_ERR_INVALID, "null output");
   *max_sweeps = fused_level(p, l, kind) ? pass_sweeps(p, l, kind, 1 << 20) : 0;
@@ -1740,6 +1981,7 @@ int mgcmt_fused_max_sweeps(const mgcmt_plan* p, int l, int kind, int* max_sweeps
 }
 
 int mgcmt_fused_max_recompute(const mgcmt_plan* p, int l, int kind, int nsweep, int* max_recompute) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_fused_max_recompute"));
   MG_TRY(check_level(p, l));
   if (!max_recompute) return fail(MGCMT_ERR_INVALID, "null output");
   *max_recompute = fused_level(p, l, kind) ? fused_max_recompute(p->levels[l].dA.k, kind == MGCMT_GS_MC ? 1 : 0, nsweep) : 0;
@@ -1747,6 +1989,7 @@ int mgcmt_fused_max_recompute(const mgcmt_plan* p, int l, int kind, int nsweep, 
 }
 
 int mgcmt_level_operator_kind(const mgcmt_plan* p, int l, int* kind) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_level_operator_kind"));
   MG_TRY(check_level(p, l));
   if (!kind) return fail(MGCMT_ERR_INVALID, "null output");
   const KOp& k = p->levels[l].dA.k;
@@ -1807,6 +2050,7 @@ int mgcmt_plan_set_option(mgcmt_plan* p, int option, int value) {
 }
 
 int mgcmt_lex_wave_stats(mgcmt_plan* p, uint32_t* out, int64_t capacity) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_lex_wave_stats"));
   if (!p || !out) return fail(MGCMT_ERR_INVALID, "null argument");
   if (!p->lex_sync) return fail(MGCMT_ERR_INVALID, "no lexicographic wave sweep has run on this plan");
   const int64_t n = capacity < (int64_t)p->lex_sync_words ? capacity : (int64_t)p->lex_sync_words;
@@ -1816,6 +2060,7 @@ int mgcmt_lex_wave_stats(mgcmt_plan* p, uint32_t* out, int64_t capacity) {
 }
 
 int mgcmt_time_smoother(mgcmt_plan* p, int l, int kind, int nu, double omega, int reps, double* ms_out, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_time_smoother"));
   MG_TRY(check_level(p, l));
   if (!ms_out || reps < 1) return fail(MGCMT_ERR_INVALID, "bad arguments");
   hipEvent_t a, b;
@@ -1834,6 +2079,7 @@ int mgcmt_time_smoother(mgcmt_plan* p, int l, int kind, int nu, double omega, in
 }
 
 int mgcmt_bandwidth_probe(mgcmt_plan* p, int l, int kind, int blocks, int reps, double* ms_out, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_bandwidth_probe"));
   MG_TRY(check_level(p, l));
   if (!ms_out || reps < 1 || blocks < 1 || kind < 0 || (kind > 17 && (kind < 20 || kind > 23))) return fail(MGCMT_ERR_INVALID, "bad arguments");
   MG_TRY(ensure_slot(p, l, MGCMT_SLOT_V));

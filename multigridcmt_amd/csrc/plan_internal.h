@@ -27,10 +27,12 @@ struct Tri {
 struct HostOp {
   int nterms = 0;
   std::vector<Tri> X, Y;  // per term
+  std::vector<Tri> Z;     // 3-D levels: X over z, Y over y, Z over x
 };
 
 struct DevOp {
   KOp k{};
+  K3Op k3{};  // 3-D levels
   std::vector<double*> owned;
 };
 
@@ -59,7 +61,8 @@ struct ShardComm;  // sharded.hip
 }  // namespace mgcmt
 
 struct mgcmt_plan {
-  int dim = 1;
+  int dim = 1;  // 3: a 3-D plan (mgcmt_plan_create3d): level l is (g >> l)^3 points as g >> l z-planes (nr = gr) of (g >> l)^2
+                // points (gc), one zero halo plane above and below every vector
   int nvec = 1;
   int device = 0;
   int64_t g = 0, lowest = 0;
@@ -136,6 +139,9 @@ struct mgcmt_plan {
 namespace mgcmt {
 // helpers of plan.hip used by sharded.hip
 int fail(int code, const std::string& msg);
+// MGCMT_ERR_UNSUPPORTED (with a message naming `what`) on a 3-D plan: the entries of the 1-D / 2-D path that have no
+// 3-D form; MGCMT_OK otherwise (a null plan included: the entry's own checks report it)
+int unsupported_3d(const mgcmt_plan* p, const char* what);
 int ensure_slot(mgcmt_plan* p, int l, int slot);
 int post_launch();
 bool fused_level(const mgcmt_plan* p, int l, int kind);

@@ -530,6 +530,7 @@ static int comm_common(mgcmt_plan* p, int rank, int nranks, ShardComm** out) {
 }
 
 int mgcmt_comm_init(mgcmt_plan* p, int rank, int nranks, const void* unique_id) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_comm_init"));
   if (!unique_id) return fail(MGCMT_ERR_INVALID, "null unique id");
   RcclApi* api = rccl();
   if (!api) return fail(MGCMT_ERR_UNSUPPORTED, "RCCL is not available in this process");
@@ -548,6 +549,7 @@ int mgcmt_comm_init(mgcmt_plan* p, int rank, int nranks, const void* unique_id) 
 
 int mgcmt_comm_init_external(mgcmt_plan* p, int rank, int nranks, mgcmt_p2p_fn p2p, mgcmt_allgather_fn allgather,
                              mgcmt_allreduce_fn allreduce, void* user) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_comm_init_external"));
   if (nranks > 1 && (!p2p || !allgather)) return fail(MGCMT_ERR_INVALID, "missing transport callbacks");
   ShardComm* c = nullptr;
   MG_TRY(comm_common(p, rank, nranks, &c));
@@ -566,6 +568,7 @@ int mgcmt_comm_destroy(mgcmt_plan* p) {
 }
 
 int mgcmt_comm_set_option(mgcmt_plan* p, int option, int value) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_comm_set_option"));
   MG_TRY(check_comm(p));
   if (option == MGCMT_COMM_OPT_OVERLAP) p->comm->overlap = value != 0 && p->comm->nccl != nullptr;
   else if (option == MGCMT_COMM_OPT_SPLIT) p->comm->split = value < 0 ? 0 : (value > 2 ? 2 : value);
@@ -583,6 +586,7 @@ int mgcmt_comm_set_option(mgcmt_plan* p, int option, int value) {
 }
 
 int mgcmt_halo_exchange(mgcmt_plan* p, int l, int slot_mask, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_halo_exchange"));
   MG_TRY(check_comm(p));
   if (l < 0 || l >= (int)p->levels.size()) return fail(MGCMT_ERR_INVALID, "level out of range");
   const bool ring = (slot_mask & kRing) != 0;
@@ -598,6 +602,8 @@ int mgcmt_halo_exchange(mgcmt_plan* p, int l, int slot_mask, void* stream) {
 }
 
 int mgcmt_gather_coarse(mgcmt_plan* p, int l, int slot, mgcmt_plan* coarse, int dst_slot, int k, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_gather_coarse"));
+  MG_TRY(mgcmt::unsupported_3d(coarse, "mgcmt_gather_coarse"));
   MG_TRY(check_comm(p));
   if (!coarse) return fail(MGCMT_ERR_INVALID, "null coarse plan");
   if (l < 0 || l >= (int)p->levels.size()) return fail(MGCMT_ERR_INVALID, "level out of range");
@@ -642,6 +648,7 @@ int mgcmt_gather_coarse(mgcmt_plan* p, int l, int slot, mgcmt_plan* coarse, int 
 }
 
 int mgcmt_allreduce_sum(mgcmt_plan* p, double* host_inout, int n, void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_allreduce_sum"));
   MG_TRY(check_comm(p));
   if (!host_inout || n < 1 || n > 2 * kMaxVec) return fail(MGCMT_ERR_INVALID, "allreduce: 1..64 values");
   ShardComm* c = p->comm;
@@ -668,6 +675,7 @@ int mgcmt_allreduce_sum(mgcmt_plan* p, double* host_inout, int n, void* stream) 
 // arithmetic (the Gram-Schmidt's inner products are summed rank by rank: equal to rounding).
 int mgcmt_sharded_vcycle(mgcmt_plan* p, mgcmt_plan* coarse, int nu1, int nu2, int nu_coarse, int kind, double omega, int k, int flags,
                          void* stream) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_sharded_vcycle"));
   MG_TRY(check_comm(p));
   if (!coarse) return fail(MGCMT_ERR_INVALID, "null coarse plan");
   if (kind != MGCMT_WJACOBI && kind != MGCMT_GS_MC)

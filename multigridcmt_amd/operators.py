@@ -48,6 +48,14 @@ class StructuredOperator:
     def __init__(self, dimension, g, terms):
         self.dimension = dimension
         self.g = int(g)
+        if dimension == "3d":
+            # (X, Y, Z) per term: A = sum_m X_m (x) Y_m (x) Z_m over z, y, x (idx = z g^2 + y g + x)
+            self.terms = [tuple(np.ascontiguousarray(a, dtype=np.float64) for a in t) for t in terms]
+            if any(len(t) != 3 for t in self.terms):
+                raise ValueError("3-D terms are (X, Y, Z) triples")
+            self.shape = (self.g ** 3, self.g ** 3)
+            self._fingerprint = None
+            return
         self.terms = [(None if x is None else np.ascontiguousarray(x, dtype=np.float64),
                        np.ascontiguousarray(y, dtype=np.float64)) for x, y in terms]
         n = self.g if dimension == "1d" else self.g * self.g
@@ -59,6 +67,8 @@ class StructuredOperator:
         c = float(c)
         if self.dimension == "1d":
             return StructuredOperator("1d", self.g, [(None, y * c) for _, y in self.terms])
+        if self.dimension == "3d":
+            return StructuredOperator("3d", self.g, [(x, y, z * c) for x, y, z in self.terms])
         return StructuredOperator("2d", self.g, [(x, y * c) for x, y in self.terms])
 
     def __mul__(self, other):
@@ -82,6 +92,10 @@ class StructuredOperator:
 
     def shifted(self, mu):
         """A - mu*I as a structured operator (the shift folded into the first term's diagonal)."""
+        if self.dimension == "3d":
+            i = tri_identity(self.g)
+            terms = [tuple(a.copy() for a in t) for t in self.terms] + [(i, i.copy(), i * (-float(mu)))]
+            return StructuredOperator("3d", self.g, terms)
         terms = [(None if x is None else x.copy(), y.copy()) for x, y in self.terms]
         if self.dimension == "1d":
             terms[0][1][1] -= mu
@@ -93,6 +107,8 @@ class StructuredOperator:
     def diagonal(self):
         if self.dimension == "1d":
             return sum(y[1] for _, y in self.terms)
+        if self.dimension == "3d":
+            return sum(np.kron(x[1], np.kron(y[1], z[1])) for x, y, z in self.terms)
         return sum(np.outer(x[1], y[1]) for x, y in self.terms).reshape(-1)
 
     def tocsr(self):
@@ -100,6 +116,9 @@ class StructuredOperator:
             raise MemoryError("refusing to assemble a %d x %d sparse matrix" % self.shape)
         if self.dimension == "1d":
             return sum(tri_to_sparse(y) for _, y in self.terms).tocsr()
+        if self.dimension == "3d":
+            return sum(sp.kron(tri_to_sparse(x), sp.kron(tri_to_sparse(y), tri_to_sparse(z), format="csr"), format="csr")
+                       for x, y, z in self.terms).tocsr()
         return sum(sp.kron(tri_to_sparse(x), tri_to_sparse(y), format="csr") for x, y in self.terms).tocsr()
 
     def tocsc(self):
@@ -114,7 +133,10 @@ class StructuredOperator:
 
     # -- for the plan cache -----------------------------------------------------------------------
     def factor_blocks(self):
-        """(nterms, xfac or None, yfac) as contiguous [nterms][3][g] arrays for the C-ABI."""
+        """(nterms, xfac or None, yfac) as contiguous [nterms][3][g] arrays for the C-ABI; 3-D: (nterms, zfac, yfac, xfac),
+        the factors over z, y and x (the terms' X, Y, Z)."""
+        if self.dimension == "3d":
+            return (len(self.terms),) + tuple(np.ascontiguousarray(np.stack([t[a] for t in self.terms])) for a in range(3))
         yfac = np.ascontiguousarray(np.stack([y for _, y in self.terms]))
         xfac = None if self.dimension == "1d" else np.ascontiguousarray(np.stack([x for x, _ in self.terms]))
         return len(self.terms), xfac, yfac
@@ -123,10 +145,10 @@ class StructuredOperator:
         if self._fingerprint is None:
             h = hashlib.sha1()
             h.update(("%s:%d:%d" % (self.dimension, self.g, len(self.terms))).encode())
-            for x, y in self.terms:
-                if x is not None:
-                    h.update(x.tobytes())
-                h.update(y.tobytes())
+            for t in self.terms:
+                for a in t:
+                    if a is not None:
+                        h.update(a.tobytes())
             self._fingerprint = h.hexdigest()
         return self._fingerprint
 
@@ -136,6 +158,10 @@ def laplacian_operator(n, dimension="1d"):
     n = int(n)
     if dimension == "1d":
         return StructuredOperator("1d", n, [(None, tri_laplacian(n))])
+    if dimension == "3d":
+        # kronsum(kronsum(L, L), L) = I (x) I (x) L + I (x) L (x) I + L (x) I (x) I
+        i, L = tri_identity(n), tri_laplacian(n)
+        return StructuredOperator("3d", n, [(i, i.copy(), L), (i.copy(), L.copy(), i.copy()), (L.copy(), i.copy(), i.copy())])
     # kronsum(L, L) = I (x) L + L (x) I   (MGCMTStencilMaker.py:23-24)
     return StructuredOperator("2d", n, [(tri_identity(n), tri_laplacian(n)), (tri_laplacian(n), tri_identity(n))])
 
@@ -223,6 +249,92 @@ def _cache_key(A):
 
 
 def recognise(A, dimension=None):
+    """StructuredOperator for a scipy.sparse matrix of the shapes the reference's callers build (``_recognise_12``: 1-D
+    and 2-D) or a 3-D operator  X (x) I (x) I + I (x) Y (x) I + I (x) I (x) Z  with tridiagonal factors
+    (``_recognise_3d``).  With ``dimension=None`` 3-D is tried only after the 1-D and 2-D attempts have failed."""
+    if dimension == "3d" and not isinstance(A, StructuredOperator):
+        return _recognise_3d(A)
+    try:
+        return _recognise_12(A, dimension)
+    except UnrecognisedOperator as e12:
+        if dimension is not None or isinstance(A, StructuredOperator):
+            raise
+        try:
+            return _recognise_3d(A)
+        except UnrecognisedOperator:
+            raise e12
+
+
+def _recognise_3d(A):
+    """X (x) I (x) I + I (x) Y (x) I + I (x) I (x) Z on a g^3 grid (idx = z g^2 + y g + x): scaled and shifted 3-D
+    Laplacians and additively separable diagonals.  The off-diagonals along each axis must depend on that axis' index
+    only; the diagonal is split into three parts and the result verified by re-assembly."""
+    if not sp.issparse(A):
+        A = sp.csr_matrix(np.asarray(A, dtype=np.float64))
+    tagged = getattr(A, "_mgcmt_structured", None)
+    if tagged is not None and tagged[1] == _digest(A) and tagged[0].dimension == "3d":
+        return tagged[0]
+    key = _cache_key(A)
+    hit = _CACHE.get(key)
+    if hit is not None and hit[0] is A and hit[1].dimension == "3d":
+        return hit[1]
+    n = A.shape[0]
+    if A.shape[0] != A.shape[1]:
+        raise UnrecognisedOperator("operator must be square")
+    if np.iscomplexobj(A):
+        raise UnrecognisedOperator("complex operators are not supported by the HIP path")
+    g = int(round(n ** (1.0 / 3.0)))
+    while g ** 3 > n:
+        g -= 1
+    while (g + 1) ** 3 <= n:
+        g += 1
+    if g ** 3 != n or g < 2:
+        raise UnrecognisedOperator("3-D operator size %d is not a cube number" % n)
+    M = sp.csr_matrix(A, dtype=np.float64, copy=True)
+    M.eliminate_zeros()
+
+    def band(off):
+        out = np.zeros(n)
+        d = M.diagonal(off)
+        if off >= 0:
+            out[:n - off] = d
+        else:
+            out[-off:] = d
+        return out.reshape(g, g, g)                       # [z, y, x] of the row
+
+    d0 = M.diagonal(0).reshape(g, g, g)
+    bands = {off: band(off) for off in (1, -1, g, -g, g * g, -g * g)}
+    if sum(np.count_nonzero(b) for b in bands.values()) + np.count_nonzero(d0) != M.nnz:
+        raise UnrecognisedOperator("3-D operator has entries off the 7-point stencil")
+
+    def along(b, axis):
+        """the band's values as a function of the index along `axis` alone, or None"""
+        line = np.moveaxis(b, axis, -1)[0, 0]
+        return line if np.array_equal(b, np.moveaxis(np.broadcast_to(line, (g, g, g)), -1, axis)) else None
+
+    xs = [along(bands[1], 2), along(bands[-1], 2)]
+    ys = [along(bands[g], 1), along(bands[-g], 1)]
+    zs = [along(bands[g * g], 0), along(bands[-g * g], 0)]
+    if any(a is None for a in xs + ys + zs):
+        raise UnrecognisedOperator("3-D operator's off-diagonals are not of the form X (x) I (x) I + I (x) Y (x) I + I (x) I (x) Z")
+    c = d0[0, 0, 0] / 3.0
+    Zt, Yt, Xt = np.zeros((3, g)), np.zeros((3, g)), np.zeros((3, g))
+    Zt[0], Zt[1], Zt[2] = zs[1], d0[:, 0, 0] - 2.0 * c, zs[0]
+    Yt[0], Yt[1], Yt[2] = ys[1], d0[0, :, 0] - 2.0 * c, ys[0]
+    Xt[0], Xt[1], Xt[2] = xs[1], d0[0, 0, :] - 2.0 * c, xs[0]
+    i = tri_identity(g)
+    op = StructuredOperator("3d", g, [(i, i.copy(), Xt), (i.copy(), Yt, i.copy()), (Zt, i.copy(), i.copy())])
+    D = (M - op.tocsr()).tocsr()
+    scale = max(np.abs(M.data).max() if M.nnz else 0.0, 1e-300)
+    if D.nnz and np.abs(D.data).max() > 16 * np.finfo(float).eps * scale:
+        raise UnrecognisedOperator("3-D operator's diagonal is not additively separable a(z) + b(y) + c(x)")
+    if len(_CACHE) > 64:
+        _CACHE.clear()
+    _CACHE[key] = (A, op)
+    return op
+
+
+def _recognise_12(A, dimension=None):
     """StructuredOperator for a scipy.sparse matrix of the shapes the reference's callers build.
 
     1-D: any tridiagonal matrix.  2-D: a 5-point operator  I (x) Y + X (x) I  whose diagonal is

@@ -22,11 +22,14 @@ class Plan:
         self._h = c_void_p()
         self.op = op
         self.mass = mass
-        self.dim = 1 if op.dimension == "1d" else 2
+        self.dim = {"1d": 1, "2d": 2, "3d": 3}[op.dimension]
         self.g = op.g
         self.lowest = int(lowest)
         self.nvec = int(nvec)
         self.device = device
+        if self.dim == 3:
+            self._create3d(op, mass, row_begin, row_end, strip_levels)
+            return
         nterms, xfac, yfac = op.factor_blocks()
         desc = PlanDesc()
         desc.dim, desc.nterms, desc.g, desc.lowest = self.dim, nterms, self.g, self.lowest
@@ -43,6 +46,25 @@ class Plan:
         desc.row_begin, desc.row_end, desc.strip_levels = row_begin, row_end, strip_levels
         check(_lib.lib().mgcmt_plan_create(ctypes.byref(desc), ctypes.byref(self._h)))
         del keep
+        n = c_int(0)
+        check(_lib.lib().mgcmt_plan_num_levels(self._h, ctypes.byref(n)))
+        self.num_levels = n.value
+        self.shapes = [self.level_shape(l) for l in range(self.num_levels)]
+        self._shifts = None
+
+    def _create3d(self, op, mass, row_begin, row_end, strip_levels):
+        if mass is not None:
+            raise ValueError("mass operators are not available on 3-D grids")
+        if row_begin or row_end or strip_levels:
+            raise ValueError("3-D plans are not sharded")
+        if self.lowest > 16:
+            raise ValueError("lowest_level=%d: the coarsest 3-D level is solved directly and may be at most 16^3" % self.lowest)
+        nterms, zfac, yfac, xfac = op.factor_blocks()
+        desc = _lib.Plan3dDesc()
+        desc.nterms, desc.nvec, desc.g, desc.lowest = nterms, self.nvec, self.g, self.lowest
+        desc.zfac, desc.yfac, desc.xfac = as_dp(zfac), as_dp(yfac), as_dp(xfac)
+        desc.device = self.device
+        check(_lib.lib().mgcmt_plan_create3d(ctypes.byref(desc), ctypes.byref(self._h)))
         n = c_int(0)
         check(_lib.lib().mgcmt_plan_num_levels(self._h, ctypes.byref(n)))
         self.num_levels = n.value
@@ -75,7 +97,7 @@ class Plan:
         """Host copy of a level's Kronecker factors: array [nterms, 3, n]."""
         src = self.op if op == OP_A else self.mass
         nterms = len(src.terms)
-        n = (self.g >> level) if (which == 1 or self.dim == 2) else 1
+        n = (self.g >> level) if (which == 1 or self.dim >= 2) else 1
         out = np.zeros((nterms, 3, n))
         check(_lib.lib().mgcmt_plan_get_factors(self._h, op, level, which, as_dp(out), out.size))
         return out
@@ -337,7 +359,8 @@ def apply_operator(op, x):
     x = np.asarray(x, dtype=np.float64)
     n = op.shape[0]
     cols = x.reshape(n, -1)
-    plan = get_plan(op, op.g, nvec=1)      # a single level is enough
+    # a single level is enough (3-D: the coarsest level may be at most 16^3; the levels below hold no vectors until used)
+    plan = get_plan(op, op.g if op.dimension != "3d" else min(op.g, 16), nvec=1)
     out = np.empty_like(cols)
     for c in range(cols.shape[1]):
         plan.upload(0, SLOT_V, 0, cols[:, c])

@@ -48,6 +48,14 @@ def _force_column(a, n):
     return a
 
 
+def _check_3d_smoother(kind):
+    """3-D grids have weighted Jacobi and multicolour Gauss-Seidel; a lexicographic smoother raises instead of being
+    replaced by another one."""
+    if kind in (GS_LEX, SOR_LEX):
+        raise ValueError("gseidel / sor (lexicographic) are not available on 3-D grids; the supported smoothers are "
+                         "wjacobi, gseidel_rb (multicolour) and foreign smoother callables")
+
+
 class MGCMTSolver:
     """
     Same constructor as the reference (MGCMTSolver.py:13-15): owns a stencil maker and a processor.
@@ -62,13 +70,19 @@ class MGCMTSolver:
     # ------------------------------------------------------------------------------------------
     def _smooth(self, v0, f, A, kind, nu, omega, dimension=None):
         n = len(v0)
+        if dimension == "3d":
+            _check_3d_smoother(kind)
         try:
             op = recognise(A, dimension)
         except UnrecognisedOperator:
-            if dimension == "2d":
+            if dimension in ("2d", "3d"):
                 raise
             return self._smooth_general(v0, f, A, kind, nu, omega)
-        plan = get_plan(op, op.g, nvec=1)
+        if op.dimension == "3d" and dimension is None and kind != WJACOBI:
+            # a matrix recognised as 3-D only because no dimension was named: the lexicographic and multicolour orders
+            # of the general path are what such calls ran before 3-D grids existed
+            return self._smooth_general(v0, f, A, kind, nu, omega)
+        plan = get_plan(op, op.g if op.dimension != "3d" else min(op.g, 16), nvec=1)   # (3-D: the coarsest level is at most 16^3)
         plan.set_shifts([0.0])
         plan.upload(0, SLOT_V, 0, np.asarray(v0, dtype=np.float64).reshape(-1))
         plan.upload(0, SLOT_F, 0, np.asarray(f, dtype=np.float64).reshape(-1))
@@ -188,6 +202,12 @@ class MGCMTSolver:
     def _level_matrix(self, plan, level, shift):
         """(A_level - shift I) as the scipy.sparse matrix the reference hands to a smoother (:287-288,313); A_level is
         the Galerkin operator R*A*P of that level (:318), rebuilt from the plan's Kronecker factors."""
+        if plan.dim == 3:
+            fs = [plan.factors(level, w) for w in range(3)]
+            op = StructuredOperator("3d", plan.g >> level, [tuple(f[m].copy() for f in fs) for m in range(fs[0].shape[0])])
+            if shift:
+                op = op.shifted(float(shift))
+            return tag_structured(op.tocsr(), op)
         xf = plan.factors(level, 0) if plan.dim == 2 else None
         yf = plan.factors(level, 1)
         terms = [((xf[m].copy() if xf is not None else None), yf[m].copy()) for m in range(yf.shape[0])]
@@ -235,6 +255,12 @@ class MGCMTSolver:
             return n
         if dimension == "2d":
             return np.sqrt(n)
+        if dimension == "3d":                       # addition: the exact integer cube root, else a non-integer
+            g = int(round(n ** (1.0 / 3.0)))
+            for c in (g - 1, g, g + 1):
+                if c > 0 and c ** 3 == n:
+                    return c
+            return n ** (1.0 / 3.0)
         return 0
 
     def _check_grid(self, g, lowest_level):
@@ -264,6 +290,8 @@ class MGCMTSolver:
         arrays level by level with the transfers on the device (``_cycle_with_host_smoother``).
         """
         kind, omega = self._resolve_smoother(smoother)
+        if dimension == "3d":
+            _check_3d_smoother(kind)
         self._check_stencil_maker(stencil_maker, dimension)
         n = len(v0)
         g = self._grid(n, dimension)
@@ -370,6 +398,8 @@ class MGCMTSolver:
             raise ValueError("dimension mismatch: %d shifts for %d columns" % (len(shifts), k))
         if k > _lib.MAX_VEC:
             raise ValueError("at most %d columns per call" % _lib.MAX_VEC)
+        if dimension == "3d":
+            _check_3d_smoother(kind)
         g = self._grid(n, dimension)
         if not self._check_grid(g, lowest_level):
             return None

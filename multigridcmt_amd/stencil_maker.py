@@ -36,6 +36,10 @@ class MGCMTStencilMaker:
         if dimension == "2d":
             one_d = self.laplacian(n, dimension="1d")
             return spsparse.kronsum(one_d, one_d)
+        if dimension == "3d":
+            # addition: kronsum(kronsum(L, L), L), index z*n^2 + y*n + x
+            one_d = self.laplacian(n, dimension="1d")
+            return spsparse.kronsum(spsparse.kronsum(one_d, one_d), one_d, format="csc")
         return None
 
     def mehrstellen(self, n, matrix_free=False):
@@ -57,6 +61,9 @@ class MGCMTStencilMaker:
         if dimension == "2d":
             s = self.interpolation(old_gridsize, new_gridsize, dimension="1d")
             return None if s is None else spsparse.kron(s, s, format="csc")
+        if dimension == "3d":       # addition: trilinear, kron(S, kron(S, S))
+            s = self.interpolation(old_gridsize, new_gridsize, dimension="1d")
+            return None if s is None else spsparse.kron(s, spsparse.kron(s, s, format="csc"), format="csc")
         if dimension != "1d":
             return None
         p_old, old_ok = _power_of_two(old_gridsize)
@@ -86,6 +93,9 @@ class MGCMTStencilMaker:
         if dimension == "2d":
             p = self.interpolation(new_gridsize, old_gridsize, dimension="2d")
             return None if p is None else 1. / 4. * p.T
+        if dimension == "3d":       # addition: the 2-D formula with the 3-D factor (fixed 1/8, like the fixed 1/4)
+            p = self.interpolation(new_gridsize, old_gridsize, dimension="3d")
+            return None if p is None else 1. / 8. * p.T
         if dimension != "1d":
             return None
         p_old, old_ok = _power_of_two(old_gridsize)

@@ -33,8 +33,12 @@
  *     (1,1,1), (0,0,0), (0,1,1), (1,0,1), (1,1,0): odd coordinate sum first, i.e. red-black on the 7-point fine level.
  *     On a 3-D plan mgcmt_plan_level_shape reports rows = z-planes (g_l) and cols = points per plane (g_l^2), and
  *     mgcmt_plan_get_factors takes which = 0 (z), 1 (y) or 2 (x).  Weighted Jacobi and multicolour Gauss-Seidel are the
- *     3-D smoothers; the entries with no 3-D form (lexicographic smoothers, twogrid, the Rayleigh-quotient family,
- *     mass operators, sharding, fused-pass and timing entries) return MGCMT_ERR_UNSUPPORTED on a 3-D plan.
+ *     3-D smoothers.  A 3-D plan created with a mass operator (mgcmt_plan_create3d_mass) also runs the Rayleigh-quotient
+ *     entries (mgcmt_rqmin, mgcmt_rq_line_step, mgcmt_rq_history, mgcmt_vcycle_rqmg) on the Galerkin pairs
+ *     (R A P, R M P); on a 3-D plan without one they return MGCMT_ERR_UNSUPPORTED (pass M = I explicitly: the coarse
+ *     levels then minimise with R I P, as the reference does).  The entries with no 3-D form (lexicographic smoothers,
+ *     twogrid, ritz_pair, rayleigh_residual, sharding, fused-pass and timing entries) return MGCMT_ERR_UNSUPPORTED on
+ *     a 3-D plan.
  */
 #ifndef MGCMT_HIP_H
 #define MGCMT_HIP_H
@@ -117,6 +121,11 @@ typedef struct mgcmt_plan3d_desc {
   int32_t reserved;
 } mgcmt_plan3d_desc;
 int mgcmt_plan_create3d(const mgcmt_plan3d_desc* desc, mgcmt_plan** out);
+/* A 3-D plan with a mass operator M = sum_m m_zfac_m (x) m_yfac_m (x) m_xfac_m (1 .. MGCMT_MAX_TERMS terms, the factor
+ * layout of desc's), coarsened per axis like A; M with one identity term is never applied.  The Rayleigh-quotient
+ * entries need one on a 3-D plan. */
+int mgcmt_plan_create3d_mass(const mgcmt_plan3d_desc* desc, int32_t m_nterms, const double* m_zfac, const double* m_yfac, const double* m_xfac,
+                             mgcmt_plan** out);
 int mgcmt_plan_num_levels(const mgcmt_plan* plan, int* levels);
 int mgcmt_plan_level_shape(const mgcmt_plan* plan, int level, int64_t* rows, int64_t* cols, int64_t* row_begin);
 /* host copy of a level's factors, [nterms][3][n] with n = global rows (which=0) or cols (which=1) */

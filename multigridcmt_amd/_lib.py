@@ -78,6 +78,7 @@ _SIGNATURES = {
     "mgcmt_device_name": (c_int, [c_int, ctypes.c_char_p, c_int]),
     "mgcmt_plan_create": (c_int, [POINTER(PlanDesc), POINTER(c_void_p)]),
     "mgcmt_plan_create3d": (c_int, [POINTER(Plan3dDesc), POINTER(c_void_p)]),
+    "mgcmt_plan_create3d_mass": (c_int, [POINTER(Plan3dDesc), c_int32, _dp, _dp, _dp, POINTER(c_void_p)]),
     "mgcmt_plan_destroy": (c_int, [c_void_p]),
     "mgcmt_plan_num_levels": (c_int, [c_void_p, POINTER(c_int)]),
     "mgcmt_plan_level_shape": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),

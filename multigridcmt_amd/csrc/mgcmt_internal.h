@@ -177,6 +177,8 @@ bool launch_rq_gmg(hipStream_t s, KGrid g, KOp Mo, const double* gv, double* par
 // the whole rqmin call (initial pair + nu steps) in one single-workgroup launch where the level is small enough; false: not taken
 bool launch_rq_small(hipStream_t s, KGrid g, KOp A, KOp Mo, int m_identity, double* x, double* p, double* gv, double* state, int nu, int robust);
 // m_identity: 1 = M is the identity, 0 = <g, M g> is in state[rq_word_gmg()], 2 = it is result 3 of the partial sums (launch_rq_gmg)
+// the scalars of pass 1 alone (the kernel launch_rq_pass1 ends with), behind the 3-D passes
+void launch_rq_scalars1(hipStream_t s, const double* partials, int nblocks, double* state, int init, int robust);
 void launch_rq_scalars2(hipStream_t s, const double* partials, int nblocks, double* state, int m_identity, int init);
 
 // the levels of at most 32 x 32 points of a V-cycle in one launch (kernels_tail.hip)
@@ -248,5 +250,17 @@ void launch3_prolong(hipStream_t s, long n, KVec e, KVec dst, int accumulate, in
 // vout <- one weighted-Jacobi sweep from w = vin + P e (w is not stored)
 void launch3_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
 void launch3_band_assemble(hipStream_t s, const K3Op& op, const double* shifts, KBand b, int k);
+
+// Rayleigh-quotient passes on 3-D levels (kernels_rq3d.hip), the protocol of launch_rq_pass1 / launch_rq_pass2 /
+// launch_rq_scalars2 and the same state words: pass 1 ends with the step's scalars; pass 2 returns the number of partial
+// sums per result; with M != I, launch_rq3_gmg puts <g, M g> into result 3 of them (then m_identity = 2 for
+// launch_rq_scalars2).  launch_rq3_small: the whole call in one launch on levels of at most 16^3 points (false: not taken).
+bool rq3_marching(const K3Op& A, int m_identity);
+void launch_rq3_pass1(hipStream_t s, const K3Op& A, const K3Op& Mo, int m_identity, const double* x, const double* gv, const double* pold, double* pnew,
+                      double* state, int init, int robust, double* partials);
+int launch_rq3_pass2(hipStream_t s, const K3Op& A, const K3Op& Mo, int m_identity, const double* x, const double* p, double* xnew, double* gout, double* state,
+                     int init, double* partials);
+bool launch_rq3_gmg(hipStream_t s, const K3Op& Mo, const double* gv, double* partials, int nblocks);
+bool launch_rq3_small(hipStream_t s, const K3Op& A, const K3Op& Mo, int m_identity, double* x, double* p, double* gv, double* state, int nu, int robust);
 
 }  // namespace mgcmt

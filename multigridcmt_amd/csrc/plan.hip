@@ -26,6 +26,14 @@ int unsupported_3d(const mgcmt_plan* p, const char* what) {
   if (p && p->dim == 3) return fail(MGCMT_ERR_UNSUPPORTED, std::string(what) + " is not available on a 3-D plan");
   return MGCMT_OK;
 }
+
+// the Rayleigh-quotient entries run on a 3-D plan that carries a mass operator (mgcmt_plan_create3d_mass): without one the
+// coarse levels would minimise with I where the reference has R I P, so callers pass M = I explicitly
+int unsupported_3d_massless(const mgcmt_plan* p, const char* what) {
+  if (p && p->dim == 3 && !p->has_mass)
+    return fail(MGCMT_ERR_UNSUPPORTED, std::string(what) + " is not available on a 3-D plan without a mass operator (mgcmt_plan_create3d_mass)");
+  return MGCMT_OK;
+}
 }  // namespace mgcmt
 
 namespace {
@@ -1138,7 +1146,8 @@ int mgcmt_plan_create(const mgcmt_plan_desc* d, mgcmt_plan** out) {
   return MGCMT_OK;
 }
 
-int mgcmt_plan_create3d(const mgcmt_plan3d_desc* d, mgcmt_plan** out) {
+static int create3d(const mgcmt_plan3d_desc* d, int32_t m_nterms, const double* m_zfac, const double* m_yfac, const double* m_xfac,
+                    mgcmt_plan** out) {
   if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
   *out = nullptr;
   if (!is_pow2(d->g) || !is_pow2(d->lowest) || d->lowest > d->g) return fail(MGCMT_ERR_INVALID, "g and lowest must be powers of two with lowest <= g");
@@ -1147,11 +1156,14 @@ int mgcmt_plan_create3d(const mgcmt_plan3d_desc* d, mgcmt_plan** out) {
   if (d->lowest > 16) return fail(MGCMT_ERR_INVALID, "lowest must be at most 16 on a 3-D plan (the coarsest level is solved directly)");
   if (d->nterms < 1 || d->nterms > kMaxTerms) return fail(MGCMT_ERR_INVALID, "nterms out of range");
   if (!d->xfac || !d->yfac || !d->zfac) return fail(MGCMT_ERR_INVALID, "missing factor arrays");
+  if (m_nterms < 0 || m_nterms > kMaxTerms) return fail(MGCMT_ERR_INVALID, "mass nterms out of range");
+  if (m_nterms > 0 && (!m_xfac || !m_yfac || !m_zfac)) return fail(MGCMT_ERR_INVALID, "missing mass factor arrays");
   if (d->nvec < 1 || d->nvec > kMaxVec) return fail(MGCMT_ERR_INVALID, "nvec out of range (1..32)");
   MG_HIP(hipSetDevice(d->device));
 
   mgcmt_plan* p = new mgcmt_plan();
   p->dim = 3;
+  p->has_mass = m_nterms > 0;
   p->nvec = d->nvec;
   p->device = d->device;
   p->g = d->g;
@@ -1178,24 +1190,28 @@ int mgcmt_plan_create3d(const mgcmt_plan3d_desc* d, mgcmt_plan** out) {
     L.r0 = 0;
     L.halo = 1;       // one zero plane above and below
     L.stride = ((L.nr + 2 * L.halo) * L.gc + 31) / 32 * 32;
-    HostOp& h = L.hA;
-    h.nterms = d->nterms;
-    h.X.resize(d->nterms);
-    h.Y.resize(d->nterms);
-    h.Z.resize(d->nterms);
-    for (int m = 0; m < d->nterms; ++m) {
-      if (l == 0) {
-        h.X[m] = load(d->zfac, m);
-        h.Y[m] = load(d->yfac, m);
-        h.Z[m] = load(d->xfac, m);
-      } else {  // R A P with P = P1 (x) P1 (x) P1: each factor coarsened on its own (plan.hip: galerkin)
-        const HostOp& f = p->levels[l - 1].hA;
-        h.X[m] = galerkin(f.X[m]);
-        h.Y[m] = galerkin(f.Y[m]);
-        h.Z[m] = galerkin(f.Z[m]);
+    // R A P (and R M P) with P = P1 (x) P1 (x) P1: each factor coarsened on its own (galerkin), a Kronecker sum stays one
+    auto build = [&](HostOp& h, const HostOp* finer, int nterms, const double* zf, const double* yf, const double* xf) {
+      h.nterms = nterms;
+      h.X.resize(nterms);
+      h.Y.resize(nterms);
+      h.Z.resize(nterms);
+      for (int m = 0; m < nterms; ++m) {
+        if (l == 0) {
+          h.X[m] = load(zf, m);
+          h.Y[m] = load(yf, m);
+          h.Z[m] = load(xf, m);
+        } else {
+          h.X[m] = galerkin(finer->X[m]);
+          h.Y[m] = galerkin(finer->Y[m]);
+          h.Z[m] = galerkin(finer->Z[m]);
+        }
       }
-    }
-    const int rc = upload_op3(h, n, &L.dA);
+    };
+    build(L.hA, l ? &p->levels[l - 1].hA : nullptr, d->nterms, d->zfac, d->yfac, d->xfac);
+    if (p->has_mass) build(L.hM, l ? &p->levels[l - 1].hM : nullptr, m_nterms, m_zfac, m_yfac, m_xfac);
+    int rc = upload_op3(L.hA, n, &L.dA);
+    if (rc == MGCMT_OK && p->has_mass) rc = upload_op3(L.hM, n, &L.dM);
     if (rc != MGCMT_OK) {
       mgcmt_plan_destroy(p);
       return rc;
@@ -1214,6 +1230,14 @@ int mgcmt_plan_create3d(const mgcmt_plan3d_desc* d, mgcmt_plan** out) {
   }
   *out = p;
   return MGCMT_OK;
+}
+
+int mgcmt_plan_create3d(const mgcmt_plan3d_desc* d, mgcmt_plan** out) { return create3d(d, 0, nullptr, nullptr, nullptr, out); }
+
+int mgcmt_plan_create3d_mass(const mgcmt_plan3d_desc* d, int32_t m_nterms, const double* m_zfac, const double* m_yfac, const double* m_xfac,
+                             mgcmt_plan** out) {
+  if (m_nterms < 1 || m_nterms > kMaxTerms) return fail(MGCMT_ERR_INVALID, "mass nterms out of range (1..4)");
+  return create3d(d, m_nterms, m_zfac, m_yfac, m_xfac, out);
 }
 
 int mgcmt_plan_destroy(mgcmt_plan* p) {
@@ -1471,7 +1495,8 @@ int mgcmt_apply(mgcmt_plan* p, int op, int l, int src_slot, int src_vec, int dst
   const KOp& k = op == MGCMT_OP_M ? p->levels[l].dM.k : p->levels[l].dA.k;
   const double* sh = with_shift ? p->d_shifts + src_vec : p->d_zero;
   if (p->dim == 3) {
-    launch3_apply(S(stream), p->levels[l].dA.k3, p->kvec(l, src_slot, src_vec), p->kvec(l, dst_slot, dst_vec), sh, 1);
+    const K3Op& k3 = op == MGCMT_OP_M ? p->levels[l].dM.k3 : p->levels[l].dA.k3;
+    launch3_apply(S(stream), k3, p->kvec(l, src_slot, src_vec), p->kvec(l, dst_slot, dst_vec), sh, 1);
     return post_launch();
   }
   launch_apply(S(stream), p->kgrid(l), k, p->kvec(l, src_slot, src_vec), p->kvec(l, dst_slot, dst_vec), sh, 1);
@@ -1633,10 +1658,48 @@ static bool mass_is_identity(const mgcmt_plan* p, int l) {
       if (t.di(i) != 1.0 || (i > 0 && t.lo(i) != 0.0) || (i + 1 < t.n && t.up(i) != 0.0)) return false;
     return true;
   };
-  return L.hM.nterms == 1 && is_identity(L.hM.X[0]) && is_identity(L.hM.Y[0]);
+  return L.hM.nterms == 1 && is_identity(L.hM.X[0]) && is_identity(L.hM.Y[0]) && (p->dim != 3 || is_identity(L.hM.Z[0]));
+}
+
+// rqmin_impl on a 3-D level (kernels_rq3d.hip): the same sequence of passes and scalar kernels; <g, M g> always as result 3
+// of pass 2's partial sums (with M != I pass 2 takes the flat form, whose grid the product's kernel shares)
+static int rqmin3_impl(mgcmt_plan* p, int l, int slot, const int* vecs, int nu, int robust, hipStream_t s) {
+  const Level& L = p->levels[l];
+  const K3Op& A = L.dA.k3;
+  const K3Op& Mo = L.dM.k3;  // (3-D Rayleigh-quotient plans always carry M)
+  const int mid = mass_is_identity(p, l) ? 1 : 0;
+  double* x = p->kvec(l, slot, vecs[0]).p;
+  double* xalt = p->kvec(l, slot, vecs[1]).p;
+  double* pv = p->kvec(l, slot, vecs[2]).p;
+  double* palt = p->kvec(l, slot, vecs[3]).p;
+  double* gv = p->kvec(l, slot, vecs[4]).p;
+  double* st = p->d_rqstate;
+  double* part = p->d_partials;
+  const long n = p->interior(l);
+  double* x0 = x;
+  const char* small_env = getenv("MGCMT_RQ_SMALL");
+  const bool small_ok = !(small_env && small_env[0] == '0');
+  if (small_ok && launch_rq3_small(s, A, Mo, mid, x, pv, gv, st, nu, robust)) return post_launch();
+  for (int it = -1; it < nu; ++it) {
+    const int init = it < 0 ? 1 : (it == 0 ? 2 : 0);
+    launch_rq3_pass1(s, A, Mo, mid, x, gv, pv, palt, st, init, robust, part);
+    if (init != 1) std::swap(pv, palt);
+    const int nb = launch_rq3_pass2(s, A, Mo, mid, x, pv, xalt, gv, st, init, part);
+    if (init != 1) std::swap(x, xalt);
+    int mflag = 1;
+    if (!mid) {
+      if (!launch_rq3_gmg(s, Mo, gv, part, nb)) return fail(MGCMT_ERR_INVALID, "rqmin: no <g, M g> form for this 3-D level");
+      mflag = 2;
+    }
+    launch_rq_scalars2(s, part, nb, st, mflag, init);
+  }
+  MG_TRY(post_launch());
+  if (x != x0) MG_HIP(hipMemcpyAsync(x0, x, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+  return MGCMT_OK;
 }
 
 static int rqmin_impl(mgcmt_plan* p, int l, int slot, const int* vecs, int nu, int robust, hipStream_t s) {
+  if (p->dim == 3) return rqmin3_impl(p, l, slot, vecs, nu, robust, s);
   const Level& L = p->levels[l];
   const KOp& A = L.dA.k;
   const bool m_identity = mass_is_identity(p, l);
@@ -1688,7 +1751,7 @@ static int rq_result(mgcmt_plan* p, double* rho_out, hipStream_t s) {
 }
 
 int mgcmt_rqmin(mgcmt_plan* p, int l, int slot, const int* vecs, int nu, int robust, double* rho_out, void* stream) {
-  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_rqmin"));
+  MG_TRY(mgcmt::unsupported_3d_massless(p, "mgcmt_rqmin"));
   MG_TRY(rqmin_check(p, l, slot, vecs, nu));
   MG_TRY(rqmin_impl(p, l, slot, vecs, nu, robust, S(stream)));
   return rq_result(p, rho_out, S(stream));
@@ -1698,7 +1761,7 @@ int mgcmt_rqmin(mgcmt_plan* p, int l, int slot, const int* vecs, int nu, int rob
 // rqmin with p = w read as it is and not stored, then x' = x + delta w and its gradient.
 int mgcmt_rq_line_step(mgcmt_plan* p, int l, const int* xv, const int* wv, const int* xoutv, const int* gv, const int* tmpv, int robust, int record,
                        void* stream) {
-  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_rq_line_step"));
+  MG_TRY(mgcmt::unsupported_3d_massless(p, "mgcmt_rq_line_step"));
   MG_TRY(check_level(p, l));
   if (!xv || !gv) return fail(MGCMT_ERR_INVALID, "rq_line_step: x and g are required");
   if (wv && !xoutv) return fail(MGCMT_ERR_INVALID, "rq_line_step: a step needs a vector for x + delta w");
@@ -1731,6 +1794,18 @@ int mgcmt_rq_line_step(mgcmt_plan* p, int l, const int* xv, const int* wv, const
   double* part = p->d_partials;
   // without a direction: the initial pair of rqmin (rho and g of x); with one: pass 1 reads p = w (init 3), pass 2 is a step's
   const int init1 = w ? 3 : 1, init2 = w ? 0 : 1;
+  if (p->dim == 3) {
+    const K3Op& A3 = L.dA.k3;
+    const K3Op& M3 = L.dM.k3;
+    const int mid = m_identity ? 1 : 0;
+    launch_rq3_pass1(s, A3, M3, mid, x, w, nullptr, nullptr, st, init1, robust, part);
+    const int nb = launch_rq3_pass2(s, A3, M3, mid, x, w, xout, gout, st, init2, part);
+    if (!m_identity && !launch_rq3_gmg(s, M3, gout, part, nb)) return fail(MGCMT_ERR_INVALID, "rq_line_step: no <g, M g> form for this 3-D level");
+    launch_rq_scalars2(s, part, nb, st, m_identity ? 1 : 2, init2);
+    MG_TRY(post_launch());
+    if (record >= 0) MG_HIP(hipMemcpyAsync(p->d_rqhistory + record, st + rq_word_rho(), sizeof(double), hipMemcpyDeviceToDevice, s));
+    return MGCMT_OK;
+  }
   launch_rq_pass1(s, g, A, Mo, m_identity ? 1 : 0, x, w, nullptr, nullptr, st, init1, robust, part);
   const int nb = launch_rq_pass2(s, g, A, Mo, m_identity ? 1 : 0, x, w, xout, gout, st, init2, part);
   int mflag = m_identity ? 1 : 0;
@@ -1750,7 +1825,7 @@ int mgcmt_rq_line_step(mgcmt_plan* p, int l, const int* xv, const int* wv, const
 }
 
 int mgcmt_rq_history(mgcmt_plan* p, int first, int count, double* out, void* stream) {
-  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_rq_history"));
+  MG_TRY(mgcmt::unsupported_3d_massless(p, "mgcmt_rq_history"));
   if (!p || !out || first < 0 || count < 0 || first + count > MGCMT_RQ_HISTORY) return fail(MGCMT_ERR_INVALID, "rq_history: bad range");
   if (count == 0) return MGCMT_OK;
   if (!p->d_rqhistory) return fail(MGCMT_ERR_INVALID, "rq_history: nothing recorded");
@@ -1767,15 +1842,17 @@ static int rqmg_body(mgcmt_plan* p, int l, int slot, const int* vecs, int nu1, i
   const int last = (int)p->levels.size() - 1;
   MG_TRY(rqmin_impl(p, l, slot, vecs, nu1, robust, s));
   if (l == last) return MGCMT_OK;
-  launch_restrict(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l, slot, vecs[0]), p->kvec(l + 1, slot, vecs[0]), 1);
+  if (p->dim == 3) launch3_restrict(s, p->levels[l].dA.k3, p->kvec(l, slot, vecs[0]), p->kvec(l + 1, slot, vecs[0]), 1);
+  else launch_restrict(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l, slot, vecs[0]), p->kvec(l + 1, slot, vecs[0]), 1);
   MG_TRY(rqmg_body(p, l + 1, slot, vecs, nu1, nu2, robust, s));
-  launch_prolong(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l + 1, slot, vecs[0]), p->kvec(l, slot, vecs[0]), 1, 1);
+  if (p->dim == 3) launch3_prolong(s, p->levels[l].gr, p->kvec(l + 1, slot, vecs[0]), p->kvec(l, slot, vecs[0]), 1, 1);
+  else launch_prolong(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l + 1, slot, vecs[0]), p->kvec(l, slot, vecs[0]), 1, 1);
   MG_TRY(post_launch());
   return rqmin_impl(p, l, slot, vecs, nu2, robust, s);
 }
 
 int mgcmt_vcycle_rqmg(mgcmt_plan* p, int slot, const int* vecs, int nu1, int nu2, int robust, double* rho_out, void* stream) {
-  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_vcycle_rqmg"));
+  MG_TRY(mgcmt::unsupported_3d_massless(p, "mgcmt_vcycle_rqmg"));
   if (!p) return fail(MGCMT_ERR_INVALID, "null plan");
   if (nu1 < 0 || nu2 < 0) return fail(MGCMT_ERR_INVALID, "step counts must be >= 0");
   for (int l = 0; l < (int)p->levels.size(); ++l) MG_TRY(rqmin_check(p, l, slot, vecs, nu1));

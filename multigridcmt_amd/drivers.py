@@ -21,12 +21,14 @@ from .stencil_maker import MGCMTStencilMaker
 
 def exact_box_eigenvalues(gridsize, dimension, count):
     """Eigenvalues of -laplacian(gridsize)/pi^2 (the discrete operator, not the continuum n^2): in 1-D
-    (4 g^2/pi^2) sin^2(k pi / (2 (g+1))), k = 1..g; in 2-D all pairwise sums, sorted."""
+    (4 g^2/pi^2) sin^2(k pi / (2 (g+1))), k = 1..g; in 2-D all pairwise sums, in 3-D all triple sums, sorted."""
     k = np.arange(1, gridsize + 1)
     one_d = (4.0 * gridsize ** 2 / np.pi ** 2) * np.sin(k * np.pi / (2.0 * (gridsize + 1))) ** 2
     if dimension == "1d":
         return one_d[:count]
     m = min(gridsize, count + 2)
+    if dimension == "3d":
+        return np.sort(np.add.outer(np.add.outer(one_d[:m], one_d[:m]), one_d[:m]).ravel())[:count]
     return np.sort(np.add.outer(one_d[:m], one_d[:m]).ravel())[:count]
 
 
@@ -205,7 +207,7 @@ def rayleigh_quotient_multigrid(gridsize=2 ** 6, first_cycles=2, second_cycles=1
 
 
 def potential_well_eigensolve(gridsize=2 ** 7, depth=50.0, inner=None, cycles=8, method="vcycle", nu=2, lowest=8,
-                              smoother="rb", seed=0, history=None, stats=None):
+                              smoother="rb", seed=0, history=None, stats=None, dimension="2d"):
     """BASELINE config 5: the ground state of the 2-D square well  H = -laplacian/pi^2 + V  (V = `depth` outside the
     central square, PotWellSolver.py:150-153 carried to 2-D) by Rayleigh-quotient minimisation on the GPU.
 
@@ -219,6 +221,9 @@ def potential_well_eigensolve(gridsize=2 ** 7, depth=50.0, inner=None, cycles=8,
                      start (a flag: V is neither cleared nor read) and 48 B per point of vector traffic beside it;
                      nothing comes back to the host inside the loop (the Rayleigh quotients are recorded on the
                      device and fetched once).
+    dimension="3d" (addition): the cube well (a quantum dot) on g^3 points, potential_well_operator(..., dimension="3d");
+    both methods run on a plan that carries M = I explicitly (the Rayleigh-quotient entries of a 3-D plan need one), and
+    ``lowest`` is at most 16.
     Returns (rho, x); ``history`` (a list) receives rho after every cycle, ``stats`` (a dict) the seconds spent in
     the iteration loop alone (start vector generation and the host transfers excluded)."""
     from . import _lib
@@ -227,11 +232,14 @@ def potential_well_eigensolve(gridsize=2 ** 7, depth=50.0, inner=None, cycles=8,
     g = int(gridsize)
     if inner is None:
         inner = (g // 4, 3 * g // 4)
-    op = potential_well_operator(g, depth, inner)
+    if dimension not in ("2d", "3d"):
+        raise ValueError("dimension must be '2d' or '3d'")
+    three = dimension == "3d"
+    op = potential_well_operator(g, depth, inner, dimension=dimension)
     rng = np.random.RandomState(seed)
-    x0 = rng.random_sample(g * g)
+    x0 = rng.random_sample(g ** 3 if three else g * g)
     if method == "rqmg":
-        solver, M = MGCMTSolver(), identity_operator(g, "2d")
+        solver, M = MGCMTSolver(), identity_operator(g, dimension)
         rho = 0.0
         for _ in range(cycles):
             x0, rho = solver.vcycle_rqmg(x0, op, M, nu1=nu, nu2=nu, nmin=lowest)
@@ -245,7 +253,7 @@ def potential_well_eigensolve(gridsize=2 ** 7, depth=50.0, inner=None, cycles=8,
     # the iterate alternates between the two columns of slot W (x + delta w is written beside x); the V-cycle runs on
     # column 0 with shift 0: right-hand side (F, 0) = the gradient, result (V, 0) = the search direction
     X, XALT, PW, G = (W, 1), (W, 0), (V, 0), (F, 0)
-    plan = get_plan(op, int(lowest), nvec=2)
+    plan = get_plan(op, int(lowest), nvec=2, mass=identity_operator(g, "3d") if three else None)
     plan.set_shifts([0.0, 0.0])
     plan.upload(0, X[0], X[1], x0)
     plan.scale(0, 1.0 / np.sqrt(plan.dot(0, X, X)), X)
@@ -286,7 +294,7 @@ def potential_well_eigensolve(gridsize=2 ** 7, depth=50.0, inner=None, cycles=8,
 
 def block_eigensolve(op, k=4, cycles=12, nu=2, lowest=8, smoother="rb", seed=0, guesses=None, history=None, residuals=None,
                      use_p=True, stats=None, mass=None):
-    """SURVEY par. 8(f)4: the k lowest eigenpairs of a structured 2-D operator — of the pencil (A, M) with ``mass`` — by
+    """SURVEY par. 8(f)4: the k lowest eigenpairs of a structured 2-D or 3-D operator — of the pencil (A, M) with ``mass`` — by
     BLOCKED Rayleigh-Ritz with a V-cycle preconditioner: the reference's Rayleigh-quotient routines (rqmin's 2 x 2 problem
     over span{x, p} with its generalised form R y = lambda RM y, MGCMTSolver.py:33-50; the dead vcycle_rqmg2, :59-94, which
     carries M alongside A, :78-79) carried to a block of k vectors with LOBPCG-style updates.  Not in the reference: parity

@@ -194,17 +194,36 @@ def identity_operator(n, dimension="1d"):
     n = int(n)
     if dimension == "1d":
         return StructuredOperator("1d", n, [(None, tri_identity(n))])
+    if dimension == "3d":
+        return StructuredOperator("3d", n, [(tri_identity(n), tri_identity(n), tri_identity(n))])
     return StructuredOperator("2d", n, [(tri_identity(n), tri_identity(n))])
 
 
-def potential_well_operator(g, depth, inner, scale=-1.0 / np.pi ** 2):
+def potential_well_operator(g, depth, inner, scale=-1.0 / np.pi ** 2, dimension="2d"):
     """H = scale * laplacian(g, "2d") + diag(V) with the square-well potential of PotWellSolver.py:150-153 carried to
     2-D: V = `depth` outside the square [inner[0], inner[1])^2 of grid indices and 0 inside (BASELINE config 5).
 
     V = depth * (1 - chi (x) chi) is a sum of Kronecker products of diagonal factors, so H has three terms:
     I (x) (scale L + depth I)  +  (scale L) (x) I  -  (depth chi) (x) chi.
+
+    dimension="3d": the cube well (a quantum dot) V = depth * (1 - chi (x) chi (x) chi) on g^3 points, four terms:
+    I (x) I (x) (scale L + depth I)  +  I (x) (scale L) (x) I  +  (scale L) (x) I (x) I  -  (depth chi) (x) chi (x) chi.
     """
     g = int(g)
+    if dimension == "3d":
+        lo, hi = int(inner[0]), int(inner[1])
+        chi = np.zeros(g)
+        chi[lo:hi] = 1.0
+        L = tri_laplacian(g) * float(scale)
+        z1 = L.copy()
+        z1[1] += float(depth)
+        dchi = np.zeros((3, g))
+        dchi[1] = chi
+        i = tri_identity(g)
+        return StructuredOperator("3d", g, [(i, i.copy(), z1), (i.copy(), L.copy(), i.copy()), (L.copy(), i.copy(), i.copy()),
+                                            (dchi * (-float(depth)), dchi.copy(), dchi.copy())])
+    if dimension != "2d":
+        raise ValueError("potential_well_operator: dimension must be '2d' or '3d'")
     lo, hi = int(inner[0]), int(inner[1])
     chi = np.zeros(g)
     chi[lo:hi] = 1.0

@@ -53,8 +53,10 @@ class Plan:
         self._shifts = None
 
     def _create3d(self, op, mass, row_begin, row_end, strip_levels):
-        if mass is not None:
-            raise ValueError("mass operators are not available on 3-D grids")
+        if mass is not None and (mass.dimension != "3d" or mass.g != op.g):
+            raise ValueError("the mass operator of a 3-D plan must be a 3-D operator on the same %d^3 grid" % op.g)
+        if mass is not None and not 1 <= len(mass.terms) <= _lib.MAX_TERMS:
+            raise ValueError("a 3-D mass operator has 1 .. %d Kronecker terms, not %d" % (_lib.MAX_TERMS, len(mass.terms)))
         if row_begin or row_end or strip_levels:
             raise ValueError("3-D plans are not sharded")
         if self.lowest > 16:
@@ -64,7 +66,11 @@ class Plan:
         desc.nterms, desc.nvec, desc.g, desc.lowest = nterms, self.nvec, self.g, self.lowest
         desc.zfac, desc.yfac, desc.xfac = as_dp(zfac), as_dp(yfac), as_dp(xfac)
         desc.device = self.device
-        check(_lib.lib().mgcmt_plan_create3d(ctypes.byref(desc), ctypes.byref(self._h)))
+        if mass is None:
+            check(_lib.lib().mgcmt_plan_create3d(ctypes.byref(desc), ctypes.byref(self._h)))
+        else:
+            mt, mz, my, mx = mass.factor_blocks()
+            check(_lib.lib().mgcmt_plan_create3d_mass(ctypes.byref(desc), mt, as_dp(mz), as_dp(my), as_dp(mx), ctypes.byref(self._h)))
         n = c_int(0)
         check(_lib.lib().mgcmt_plan_num_levels(self._h, ctypes.byref(n)))
         self.num_levels = n.value

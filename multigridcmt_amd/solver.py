@@ -11,10 +11,11 @@ import math
 
 import numpy as np
 import scipy.linalg
+import scipy.sparse as sp
 
 from . import _lib
 from ._lib import GS_LEX, GS_MC, OP_A, OP_M, SLOT_F, SLOT_T, SLOT_V, SLOT_W, SOR_LEX, WJACOBI
-from .operators import StructuredOperator, UnrecognisedOperator, laplacian_operator, recognise, tag_structured
+from .operators import StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, recognise, tag_structured
 from .plan import get_plan
 from .processor import MGCMTProcessor
 from .stencil_maker import MGCMTStencilMaker
@@ -490,8 +491,20 @@ class MGCMTSolver:
         if M is None:
             raise AttributeError("'NoneType' object has no attribute 'dot'")      # what the reference raises (:19)
         opA = recognise(A, dimension)
-        opM = recognise(M, opA.dimension)
+        opM = self._mass_operator(M, opA)
+        if opA.dimension == "3d" and int(nmin) > 16:
+            raise ValueError("nmin=%d: on 3-D grids the coarsest level of the cycle has at most 16^3 points (nmin <= 16)" % int(nmin))
         return get_plan(opA, int(nmin), nvec=self._RQ_REGS, mass=opM)
+
+    @staticmethod
+    def _mass_operator(M, opA):
+        """the StructuredOperator of M; on 3-D grids an identity matrix (sparse.eye, RQMin.py:18) maps to the one-term
+        identity, which the library never applies (recognise would split its diagonal over three terms)"""
+        if opA.dimension == "3d" and sp.issparse(M) and M.shape == opA.shape:
+            d = M.diagonal()
+            if M.nnz == len(d) and np.all(d == 1.0):
+                return identity_operator(opA.g, "3d")
+        return recognise(M, opA.dimension)
 
     def rqmin(self, A, v0, M=None, nu=4):
         """MGCMTSolver.py:17-57 — returns (x, rho).  (The reference's x / rho are complex-typed with
@@ -500,7 +513,8 @@ class MGCMTSolver:
             raise AttributeError("'NoneType' object has no attribute 'dot'")      # what the reference raises (:19)
         x0 = np.asarray(v0, dtype=np.float64).reshape(-1)
         opA = recognise(A)
-        plan = get_plan(opA, opA.g, nvec=self._RQ_REGS, mass=recognise(M, opA.dimension))
+        # (one level; a 3-D plan's coarsest level is at most 16^3, the levels below hold no vectors until used)
+        plan = get_plan(opA, opA.g if opA.dimension != "3d" else min(opA.g, 16), nvec=self._RQ_REGS, mass=self._mass_operator(M, opA))
         plan.set_shifts(np.zeros(self._RQ_REGS))
         plan.upload(0, SLOT_V, self._X, x0)
         rho = self._rqmin_device(plan, 0, int(nu))
@@ -524,8 +538,8 @@ class MGCMTSolver:
     def vcycle_rqmg(self, x, A, M, nu1=4, nu2=4, nmin=2):
         """MGCMTSolver.py:99-122 — Rayleigh-quotient multigrid: rqmin, restrict the ITERATE, recurse
         on the Galerkin pair (R A P, R M P), add the interpolated coarse iterate, rqmin; returns (k, rho).
-        The reference only has the 1-D transfer operators here (:107-108); for a 2-D operator (a
-        StructuredOperator) the same algorithm runs with the 2-D ones and nmin counts points per direction."""
+        The reference only has the 1-D transfer operators here (:107-108); for a 2-D or 3-D operator the same algorithm
+        runs with the 2-D or 3-D ones (3-D: R = (1/8) P^T) and nmin counts points per direction (3-D: at most 16)."""
         x0 = np.asarray(x, dtype=np.float64).reshape(-1)
         g = recognise(A).g                     # points per direction (the vector length in 1-D, as in the reference)
         plan = self._rq_plan(A, M, max(int(nmin), 2) if g > nmin else g)
@@ -545,7 +559,10 @@ class MGCMTSolver:
         if nv > _lib.MAX_VEC:
             raise ValueError("at most %d columns per call" % _lib.MAX_VEC)
         opA = recognise(A)
-        plan = get_plan(opA, max(int(nmin), 2) if opA.g > nmin else opA.g, nvec=max(self._RQ_REGS, nv), mass=recognise(M, opA.dimension))
+        lowest = max(int(nmin), 2) if opA.g > nmin else opA.g
+        if opA.dimension == "3d" and lowest > 16:
+            raise ValueError("nmin=%d: on 3-D grids the coarsest level of the cycle has at most 16^3 points (nmin <= 16)" % int(nmin))
+        plan = get_plan(opA, lowest, nvec=max(self._RQ_REGS, nv), mass=self._mass_operator(M, opA))
         plan.set_shifts(np.zeros(plan.nvec))
         for i in range(nv):
             plan.upload(0, SLOT_W, i, k0[:, i])
@@ -586,7 +603,10 @@ class MGCMTSolver:
         if not repaired:
             raise NameError("name 'eigh' is not defined")
         x0 = np.asarray(v0, dtype=np.float64).reshape(-1)
-        g = recognise(A).g
+        opA = recognise(A)
+        if opA.dimension == "3d":
+            raise ValueError("twogridrqmin is not available on 3-D grids (use vcycle_rqmg)")
+        g = opA.g
         if g < 4:
             raise ValueError("twogridrqmin needs at least 4 points per direction")
         plan = self._rq_plan(A, M, g // 2)

@@ -1,0 +1,511 @@
+// The level hierarchy of a plan: the host Galerkin factors of every level, their upload (with the classification of
+// the operator the kernels branch on), plan creation for 1, 2 and 3 axes, destruction and the entries that describe levels.
+// Host code only.
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "plan_internal.h"
+
+using namespace mgcmt;
+
+namespace {
+
+bool is_pow2(int64_t x) { return x > 0 && (x & (x - 1)) == 0; }
+
+// Galerkin product of one factor: R1 * T * P1 with R1 = full weighting (1/4,1/2,1/4 on fine
+// 2I..2I+2) and P1 = 2 R1^T (MGCMTStencilMaker.py:27-78, MGCMTSolver.py:318).  Stays tridiagonal.
+Tri galerkin(const Tri& f) {
+  static const double rw[3] = {0.25, 0.5, 0.25};
+  static const double pw[3] = {0.5, 1.0, 0.5};
+  Tri c;
+  c.n = f.n / 2;
+  c.a.assign(3 * c.n, 0.0);
+  for (int64_t I = 0; I < c.n; ++I) {
+    for (int dJ = -1; dJ <= 1; ++dJ) {
+      const int64_t J = I + dJ;
+      if (J < 0 || J >= c.n) continue;
+      double acc = 0.0;
+      for (int t = 0; t < 3; ++t) {
+        const int64_t a = 2 * I + t;
+        if (a >= f.n) continue;
+        for (int s = -1; s <= 1; ++s) {
+          const int64_t b = a + s;
+          if (b < 0 || b >= f.n) continue;
+          const int64_t o = b - 2 * J;
+          if (o < 0 || o > 2) continue;
+          acc += rw[t] * f.at(a, b) * pw[o];
+        }
+      }
+      c.a[(dJ + 1) * c.n + I] = acc;
+    }
+  }
+  return c;
+}
+
+Tri identity_tri(int64_t n) {
+  Tri t;
+  t.n = n;
+  t.a.assign(3 * n, 0.0);
+  for (int64_t i = 0; i < n; ++i) t.a[n + i] = 1.0;
+  return t;
+}
+
+// n doubles on the device, freed with the operator (d->owned)
+int upload_array(DevOp* d, const double* src, size_t n, const double** dst) {
+  double* q = nullptr;
+  MG_HIP(hipMalloc((void**)&q, n * sizeof(double)));
+  d->owned.push_back(q);
+  MG_HIP(hipMemcpy(q, src, n * sizeof(double), hipMemcpyHostToDevice));
+  *dst = q;
+  return MGCMT_OK;
+}
+
+int upload_op(const HostOp& h, const Level& L, int dim, DevOp* d) {
+  KOp& k = d->k;
+  k = KOp{};
+  k.nterms = h.nterms;
+  k.ldx = L.nr + 2 * L.halo;
+  k.ldy = L.gc;
+  for (int m = 0; m < h.nterms; ++m) {
+    std::vector<double> xs(3 * k.ldx, 0.0);
+    for (int part = 0; part < 3; ++part)
+      for (int64_t i = -L.halo; i < L.nr + L.halo; ++i) {
+        const int64_t gi = L.r0 + i;
+        if (gi >= 0 && gi < L.gr) xs[part * k.ldx + (i + L.halo)] = h.X[m].a[part * L.gr + gi];
+      }
+    const double* dx = nullptr;
+    MG_TRY(upload_array(d, xs.data(), xs.size(), &dx));
+    MG_TRY(upload_array(d, h.Y[m].a.data(), 3 * L.gc, &k.Y[m]));
+    k.X[m] = dx + L.halo;
+  }
+  if (dim == 1 && h.nterms > 0) {
+    // 1-D: X_m is 1 x 1, so the operator is ONE tridiagonal, sum_m x_m Y_m — folded here for the fused 1-D passes
+    const int64_t n = L.gc;
+    std::vector<double> t(3 * n, 0.0);
+    for (int m = 0; m < h.nterms; ++m) {
+      const double x = h.X[m].di(0);
+      for (int64_t i = 0; i < 3 * n; ++i) t[i] += x * h.Y[m].a[i];
+    }
+    MG_TRY(upload_array(d, t.data(), t.size(), &k.tri));
+    k.one_d = 1;
+    bool constant = n >= 3;
+    for (int64_t i = 0; constant && i < n; ++i) {
+      if (i > 0 && t[i] != t[1]) constant = false;                          // lower (entry 0 is outside the matrix)
+      if (i + 1 < n && (t[n + i] != t[n] || t[2 * n + i] != t[2 * n])) constant = false;  // diagonal but the last, upper (the last entry is outside)
+    }
+    if (constant) {
+      k.tri_const = 1;
+      k.t_lo = t[1];
+      k.t_di = t[n];
+      k.t_up = t[2 * n];
+      k.t_last = t[2 * n - 1];
+    }
+  }
+  // constant-coefficient 5-point (2-D) / 3-point (1-D) detection: every factor Toeplitz and the
+  // corner coefficients zero -> the kernels take three scalars instead of the factor arrays
+  auto toeplitz = [](const Tri& t, double* lo, double* di, double* up) {
+    *di = t.di(0);
+    *lo = t.n > 1 ? t.lo(1) : 0.0;
+    *up = t.n > 1 ? t.up(0) : 0.0;
+    for (int64_t i = 0; i < t.n; ++i) {
+      if (t.di(i) != *di) return false;
+      if (i > 0 && t.lo(i) != *lo) return false;
+      if (i + 1 < t.n && t.up(i) != *up) return false;
+    }
+    return true;
+  };
+  double c[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  bool all = h.nterms > 0;
+  for (int m = 0; m < h.nterms && all; ++m) {
+    double x[3], y[3];
+    if (!toeplitz(h.X[m], &x[0], &x[1], &x[2]) || !toeplitz(h.Y[m], &y[0], &y[1], &y[2])) {
+      all = false;
+      break;
+    }
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) c[a][b] += x[a] * y[b];
+  }
+  if (all && c[0][0] == 0 && c[0][2] == 0 && c[2][0] == 0 && c[2][2] == 0 && c[0][1] == c[2][1] && c[1][0] == c[1][2] &&
+      (dim == 2 || c[0][1] == 0)) {
+    k.five_point = 1;
+    k.c0 = c[1][1];
+    k.cn = c[0][1];
+    k.cw = c[1][0];
+  }
+  // constant 5-point part plus ONE product potential on the diagonal: the Toeplitz terms form a 5-point operator,
+  // the remaining term has diagonal factors only
+  if (!k.five_point && dim == 2 && h.nterms >= 2) {
+    auto diagonal_only = [](const Tri& t) {
+      for (int64_t i = 0; i < t.n; ++i)
+        if ((i > 0 && t.lo(i) != 0.0) || (i + 1 < t.n && t.up(i) != 0.0)) return false;
+      return true;
+    };
+    double c5[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    int nd = 0, dm[2] = {0, 0};
+    bool ok = true;
+    for (int m = 0; m < h.nterms && ok; ++m) {
+      double x[3], y[3];
+      if (toeplitz(h.X[m], &x[0], &x[1], &x[2]) && toeplitz(h.Y[m], &y[0], &y[1], &y[2])) {
+        for (int a = 0; a < 3; ++a)
+          for (int b = 0; b < 3; ++b) c5[a][b] += x[a] * y[b];
+      } else if (diagonal_only(h.X[m]) && diagonal_only(h.Y[m]) && nd < 1) {
+        dm[nd++] = m;
+      } else {
+        ok = false;
+      }
+    }
+    if (ok && nd == 1 && c5[0][0] == 0 && c5[0][2] == 0 && c5[2][0] == 0 && c5[2][2] == 0 && c5[0][1] == c5[2][1] && c5[1][0] == c5[1][2]) {
+      k.five_diag = 1;
+      k.ndiag = nd;
+      k.c0 = c5[1][1];
+      k.cn = c5[0][1];
+      k.cw = c5[1][0];
+      for (int t = 0; t < nd; ++t) {
+        k.dX[t] = k.X[dm[t]] + k.ldx;  // the diagonal row of the factor arrays ([lower | diag | upper])
+        k.dY[t] = k.Y[dm[t]] + k.ldy;
+      }
+    }
+  }
+  // Galerkin levels of a constant operator: Toeplitz factors whose last diagonal entry differs
+  if (!k.five_point && !k.five_diag && dim == 2 && h.nterms > 0) {
+    auto toeplitz_but_last = [](const Tri& t, double* lo, double* di, double* up, double* last) {
+      if (t.n < 3) return false;
+      *di = t.di(0);
+      *lo = t.lo(1);
+      *up = t.up(0);
+      *last = t.di(t.n - 1);
+      for (int64_t i = 0; i < t.n; ++i) {
+        if (i + 1 < t.n && t.di(i) != *di) return false;
+        if (i > 0 && t.lo(i) != *lo) return false;
+        if (i + 1 < t.n && t.up(i) != *up) return false;
+      }
+      return true;
+    };
+    bool ok = true;
+    double c9[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, crow[3] = {0, 0, 0}, ccol[3] = {0, 0, 0}, corner = 0;
+    int nconst = 0, nvar = 0, var_term = -1;
+    for (int m = 0; m < h.nterms && ok; ++m) {
+      double x[3], y[3], xl, yl;
+      if (!(toeplitz_but_last(h.X[m], &x[0], &x[1], &x[2], &xl) && toeplitz_but_last(h.Y[m], &y[0], &y[1], &y[2], &yl))) {
+        // a term with variable factors: one of them may ride on top of the constant part (nine_var)
+        ++nvar;
+        var_term = m;
+        ok = nvar <= 1;
+        continue;
+      }
+      ++nconst;
+      for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) c9[a][b] += x[a] * y[b];
+      for (int b = 0; b < 3; ++b) crow[b] += xl * y[b];   // last row: X's diagonal entry is the modified one
+      for (int a = 0; a < 3; ++a) ccol[a] += x[a] * yl;   // last column: Y's diagonal entry is the modified one
+      corner += xl * yl;
+      crow[1] += 0.0;
+    }
+    if (ok && nconst >= 1) {
+      // on the last row the centre coefficient of the last column is the corner; crow[1] is the centre elsewhere
+      if (nvar == 0) {
+        k.nine_const = 1;
+      } else {
+        k.nine_var = 1;
+        k.vX = k.X[var_term];
+        k.vY = k.Y[var_term];
+      }
+      for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) k.c9[a][b] = c9[a][b];
+        k.c9row[a] = crow[a];
+        k.c9col[a] = ccol[a];
+      }
+      k.c9corner = corner;
+    }
+  }
+  return MGCMT_OK;
+}
+
+// a 3-D level's factors on the device, and the constant 7-point form where every factor is Toeplitz and the summed
+// stencil has no entry off the three axes
+int upload_op3(const HostOp& h, int64_t n, DevOp* d) {
+  K3Op& k = d->k3;
+  k = K3Op{};
+  k.nterms = h.nterms;
+  k.n = (long)n;
+  for (int m = 0; m < h.nterms; ++m) {
+    MG_TRY(upload_array(d, h.X[m].a.data(), h.X[m].a.size(), &k.X[m]));
+    MG_TRY(upload_array(d, h.Y[m].a.data(), h.Y[m].a.size(), &k.Y[m]));
+    MG_TRY(upload_array(d, h.Z[m].a.data(), h.Z[m].a.size(), &k.Z[m]));
+  }
+  auto toeplitz = [](const Tri& t, double* f) {
+    f[1] = t.di(0);
+    f[0] = t.n > 1 ? t.lo(1) : 0.0;
+    f[2] = t.n > 1 ? t.up(0) : 0.0;
+    for (int64_t i = 0; i < t.n; ++i) {
+      if (t.di(i) != f[1]) return false;
+      if (i > 0 && t.lo(i) != f[0]) return false;
+      if (i + 1 < t.n && t.up(i) != f[2]) return false;
+    }
+    return true;
+  };
+  double c[3][3][3] = {};
+  bool all = h.nterms > 0 && n >= 2;
+  for (int m = 0; m < h.nterms && all; ++m) {
+    double fz[3], fy[3], fx[3];
+    if (!toeplitz(h.X[m], fz) || !toeplitz(h.Y[m], fy) || !toeplitz(h.Z[m], fx)) {
+      all = false;
+      break;
+    }
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b)
+        for (int e = 0; e < 3; ++e) c[a][b][e] += fz[a] * fy[b] * fx[e];
+  }
+  for (int a = 0; a < 3 && all; ++a)
+    for (int b = 0; b < 3; ++b)
+      for (int e = 0; e < 3; ++e)
+        if ((a != 1) + (b != 1) + (e != 1) >= 2 && c[a][b][e] != 0.0) all = false;
+  if (all) {
+    k.seven = 1;
+    k.c0 = c[1][1][1];
+    k.czm = c[0][1][1];
+    k.czp = c[2][1][1];
+    k.cym = c[1][0][1];
+    k.cyp = c[1][2][1];
+    k.cxm = c[1][1][0];
+    k.cxp = c[1][1][2];
+  }
+  return MGCMT_OK;
+}
+
+// What a creator asks for.  fac / m_fac: the factor arrays of A / M per axis as HostOp holds them — {X, Y, Z}, i.e.
+// 3-D: {z, y, x}; 2-D: {rows, columns}; 1-D: {none, the vector} (X is the 1 x 1 identity there) — nterms blocks of 3 g each
+struct PlanSpec {
+  int dim, nvec, device;
+  int64_t g, lowest;
+  int nterms, m_nterms;
+  const double* fac[3];
+  const double* m_fac[3];
+  int64_t row_begin, row_end;  // a 2-D plan's rows of level 0, (0, 0) = all; ignored otherwise
+  int strip_levels;
+};
+
+// the seven pieces of device scratch every plan starts with
+hipError_t alloc_scratch(mgcmt_plan* p) {
+  hipError_t e = hipMalloc((void**)&p->d_shifts, sizeof(double) * kMaxVec);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->d_zero, sizeof(double) * kMaxVec);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->d_partials, sizeof(double) * (kMaxVec + 1) * 1024 * 2);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->d_mgs, sizeof(double) * mgs_block_words());
+  if (e == hipSuccess) e = hipMalloc((void**)&p->d_scalars, sizeof(double) * 4 * kMaxVec);
+  if (e == hipSuccess) e = hipMemset(p->d_shifts, 0, sizeof(double) * kMaxVec);
+  if (e == hipSuccess) e = hipMemset(p->d_zero, 0, sizeof(double) * kMaxVec);
+  return e;
+}
+
+// A plan of 1, 2 or 3 axes: level l has g >> l points per axis.  1-D: one "row" of g >> l; 2-D: (g >> l)^2 as rows
+// (a strip of them on the first strip_levels levels); 3-D: g >> l z-planes of (g >> l)^2 points, one zero halo plane
+// above and below.  The creators have checked what is theirs alone (dim, the mass terms, the direct solve's limit in 3-D).
+int build_plan(const PlanSpec& d, mgcmt_plan** out) {
+  if (!is_pow2(d.g) || !is_pow2(d.lowest) || d.lowest > d.g) return fail(MGCMT_ERR_INVALID, "g and lowest must be powers of two with lowest <= g");
+  if (d.g < 2) return fail(MGCMT_ERR_INVALID, "Length of start vector is not a power of 2");
+  if (d.lowest < 2) return fail(MGCMT_ERR_INVALID, "lowest must be at least 2");
+  if (d.nterms < 1 || d.nterms > kMaxTerms) return fail(MGCMT_ERR_INVALID, "nterms out of range");
+  const int first_axis = d.dim == 1 ? 1 : 0, naxes = d.dim == 3 ? 3 : 2;
+  for (int a = first_axis; a < naxes; ++a)
+    if (!d.fac[a]) return fail(MGCMT_ERR_INVALID, "missing factor arrays");
+  if (d.nvec < 1 || d.nvec > kMaxVec) return fail(MGCMT_ERR_INVALID, "nvec out of range (1..32)");
+  const int64_t rows = d.dim == 1 ? 1 : d.g;
+  int64_t rb = d.row_begin, re = d.row_end;
+  if (d.dim != 2 || (rb == 0 && re == 0)) {
+    rb = 0;
+    re = rows;
+  }
+  if (rb < 0 || re > rows || rb >= re) return fail(MGCMT_ERR_INVALID, "bad row range");
+  MG_HIP(hipSetDevice(d.device));
+
+  mgcmt_plan* p = new mgcmt_plan();
+  p->dim = d.dim;
+  p->nvec = d.nvec;
+  p->device = d.device;
+  p->g = d.g;
+  p->lowest = d.lowest;
+  p->has_mass = d.m_nterms > 0;
+  p->h_shifts.assign(kMaxVec, 0.0);
+  const char* mb = getenv("MGCMT_MGS_BLOCK_MIN");  // points per column from which Gram-Schmidt takes its two-pass form (tests, tuning)
+  if (mb && atol(mb) > 1) p->mgs_block_min = atol(mb);
+  if (d.dim != 3) {
+    const char* e = getenv("MGCMT_TAIL_DENSE");  // "0": the tail as the LDS-resident launch by default (the host-only test build:
+    p->use_tail_dense = !(e && e[0] == '0');     // emulating the 1024 workgroups that form the matrix takes minutes)
+  }
+
+  int nlev = 1;
+  for (int64_t s = d.g; s > d.lowest; s >>= 1) ++nlev;
+  const bool whole = rb == 0 && re == rows;
+  int strip_levels = whole ? 0 : (d.strip_levels > 0 ? d.strip_levels : nlev);
+  if (strip_levels > nlev) strip_levels = nlev;
+  if (!whole) {
+    const int64_t align = (int64_t)1 << (strip_levels - 1);
+    if (rb % align || re % align) {
+      delete p;
+      return fail(MGCMT_ERR_INVALID, "strip bounds must be multiples of 2^(strip_levels-1)");
+    }
+  }
+
+  p->levels.resize(nlev);
+  for (int l = 0; l < nlev; ++l) {
+    Level& L = p->levels[l];
+    const int64_t n = d.g >> l;
+    L.gr = d.dim == 1 ? 1 : n;
+    L.gc = d.dim == 3 ? n * n : n;
+    L.r0 = l < strip_levels ? rb >> l : 0;
+    L.nr = l < strip_levels ? (re - rb) >> l : L.gr;
+    L.halo = d.dim == 2 ? kHalo : 1;
+    L.stride = ((L.nr + 2 * L.halo) * L.gc + 31) / 32 * 32;
+    // level 0 holds the caller's factors; below it R A P (and R M P) with P = P1 (x) ... (x) P1: each factor coarsened
+    // on its own (galerkin), a Kronecker sum stays one
+    auto build = [&](HostOp& h, const HostOp* finer, int nterms, const double* const* src) {
+      h.nterms = nterms;
+      std::vector<Tri>* mine[3] = {&h.X, &h.Y, &h.Z};
+      for (int a = 0; a < naxes; ++a) {
+        const std::vector<Tri>* above = !finer ? nullptr : a == 0 ? &finer->X : a == 1 ? &finer->Y : &finer->Z;
+        mine[a]->resize(nterms);
+        for (int m = 0; m < nterms; ++m) {
+          Tri& t = (*mine[a])[m];
+          if (a < first_axis) {
+            t = identity_tri(1);
+          } else if (l == 0) {
+            t.n = d.g;
+            t.a.assign(src[a] + (size_t)m * 3 * d.g, src[a] + (size_t)(m + 1) * 3 * d.g);
+          } else {
+            t = galerkin((*above)[m]);
+          }
+        }
+      }
+    };
+    build(L.hA, l ? &p->levels[l - 1].hA : nullptr, d.nterms, d.fac);
+    if (p->has_mass) build(L.hM, l ? &p->levels[l - 1].hM : nullptr, d.m_nterms, d.m_fac);
+    int rc = d.dim == 3 ? upload_op3(L.hA, n, &L.dA) : upload_op(L.hA, L, d.dim, &L.dA);
+    if (rc == MGCMT_OK && p->has_mass) rc = d.dim == 3 ? upload_op3(L.hM, n, &L.dM) : upload_op(L.hM, L, d.dim, &L.dM);
+    if (rc != MGCMT_OK) {
+      mgcmt_plan_destroy(p);
+      return rc;
+    }
+  }
+  const hipError_t e = alloc_scratch(p);
+  if (e != hipSuccess) {
+    mgcmt_plan_destroy(p);
+    return fail(MGCMT_ERR_HIP, std::string("plan scratch allocation: ") + hipGetErrorString(e));
+  }
+  *out = p;
+  return MGCMT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mgcmt_plan_create(const mgcmt_plan_desc* d, mgcmt_plan** out) {
+  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (d->dim != 1 && d->dim != 2) return fail(MGCMT_ERR_INVALID, "dim must be 1 or 2");
+  if (d->m_nterms < 0 || d->m_nterms > kMaxTerms) return fail(MGCMT_ERR_INVALID, "nterms out of range");
+  return build_plan(PlanSpec{d->dim, d->nvec, d->device, d->g, d->lowest, d->nterms, d->m_nterms, {d->xfac, d->yfac, nullptr},
+                             {d->m_xfac, d->m_yfac, nullptr}, d->row_begin, d->row_end, d->strip_levels},
+                    out);
+}
+
+static int create3d(const mgcmt_plan3d_desc* d, int32_t m_nterms, const double* m_zfac, const double* m_yfac, const double* m_xfac,
+                    mgcmt_plan** out) {
+  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (d->lowest > 16) return fail(MGCMT_ERR_INVALID, "lowest must be at most 16 on a 3-D plan (the coarsest level is solved directly)");
+  if (m_nterms < 0 || m_nterms > kMaxTerms) return fail(MGCMT_ERR_INVALID, "mass nterms out of range");
+  if (m_nterms > 0 && (!m_xfac || !m_yfac || !m_zfac)) return fail(MGCMT_ERR_INVALID, "missing mass factor arrays");
+  return build_plan(PlanSpec{3, d->nvec, d->device, d->g, d->lowest, d->nterms, m_nterms, {d->zfac, d->yfac, d->xfac},
+                             {m_zfac, m_yfac, m_xfac}, 0, 0, 0},
+                    out);
+}
+
+int mgcmt_plan_create3d(const mgcmt_plan3d_desc* d, mgcmt_plan** out) { return create3d(d, 0, nullptr, nullptr, nullptr, out); }
+
+int mgcmt_plan_create3d_mass(const mgcmt_plan3d_desc* d, int32_t m_nterms, const double* m_zfac, const double* m_yfac, const double* m_xfac,
+                             mgcmt_plan** out) {
+  if (m_nterms < 1 || m_nterms > kMaxTerms) return fail(MGCMT_ERR_INVALID, "mass nterms out of range (1..4)");
+  return create3d(d, m_nterms, m_zfac, m_yfac, m_xfac, out);
+}
+
+int mgcmt_plan_destroy(mgcmt_plan* p) {
+  if (!p) return MGCMT_OK;
+  comm_release(p);
+  for (Level& L : p->levels) {
+    for (int s = 0; s < 4; ++s)
+      if (L.base[s]) (void)hipFree(L.base[s]);
+    for (double* q : L.dA.owned) (void)hipFree(q);
+    for (double* q : L.dM.owned) (void)hipFree(q);
+    if (L.band.b.ab) (void)hipFree(L.band.b.ab);
+    if (L.band.b.piv) (void)hipFree(L.band.b.piv);
+    if (L.band.inv) (void)hipFree(L.band.inv);
+  }
+  for (auto& g : p->graphs)
+    if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
+  if (p->capture_stream) (void)hipStreamDestroy(p->capture_stream);
+  if (p->d_rq) (void)hipFree(p->d_rq);
+  if (p->d_rqstate) (void)hipFree(p->d_rqstate);
+  if (p->d_rqhistory) (void)hipFree(p->d_rqhistory);
+  if (p->d_mgs) (void)hipFree(p->d_mgs);
+  if (p->tailmat.mt) (void)hipFree(p->tailmat.mt);
+  if (p->lex_carry) (void)hipFree(p->lex_carry);
+  if (p->lex_sync) (void)hipFree(p->lex_sync);
+  if (p->d_shifts) (void)hipFree(p->d_shifts);
+  if (p->d_zero) (void)hipFree(p->d_zero);
+  if (p->d_partials) (void)hipFree(p->d_partials);
+  if (p->d_scalars) (void)hipFree(p->d_scalars);
+  delete p;
+  return MGCMT_OK;
+}
+
+int mgcmt_plan_num_levels(const mgcmt_plan* p, int* levels) {
+  if (!p || !levels) return fail(MGCMT_ERR_INVALID, "null argument");
+  *levels = (int)p->levels.size();
+  return MGCMT_OK;
+}
+
+int mgcmt_plan_level_shape(const mgcmt_plan* p, int l, int64_t* rows, int64_t* cols, int64_t* row_begin) {
+  MG_TRY(check_level(p, l));
+  if (rows) *rows = p->levels[l].nr;
+  if (cols) *cols = p->levels[l].gc;
+  if (row_begin) *row_begin = p->levels[l].r0;
+  return MGCMT_OK;
+}
+
+int mgcmt_plan_get_factors(const mgcmt_plan* p, int op, int l, int which, double* out, int64_t capacity) {
+  MG_TRY(check_level(p, l));
+  const HostOp& h = op == MGCMT_OP_M ? p->levels[l].hM : p->levels[l].hA;
+  if (op == MGCMT_OP_M && !p->has_mass) return fail(MGCMT_ERR_INVALID, "plan has no mass operator");
+  if (p->dim == 3 && (which < 0 || which > 2)) return fail(MGCMT_ERR_INVALID, "which must be 0 (z), 1 (y) or 2 (x) on a 3-D plan");
+  const std::vector<Tri>& f = which == 0 ? h.X : (which == 2 && p->dim == 3) ? h.Z : h.Y;
+  int64_t need = 0;
+  for (const Tri& t : f) need += (int64_t)t.a.size();
+  if (!out || capacity < need) return fail(MGCMT_ERR_INVALID, "factor buffer too small");
+  int64_t o = 0;
+  for (const Tri& t : f) {
+    memcpy(out + o, t.a.data(), t.a.size() * sizeof(double));
+    o += (int64_t)t.a.size();
+  }
+  return MGCMT_OK;
+}
+
+int mgcmt_plan_level_halo(const mgcmt_plan* p, int l, int* halo_rows, int* exchanged) {
+  MG_TRY(check_level(p, l));
+  if (halo_rows) *halo_rows = p->levels[l].halo;
+  if (exchanged) *exchanged = p->dim == 3 ? 0 : exchanged_rows(p, l);  // (a 3-D plan is never sharded)
+  return MGCMT_OK;
+}
+
+int mgcmt_level_operator_kind(const mgcmt_plan* p, int l, int* kind) {
+  MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_level_operator_kind"));
+  MG_TRY(check_level(p, l));
+  if (!kind) return fail(MGCMT_ERR_INVALID, "null output");
+  const KOp& k = p->levels[l].dA.k;
+  *kind = k.five_point ? MGCMT_OPK_FIVE_POINT : k.five_diag ? MGCMT_OPK_FIVE_DIAG : k.nine_const ? MGCMT_OPK_NINE_CONST : k.nine_var ? MGCMT_OPK_NINE_VAR : MGCMT_OPK_GENERAL;
+  return MGCMT_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,8 @@
-// Host-side types of libmgcmt_hip.so shared by plan.hip (hierarchy, single-GPU cycle, C-ABI) and sharded.hip
-// (communicator, sharded cycle).  Not part of the ABI.
+// Host-side types of libmgcmt_hip.so and what its host files share: hierarchy.hip (Galerkin hierarchy, plan creation),
+// cycle.hip (single-GPU cycle, HIP-graph cache), rq_host.hip (Rayleigh-quotient drivers), plan.hip (checks, vector
+// storage, the rest of the C-ABI) and sharded.hip (communicator, sharded cycle).  Not part of the ABI.
 #pragma once
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -137,13 +139,19 @@ struct mgcmt_plan {
 
 
 namespace mgcmt {
-// helpers of plan.hip used by sharded.hip
+// ---- plan.hip ----
 int fail(int code, const std::string& msg);
 // MGCMT_ERR_UNSUPPORTED (with a message naming `what`) on a 3-D plan: the entries of the 1-D / 2-D path that have no
 // 3-D form; MGCMT_OK otherwise (a null plan included: the entry's own checks report it)
 int unsupported_3d(const mgcmt_plan* p, const char* what);
+int unsupported_3d_massless(const mgcmt_plan* p, const char* what);  // ... on a 3-D plan without a mass operator
+int check_level(const mgcmt_plan* p, int l);
+int check_vec(const mgcmt_plan* p, int l, int slot, int vec);
+int check_k(const mgcmt_plan* p, int k);
+inline hipStream_t S(void* s) { return (hipStream_t)s; }
 int ensure_slot(mgcmt_plan* p, int l, int slot);
 int post_launch();
+// ---- cycle.hip ----
 bool fused_level(const mgcmt_plan* p, int l, int kind);
 int pass_sweeps(const mgcmt_plan* p, int l, int kind, int left);
 // halo rows of level l that a sharded cycle exchanges and its passes read (<= the level's halo): 8 behind a 5-point
@@ -153,8 +161,20 @@ int exchanged_rows(const mgcmt_plan* p, int l);
 // leaves the buffer roles alone (the caller issues the other row ranges of the same pass and swaps once)
 int fused_pass(mgcmt_plan* p, int l, int kind, int nsweep, double omega, int mode, int k, hipStream_t s, int npre = 0,
                long out_lo = 0, long out_hi = -1, bool swap = true, long out_lo2 = 0, long out_hi2 = 0);
-void comm_release(mgcmt_plan* p);  // sharded.hip: frees p->comm
-// transfer.hip: a whole vector between caller memory and the device through the pinned ring; completed on return
+int smooth_impl(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, hipStream_t s);
+int gramschmidt_impl(mgcmt_plan* p, int l, int slot, int k, int modified, hipStream_t s);
+int lex_wave_check(mgcmt_plan* p);  // a synchronising call looks at the error word of the wave pipeline
+// The plan's HIP-graph cache: `body` (a stream-ordered launch sequence fixed by `params` and by the buffer bases in
+// `key`) runs eagerly the first time `params` is seen, is captured, launched and stored under `key` the second time, and
+// is replayed on every later call with an equal key.  `prepare` (may be empty) is what a replay or a capture relies on
+// but must not contain; it runs eagerly before either.  swaps_buffers: the body exchanges the V / T bases of levels, so
+// they are recorded after the capture and restored after a replay, a capture that fails cannot be run again (an error)
+// and any failure turns the plan's graphs off; without it a failure clears the HIP error and the body runs eagerly.
+int graph_run(mgcmt_plan* p, const std::string& params, const std::string& key, bool swaps_buffers, const std::function<int()>& prepare,
+              const std::function<int(hipStream_t)>& body, hipStream_t s);
+// ---- sharded.hip, transfer.hip ----
+void comm_release(mgcmt_plan* p);  // frees p->comm
+// a whole vector between caller memory and the device through the pinned ring; completed on return
 int transfer(int device, bool upload, void* dev, void* host, size_t bytes, hipStream_t stream);
 }  // namespace mgcmt
 

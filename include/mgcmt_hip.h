@@ -126,6 +126,26 @@ int mgcmt_plan_create3d(const mgcmt_plan3d_desc* desc, mgcmt_plan** out);
  * entries need one on a 3-D plan. */
 int mgcmt_plan_create3d_mass(const mgcmt_plan3d_desc* desc, int32_t m_nterms, const double* m_zfac, const double* m_yfac, const double* m_xfac,
                              mgcmt_plan** out);
+/* A 2-D plan whose operator carries an arbitrary diagonal on top of its Kronecker terms:
+ *     A = sum_m X_m (x) Y_m + diag(point_diag)  - shift * I,
+ * point_diag = g x g numbers on the host, index [i * g + j] = grid point (i, j): H = -c Laplacian + V(x, y) with any
+ * potential V (the Kronecker terms carry the Laplacian and whatever of V is separable, point_diag the rest).  Under the
+ * reference's transfers the Galerkin levels R A P (MGCMTSolver.py:318) are the Kronecker part's usual levels plus a 9-point
+ * stencil with per-point coefficients, R diag(point_diag) P, formed on the device at creation.  desc as for
+ * mgcmt_plan_create with dim = 2, no mass operator and no row strip.  Such a plan runs mgcmt_vcycle (HIP-graph replay,
+ * Gram-Schmidt, per-column shifts and MGCMT_CYCLE_ZERO_START included), mgcmt_smooth, mgcmt_apply, the transfers, the
+ * coarse solve and the vector algebra with MGCMT_WJACOBI and MGCMT_GS_MC: the fine level on the fused row-streaming
+ * pass (policy Op5P; mgcmt_fused_pass and mgcmt_time_fused_pass take level 0 of such a plan), the Galerkin levels as
+ * one launch per operation (csrc/kernels_pointwise.hip), both with the same bits as MGCMT_OPT_FUSED = 0.  The entries
+ * that know Kronecker terms only return MGCMT_ERR_UNSUPPORTED with a message that names the point diagonal: the
+ * lexicographic smoother kinds, mgcmt_twogrid,
+ * mgcmt_rqmin / mgcmt_rq_line_step / mgcmt_vcycle_rqmg, mgcmt_ritz_pair, mgcmt_rayleigh_residual, mgcmt_comm_init /
+ * mgcmt_comm_init_external and mgcmt_sharded_vcycle. */
+int mgcmt_plan_create_pot(const mgcmt_plan_desc* desc, const double* point_diag, mgcmt_plan** out);
+/* host copy of the per-point part of `level` of such a plan: level 0 rows x cols numbers (point_diag); a level below nine
+ * planes of rows x cols, plane 3 a + b = the coefficient of v(i + a - 1, j + b - 1) in row (i, j), zero towards points
+ * outside the grid.  The level's matrix is the one assembled from mgcmt_plan_get_factors plus these. */
+int mgcmt_plan_get_point_stencil(const mgcmt_plan* plan, int level, double* out, int64_t capacity);
 int mgcmt_plan_num_levels(const mgcmt_plan* plan, int* levels);
 int mgcmt_plan_level_shape(const mgcmt_plan* plan, int level, int64_t* rows, int64_t* cols, int64_t* row_begin);
 /* host copy of a level's factors, [nterms][3][n] with n = global rows (which=0) or cols (which=1) */
@@ -273,12 +293,16 @@ int mgcmt_fused_max_recompute(const mgcmt_plan* plan, int level, int kind, int n
  * (Kronecker terms with variable factors), MGCMT_OPK_FIVE_POINT (constant 5-point / 3-point: the scaled, shifted
  * Laplacian of MGCMTStencilMaker.py:15-25), MGCMT_OPK_FIVE_DIAG (the same plus a product potential on the diagonal),
  * MGCMT_OPK_NINE_CONST (Galerkin coarsenings R*A*P, MGCMTSolver.py:318, of a constant operator), MGCMT_OPK_NINE_VAR
- * (the same plus one term with variable factors: the coarsened product potential). */
+ * (the same plus one term with variable factors: the coarsened product potential).  On a plan with a point diagonal
+ * (mgcmt_plan_create_pot): MGCMT_OPK_POINT_DIAG (level 0: the Kronecker terms, a 5-point operator, plus a per-point diagonal)
+ * and MGCMT_OPK_NINE_POINT (the Galerkin levels: a 9-point stencil with a per-point part). */
 #define MGCMT_OPK_GENERAL 0
 #define MGCMT_OPK_FIVE_POINT 1
 #define MGCMT_OPK_FIVE_DIAG 2
 #define MGCMT_OPK_NINE_CONST 3
 #define MGCMT_OPK_NINE_VAR 4
+#define MGCMT_OPK_POINT_DIAG 5
+#define MGCMT_OPK_NINE_POINT 6
 int mgcmt_level_operator_kind(const mgcmt_plan* plan, int level, int* kind);
 
 /* ---- multi-GPU: row strips with neighbour halo exchange --------------------------------------------

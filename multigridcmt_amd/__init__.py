@@ -4,11 +4,12 @@ Host side: the reference's three classes with unchanged signatures.  Device side
 kernels for gfx950 behind the C-ABI of include/mgcmt_hip.h (libmgcmt_hip.so, bound with ctypes).
 """
 from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator,
-                        potential_well_operator, recognise)
+                        potential_operator, potential_well_operator, recognise, recognise_potential)
 from .plan import Plan, get_plan, release_plans
 from .processor import MGCMTProcessor
 from .solver import MGCMTSolver
 from .stencil_maker import MGCMTStencilMaker
 
 __all__ = ["MGCMTSolver", "MGCMTStencilMaker", "MGCMTProcessor", "StructuredOperator", "UnrecognisedOperator",
-           "laplacian_operator", "identity_operator", "potential_well_operator", "recognise", "Plan", "get_plan", "release_plans"]
+           "laplacian_operator", "identity_operator", "potential_well_operator", "potential_operator", "recognise",
+           "recognise_potential", "Plan", "get_plan", "release_plans"]

@@ -69,6 +69,7 @@ COMM_OPT_OVERLAP, COMM_OPT_SPLIT, COMM_OPT_SELF_RING, COMM_OPT_EMULATE_OF = 0, 1
 SHARDED_V_HALO_VALID, SHARDED_F_HALO_VALID, SHARDED_GRAM_SCHMIDT = 1, 2, 4
 CYCLE_GRAM_SCHMIDT, CYCLE_ZERO_START = 1, 2    # cycle_flags of mgcmt_vcycle
 OPK_GENERAL, OPK_FIVE_POINT, OPK_FIVE_DIAG, OPK_NINE_CONST, OPK_NINE_VAR = 0, 1, 2, 3, 4    # mgcmt_level_operator_kind
+OPK_POINT_DIAG, OPK_NINE_POINT = 5, 6          # ... on a plan with a point diagonal (mgcmt_plan_create_pot)
 HALO_RING = 0x100
 
 _SIGNATURES = {
@@ -79,6 +80,8 @@ _SIGNATURES = {
     "mgcmt_plan_create": (c_int, [POINTER(PlanDesc), POINTER(c_void_p)]),
     "mgcmt_plan_create3d": (c_int, [POINTER(Plan3dDesc), POINTER(c_void_p)]),
     "mgcmt_plan_create3d_mass": (c_int, [POINTER(Plan3dDesc), c_int32, _dp, _dp, _dp, POINTER(c_void_p)]),
+    "mgcmt_plan_create_pot": (c_int, [POINTER(PlanDesc), _dp, POINTER(c_void_p)]),
+    "mgcmt_plan_get_point_stencil": (c_int, [c_void_p, c_int, _dp, c_int64]),
     "mgcmt_plan_destroy": (c_int, [c_void_p]),
     "mgcmt_plan_num_levels": (c_int, [c_void_p, POINTER(c_int)]),
     "mgcmt_plan_level_shape": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),

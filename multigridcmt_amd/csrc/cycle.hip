@@ -125,6 +125,7 @@ int smooth3(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, hipStre
 
 int mgcmt::smooth_impl(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, hipStream_t s) {
   if (p->dim == 3) return smooth3(p, l, kind, nu, omega, k, s);
+  MG_TRY(unsupported_point_smoother(p, kind));
   Level& L = p->levels[l];
   MG_TRY(ensure_slot(p, l, MGCMT_SLOT_V));
   MG_TRY(ensure_slot(p, l, MGCMT_SLOT_F));
@@ -343,7 +344,7 @@ bool two_level_ok(const mgcmt_plan* p, int l, int bottom, int kind, int nu, int 
   if (l + 1 >= bottom || nu < 1 || nu_up < 2 || nu_coarse != 2) return false;
   if (!fused_level(p, l, kind) || !fused_level(p, l + 1, kind)) return false;
   const Level &L0 = p->levels[l], &L1 = p->levels[l + 1], &L2 = p->levels[l + 2];
-  if (!L0.dA.k.five_point || L0.dA.k.one_d || !L1.dA.k.nine_const) return false;
+  if (!L0.dA.k.five_point || L0.dA.k.one_d || !L1.dA.k.nine_const || L0.dA.k.point || L1.dA.k.point) return false;
   for (const Level* L : {&L0, &L1, &L2})
     if (L->nr != L->gr || L->r0 != 0) return false;
   if (L1.gr * 2 != L0.gr || L1.gc * 2 != L0.gc || L2.gr * 2 != L1.gr || L2.gc * 2 != L1.gc) return false;
@@ -477,6 +478,7 @@ int ensure_coarse_factor(mgcmt_plan* p, int l, int k, hipStream_t s) {
 int tail_level(const mgcmt_plan* p, int level, int kind, int nu_coarse, int gram_schmidt) {
   const int last = (int)p->levels.size() - 1;
   if (!p->use_tail || !p->use_fused || p->dim != 2 || gram_schmidt || nu_coarse < 1) return -1;
+  if (p->has_point) return -1;  // the tail's kernels know Kronecker terms only: per-level launches down to the coarse solve
   if (kind != MGCMT_WJACOBI && kind != MGCMT_GS_MC) return -1;
   const Level& C = p->levels[last];
   if (C.nr != C.gr || (long)C.nr * C.gc > 1024) return -1;
@@ -780,6 +782,7 @@ int mgcmt_vcycle(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int 
   MG_TRY(check_k(p, k));
   if (nu1 < 0 || nu2 < 0 || nu_coarse < 0) return fail(MGCMT_ERR_INVALID, "sweep counts must be >= 0");
   if (cycle_flags & ~(MGCMT_CYCLE_GRAM_SCHMIDT | MGCMT_CYCLE_ZERO_START)) return fail(MGCMT_ERR_INVALID, "unknown cycle flag");
+  MG_TRY(unsupported_point_smoother(p, kind));
   hipStream_t s = S(stream);
   auto body = [&](hipStream_t on) { return vcycle_body(p, level, nu1, nu2, nu_coarse, kind, omega, k, cycle_flags, on); };
   if (!p->use_graph) return body(s);
@@ -803,6 +806,7 @@ int mgcmt_vcycle(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int 
 
 int mgcmt_twogrid(mgcmt_plan* p, int level, int nu1, int nu2, int kind, double omega, int k, void* stream) {
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_twogrid"));
+  MG_TRY(mgcmt::unsupported_point(p, "mgcmt_twogrid"));
   MG_TRY(check_level(p, level));
   MG_TRY(check_k(p, k));
   if (level + 1 >= (int)p->levels.size()) return fail(MGCMT_ERR_INVALID, "twogrid needs a coarser level");

@@ -80,6 +80,7 @@ struct FusedArgs {
   int n_row_chunks1;   // chunks of the first range (the rest cover the second)
   int rows_override;   // tuning: rows per chunk, 0 = automatic (host side only)
   int xcd_balanced;    // workgroup -> tile mapping: 1 = equal shares of the tile list per XCD, 0 = whole column groups per XCD
+  const double* pd;    // per-point diagonal D of the level (Op5P), in the vectors' row layout (row pitch nc), shared by all vectors
 };
 
 #ifndef MGCMT_FUSED_NT_STORE
@@ -174,6 +175,7 @@ struct Op5 {
     cw = a.cw;
   }
   static constexpr int kRowValues = 0;  // per-row operator data staged through LDS (none)
+  static constexpr int kPointValues = 0;  // per-point operator data streamed with the rows (none)
   static constexpr bool kSpecialRow = false;
   __device__ __forceinline__ double fetch_row(const FusedArgs&, long, int) const { return 0.0; }
   __device__ __forceinline__ void set_row(const FusedArgs&, int, const double*) {}
@@ -225,6 +227,7 @@ struct Op9c {
     last_row_index = (int)a.last_row;
   }
   static constexpr int kRowValues = 0;
+  static constexpr int kPointValues = 0;
   __device__ __forceinline__ double fetch_row(const FusedArgs&, long, int) const { return 0.0; }
   __device__ __forceinline__ void set_row(const FusedArgs&, int, const double*) {}
   __device__ __forceinline__ bool special_row(int row) const { return row == last_row_index; }
@@ -267,6 +270,7 @@ struct Op9 {
   static constexpr bool kBigBody = true;  // its 12-step loop bodies are too long to exist twice (checked + steady state)
   static constexpr bool kSpecialRow = false;
   static constexpr int kRowValues = 3 * M;
+  static constexpr int kPointValues = 0;
   double mu;
   double ya[M][3], yb[M][3];  // lower, diag, upper of Y_m at columns ja, ja+1
   double x[M][3];             // lower, diag, upper of X_m at the row being updated
@@ -324,6 +328,7 @@ struct Op9cv {
   static constexpr bool kBigBody = false;
   static constexpr bool kSpecialRow = true;
   static constexpr int kRowValues = 3;
+  static constexpr int kPointValues = 0;
   Op9c base;
   double ya[3], yb[3];  // lower, diag, upper of Y at columns ja, ja+1
   double x[3];          // lower, diag, upper of X at the row being updated
@@ -378,6 +383,7 @@ struct Op5V {
   static constexpr bool kBigBody = false;
   static constexpr bool kSpecialRow = false;
   static constexpr int kRowValues = MD;
+  static constexpr int kPointValues = 0;
   double d0, cn, cw;
   double qa[MD], qb[MD], p[MD];
   __device__ __forceinline__ void init(const FusedArgs& a, int q, long ja, long nc) {
@@ -406,6 +412,40 @@ struct Op5V {
     for (int m = 0; m < MD; ++m) d = fma(p[m], COL == 0 ? qa[m] : qb[m], d);
     dg = d;
     inv = fast_reciprocal(d);
+  }
+  template <int COL>
+  __device__ __forceinline__ void fix_special(const double*, double&, double&, double&) const {}
+};
+
+// constant 5-point operator plus a per-point diagonal D(i, j) (an arbitrary potential on a scaled Laplacian,
+// mgcmt_plan_create_pot): Op5's three scalars; D is a fourth stream — loaded with every row like the right-hand side,
+// carried in a delay line parallel to it and handed over (set_point) for the row a stage updates.  Same expressions as
+// the one-launch-per-operation kernels of such a level (kernels_pointwise.hip): the two give the same bits.
+struct Op5P {
+  static constexpr bool kNine = false;
+  static constexpr bool kBigBody = false;
+  static constexpr bool kSpecialRow = false;
+  static constexpr int kRowValues = 0;
+  static constexpr int kPointValues = 1;
+  double d0, cn, cw, pa, pb;
+  __device__ __forceinline__ void init(const FusedArgs& a, int q, long, long) {
+    d0 = a.c0 - a.shifts[q];
+    cn = a.cn;
+    cw = a.cw;
+    pa = pb = 0.0;
+  }
+  __device__ __forceinline__ double fetch_row(const FusedArgs&, long, int) const { return 0.0; }
+  __device__ __forceinline__ void set_row(const FusedArgs&, int, const double*) {}
+  __device__ __forceinline__ void set_point(double da, double db) {
+    pa = da;
+    pb = db;
+  }
+  __device__ __forceinline__ bool special_row(int) const { return false; }
+  template <int COL>
+  __device__ __forceinline__ void eval(const double* n, const double* c, const double* s, double& off, double& dg, double& inv) const {
+    off = fma(cn, n[1] + s[1], cw * (c[0] + c[2]));
+    dg = d0 + (COL == 0 ? pa : pb);
+    inv = fast_reciprocal(dg);
   }
   template <int COL>
   __device__ __forceinline__ void fix_special(const double*, double&, double&, double&) const {}
@@ -494,6 +534,24 @@ __device__ __forceinline__ void static_for(F&& f) {
 // (§4.1 of DESIGN.md): the four-colour 9-point passes sit at 176 - 184 registers = 2 waves per SIMD, and asked for 3
 // they come out at 168 with 12 registers spilled — 8192^2 pass 0.306 -> 0.341 ms, 4096^2 red-black cycle 0.402 ->
 // 0.474 ms.  The register counts the compiler picks on its own are right.)
+// a prefetched row; RowP: with the row's per-point operator values (policies with kPointValues > 0)
+struct RowPlain {
+  double2 v, f;
+  double e;
+  double xr;  // one of the row's operator values (policies with kRowValues > 0)
+};
+struct RowP : RowPlain {
+  double2 d;
+};
+template <bool P>
+struct RowOf {
+  using type = RowPlain;
+};
+template <>
+struct RowOf<true> {
+  using type = RowP;
+};
+
 template <class OP, int KIND, int NSWEEP, int FLAGS>
 __global__ void __launch_bounds__(64 * kWavesPerBlock) k_fused(FusedArgs a) {
   using Shape = FusedShape<OP, KIND, NSWEEP, FLAGS>;
@@ -596,11 +654,8 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) k_fused(FusedArgs a) {
 
   // NS register sets of D rows each, used in rotation: one is consumed while the others are in flight (refilled
   // in order), so every load has (NS - 1) * D rows of work between its issue and its use.
-  struct Row {
-    double2 v, f;
-    double e;
-    double xr;  // one of the row's operator values (policies with kRowValues > 0)
-  };
+  constexpr int PV = OP::kPointValues;
+  using Row = typename RowOf<(PV > 0)>::type;
   constexpr int RV = OP::kRowValues;
   constexpr int kRing = 16;  // rows of operator values kept in LDS; a stage lags at most S + E + 1 <= 10 rows
   __shared__ double s_ring[kWavesPerBlock][RV > 0 ? kRing * RV : 1];
@@ -624,6 +679,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) k_fused(FusedArgs a) {
       r.e = ec[I * cnc + jc_ld];
     }
     r.xr = RV > 0 ? op.fetch_row(a, frl, lane) : 0.0;
+    if constexpr (PV > 0) r.d = load2_stream(a.pd + fbase + ja_ld);  // (unconditional, the right-hand side's clamped address)
     ++frow;
   };
 #pragma unroll
@@ -637,6 +693,9 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) k_fused(FusedArgs a) {
   constexpr int NW = INPLACE ? 1 : S + E, NWN = INPLACE ? 1 : WN;
   double wa[NW][3], wb[NW][3], wl[NWN][3], wr[NWN][3];
   double fa[FN], fb[FN];
+  double da[PV > 0 ? FN : 1], db[PV > 0 ? FN : 1];  // the per-point operator values: a delay line parallel to fa / fb
+#pragma unroll
+  for (int s = 0; s < (PV > 0 ? FN : 1); ++s) da[s] = db[s] = 0.0;
 #pragma unroll
   for (int s = 0; s < NW; ++s)
 #pragma unroll
@@ -727,6 +786,20 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) k_fused(FusedArgs a) {
       fa[0] = in.f.x;
       fb[0] = in.f.y;
     }
+    if constexpr (PV > 0) {
+      if (FRING) {
+        da[T] = in.d.x;
+        db[T] = in.d.y;
+      } else {
+#pragma unroll
+        for (int s = FN - 1; s > 0; --s) {
+          da[s] = da[s - 1];
+          db[s] = db[s - 1];
+        }
+        da[0] = in.d.x;
+        db[0] = in.d.y;
+      }
+    }
 
     if constexpr (INPLACE) {
       // ---- colour smoothers: one rotating window, updated in place --------------------------------------------
@@ -786,6 +859,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) k_fused(FusedArgs a) {
           // wave-uniform; outside the grid (a few steps of the first and last chunks) the value stays zero
           if ((upd_a || upd_b) && (!CHK || (((okbits >> lag) & 1u) != 0 && rs >= cone0 + s))) {
             op.set_row(a, rs, ring + (rs & (kRing - 1)) * RV);
+            if constexpr (PV > 0) op.set_point(FRING ? da[modn(T - lag, B)] : da[lag], FRING ? db[modn(T - lag, B)] : db[lag]);
             if (upd_a) {
               double off, dg, inv;
               eval_a(off, dg, inv);
@@ -820,6 +894,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) k_fused(FusedArgs a) {
           double ra = 0.0, rb = 0.0;
           if (!CHK || (((okbits >> lag) & 1u) != 0 && rs >= r_begin)) {
             op.set_row(a, rs, ring + (rs & (kRing - 1)) * RV);
+            if constexpr (PV > 0) op.set_point(FRING ? da[modn(T - lag, B)] : da[lag], FRING ? db[modn(T - lag, B)] : db[lag]);
             double offa, offb, dga, dgb, inva, invb;
             eval_a(offa, dga, inva);
             eval_b(offb, dgb, invb);
@@ -899,6 +974,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) k_fused(FusedArgs a) {
           // wave-uniform; outside the grid (a few steps of the first and last chunks) the value stays zero
           if ((upd_a || upd_b) && (!CHK || (((okbits >> (s + 1)) & 1u) != 0 && rs >= cone0 + s))) {
             op.set_row(a, rs, ring + (rs & (kRing - 1)) * RV);
+            if constexpr (PV > 0) op.set_point(FRING ? da[modn(T - (s + 1), B)] : da[s + 1], FRING ? db[modn(T - (s + 1), B)] : db[s + 1]);
             if (upd_a) {
               double off, dg, inv;
               eval_a(off, dg, inv);
@@ -922,6 +998,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) k_fused(FusedArgs a) {
           double ra = 0.0, rb = 0.0;
           if (!CHK || (((okbits >> (s + 1)) & 1u) != 0 && rs >= r_begin)) {
             op.set_row(a, rs, ring + (rs & (kRing - 1)) * RV);
+            if constexpr (PV > 0) op.set_point(FRING ? da[modn(T - (s + 1), B)] : da[s + 1], FRING ? db[modn(T - (s + 1), B)] : db[s + 1]);
             double offa, offb, dga, dgb, inva, invb;
             eval_a(offa, dga, inva);
             eval_b(offb, dgb, invb);
@@ -1094,6 +1171,7 @@ void launch_fused_op9c(hipStream_t s, const fused::FusedArgs& a, int multicolour
 void launch_fused_op9(hipStream_t s, const fused::FusedArgs& a, int multicolour, int nsweep, int flags, int k);    // two terms
 void launch_fused_op9m3(hipStream_t s, const fused::FusedArgs& a, int multicolour, int nsweep, int flags, int k);  // three terms
 void launch_fused_op5v(hipStream_t s, const fused::FusedArgs& a, int multicolour, int nsweep, int flags, int k);   // 5-point + product potential
+void launch_fused_op5p(hipStream_t s, const fused::FusedArgs& a, int multicolour, int nsweep, int flags, int k);   // 5-point + per-point diagonal
 void launch_fused_op9cv(hipStream_t s, const fused::FusedArgs& a, int multicolour, int nsweep, int flags, int k);  // constant 9-point + one variable term
 
 }  // namespace mgcmt

@@ -285,7 +285,44 @@ struct PlanSpec {
   const double* m_fac[3];
   int64_t row_begin, row_end;  // a 2-D plan's rows of level 0, (0, 0) = all; ignored otherwise
   int strip_levels;
+  const double* point_diag = nullptr;  // 2-D: g x g numbers added to the diagonal of A (mgcmt_plan_create_pot), host
 };
+
+// The per-point part of A on every level (kernels_pointwise.hip): the diagonal D on level 0 in the level's padded row
+// layout (zero halo rows), below it the nine planes of R D P, R (R D P) P, ... formed on the device, one launch per level.
+// The Kronecker part's operators (upload_op) are in place; this adds the pointers to them.
+int build_point_part(mgcmt_plan* p, const double* point_diag) {
+  for (size_t l = 0; l < p->levels.size(); ++l) {
+    Level& L = p->levels[l];
+    KOp& k = L.dA.k;
+    double* q = nullptr;
+    if (l == 0) {
+      const size_t padded = (size_t)(L.nr + 2 * L.halo) * L.gc;
+      MG_HIP(hipMalloc((void**)&q, padded * sizeof(double)));
+      L.dA.owned.push_back(q);
+      MG_HIP(hipMemset(q, 0, padded * sizeof(double)));
+      MG_HIP(hipMemcpy(q + (size_t)L.halo * L.gc, point_diag, (size_t)L.nr * L.gc * sizeof(double), hipMemcpyHostToDevice));
+      k.point = 1;
+      k.pg = q + (size_t)L.halo * L.gc;
+      k.pld = L.gc;
+      k.pplane = 0;
+      continue;
+    }
+    const Level& F = p->levels[l - 1];
+    const KOp& kf = F.dA.k;
+    MG_HIP(hipMalloc((void**)&q, (size_t)9 * L.nr * L.gc * sizeof(double)));
+    L.dA.owned.push_back(q);
+    launch_point_coarsen(nullptr, F.nr, F.gc, kf.pg, kf.point == 1 ? 1 : 9, kf.pld, kf.pplane, q, L.gc, L.nr * L.gc);
+    MG_TRY(post_launch());
+    k.point = 2;
+    k.pg = q;
+    k.pld = L.gc;
+    k.pplane = L.nr * L.gc;
+  }
+  MG_HIP(hipDeviceSynchronize());
+  p->has_point = true;
+  return MGCMT_OK;
+}
 
 // the seven pieces of device scratch every plan starts with
 hipError_t alloc_scratch(mgcmt_plan* p) {
@@ -388,6 +425,13 @@ int build_plan(const PlanSpec& d, mgcmt_plan** out) {
       return rc;
     }
   }
+  if (d.point_diag) {
+    const int rc = build_point_part(p, d.point_diag);
+    if (rc != MGCMT_OK) {
+      mgcmt_plan_destroy(p);
+      return rc;
+    }
+  }
   const hipError_t e = alloc_scratch(p);
   if (e != hipSuccess) {
     mgcmt_plan_destroy(p);
@@ -409,6 +453,30 @@ int mgcmt_plan_create(const mgcmt_plan_desc* d, mgcmt_plan** out) {
   return build_plan(PlanSpec{d->dim, d->nvec, d->device, d->g, d->lowest, d->nterms, d->m_nterms, {d->xfac, d->yfac, nullptr},
                              {d->m_xfac, d->m_yfac, nullptr}, d->row_begin, d->row_end, d->strip_levels},
                     out);
+}
+
+int mgcmt_plan_create_pot(const mgcmt_plan_desc* d, const double* point_diag, mgcmt_plan** out) {
+  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!point_diag) return fail(MGCMT_ERR_INVALID, "null point diagonal");
+  if (d->dim != 2) return fail(MGCMT_ERR_INVALID, "a point diagonal needs a 2-D plan (dim = 2)");
+  if (d->m_nterms != 0) return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal takes no mass operator (the Rayleigh-quotient entries do not run on it)");
+  if (!((d->row_begin == 0 && d->row_end == 0) || (d->row_begin == 0 && d->row_end == d->g)))
+    return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal is a whole grid (no row strips)");
+  PlanSpec spec{2, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->xfac, d->yfac, nullptr}, {nullptr, nullptr, nullptr}, 0, 0, 0};
+  spec.point_diag = point_diag;
+  return build_plan(spec, out);
+}
+
+int mgcmt_plan_get_point_stencil(const mgcmt_plan* p, int l, double* out, int64_t capacity) {
+  MG_TRY(check_level(p, l));
+  if (!p->has_point) return fail(MGCMT_ERR_INVALID, "plan has no point diagonal");
+  const Level& L = p->levels[l];
+  const KOp& k = L.dA.k;
+  const int64_t plane = L.nr * L.gc, need = k.point == 1 ? plane : 9 * plane;
+  if (!out || capacity < need) return fail(MGCMT_ERR_INVALID, "point stencil buffer too small");
+  MG_HIP(hipMemcpy(out, k.pg, (size_t)need * sizeof(double), hipMemcpyDeviceToHost));  // (level 0: the interior rows are contiguous)
+  return MGCMT_OK;
 }
 
 static int create3d(const mgcmt_plan3d_desc* d, int32_t m_nterms, const double* m_zfac, const double* m_yfac, const double* m_xfac,
@@ -504,6 +572,10 @@ int mgcmt_level_operator_kind(const mgcmt_plan* p, int l, int* kind) {
   MG_TRY(check_level(p, l));
   if (!kind) return fail(MGCMT_ERR_INVALID, "null output");
   const KOp& k = p->levels[l].dA.k;
+  if (k.point) {
+    *kind = k.point == 1 ? MGCMT_OPK_POINT_DIAG : MGCMT_OPK_NINE_POINT;
+    return MGCMT_OK;
+  }
   *kind = k.five_point ? MGCMT_OPK_FIVE_POINT : k.five_diag ? MGCMT_OPK_FIVE_DIAG : k.nine_const ? MGCMT_OPK_NINE_CONST : k.nine_var ? MGCMT_OPK_NINE_VAR : MGCMT_OPK_GENERAL;
   return MGCMT_OK;
 }

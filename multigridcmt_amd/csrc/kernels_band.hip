@@ -220,6 +220,7 @@ void launch_dense_solve(hipStream_t s, long n, const double* inv, long inv_strid
 
 void launch_band_assemble(hipStream_t s, KGrid g, KOp op, const double* shifts, KBand b, int k) {
   hipLaunchKernelGGL(k_band_assemble, dim3((unsigned)((b.n + 255) / 256), (unsigned)k), dim3(256), 0, s, g, op, shifts, b);
+  if (op.point) launch_point_band_add(s, g, op, b, k);  // the per-point part on top of the Kronecker part's entries
 }
 
 void launch_band_factor(hipStream_t s, KBand b, int k) { hipLaunchKernelGGL(k_band_factor, dim3(k), dim3(kBandThreads), 0, s, b); }

@@ -14,6 +14,9 @@ constexpr long kFusedMinCols = MGCMT_FUSED_MIN_COLS;
 // chunk): a fused pass there replaces four to nine tiny launches, which is what small levels cost.
 bool fused_supported(const KGrid& g, const KOp& op) {
   if (!g.coarsen_rows) return fused1d_supported(g, op);
+  // a per-point part (mgcmt_plan_create_pot): the fine level — a constant 5-point operator plus a diagonal, Op5P — is
+  // covered; the variable 9-point levels below run the one-launch-per-operation kernels of kernels_pointwise.hip
+  if (op.point && !(op.point == 1 && op.five_point)) return false;
   return g.coarsen_rows && g.nr >= 4 && g.nc >= kFusedMinCols && (g.nc & 1) == 0 && (g.nr & 1) == 0 && (op.five_point || op.five_diag || op.nine_const || op.nine_var || op.nterms == 2 || op.nterms == 3);
 }
 
@@ -73,7 +76,10 @@ void launch_fused(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, K
   a.shifts = shifts;
   a.omega = omega;
   const int flags = (mode & 15) | (npre << fused::kPreShift);
-  if (op.five_point) {
+  if (op.point) {
+    a.pd = op.pg;  // (row pitch nc, like the vectors)
+    launch_fused_op5p(s, a, multicolour, nsweep, flags, k);
+  } else if (op.five_point) {
     launch_fused_op5(s, a, multicolour, nsweep, flags, k);
   } else if (op.five_diag) {
     for (int m = 0; m < op.ndiag; ++m) {

@@ -556,7 +556,7 @@ __global__ void __launch_bounds__(64) k_lex_wave(LexWaveArgs a) {
 }  // namespace
 
 bool lex_wave_supported(const KGrid& g, const KOp& op) {
-  return g.coarsen_rows && (op.five_point || op.nine_const) && g.nc >= 16 && g.nr >= 16 && g.nr + g.nc < (1L << 30);
+  return g.coarsen_rows && !op.point && (op.five_point || op.nine_const) && g.nc >= 16 && g.nr >= 16 && g.nr + g.nc < (1L << 30);
 }
 
 long lex_wave_blocks(const KGrid& g) { return (g.nr + g.nc - 1 + 63) / 64; }

@@ -12,49 +12,11 @@
 #include <cstdint>
 
 #include "mgcmt_internal.h"
+#include "stencil_point.h"
 
 namespace mgcmt {
 
 namespace {
-
-struct Point {
-  double off;   // sum over the 8 (or 4, or 2) neighbours of a_kj v_j
-  double diag;  // a_kk without the shift
-};
-
-// Neighbour sum and diagonal of the level operator at (i, j) of vector `v`.
-__device__ __forceinline__ Point eval_point(const KOp& op, const double* __restrict__ v, long nc, long i, long j) {
-  const double* c = v + i * nc + j;
-  const bool hw = j > 0, he = j + 1 < nc;
-  Point r;
-  if (op.five_point) {
-    const double w = hw ? c[-1] : 0.0, e = he ? c[1] : 0.0;
-    double acc = op.cw * (w + e);
-    if (op.cn != 0.0) acc += op.cn * (c[-nc] + c[nc]);
-    r.off = acc;
-    r.diag = op.c0;
-    return r;
-  }
-  const double n = c[-nc], s = c[nc];
-  const double w = hw ? c[-1] : 0.0, e = he ? c[1] : 0.0;
-  const double nw = hw ? c[-nc - 1] : 0.0, ne = he ? c[-nc + 1] : 0.0;
-  const double sw = hw ? c[nc - 1] : 0.0, se = he ? c[nc + 1] : 0.0;
-  double off = 0.0, diag = 0.0;
-  for (int m = 0; m < op.nterms; ++m) {
-    const double* X = op.X[m] + i;
-    const double* Y = op.Y[m] + j;
-    const double xl = X[0], xd = X[op.ldx], xu = X[2 * op.ldx];
-    const double yl = Y[0], yd = Y[op.ldy], yu = Y[2 * op.ldy];
-    const double rn = yl * nw + yd * n + yu * ne;
-    const double rc = yl * w + yu * e;
-    const double rs = yl * sw + yd * s + yu * se;
-    off += xl * rn + xd * rc + xu * rs;
-    diag += xd * yd;
-  }
-  r.off = off;
-  r.diag = diag;
-  return r;
-}
 
 // dst = (A - mu I) src
 __global__ void k_apply(KGrid g, KOp op, KVec src, KVec dst, const double* __restrict__ shifts) {
@@ -395,6 +357,7 @@ inline dim3 block_for(long nr) { return nr == 1 ? dim3(256, 1, 1) : dim3(64, 4, 
 }  // namespace
 
 void launch_apply(hipStream_t s, KGrid g, KOp op, KVec src, KVec dst, const double* shifts, int k) {
+  if (op.point) return launch_point_apply(s, g, op, src, dst, shifts, k);  // a per-point part on top: kernels_pointwise.hip
   const bool aligned = (((uintptr_t)src.p | (uintptr_t)dst.p) & 15) == 0 && (src.stride & 1) == 0 && (dst.stride & 1) == 0;
   if (g.coarsen_rows && g.nr >= 2 && g.nc >= 2 && (g.nc & 1) == 0 && aligned && ((op.five_point && op.cn != 0.0) || (op.five_diag && op.ndiag <= 2))) {
     const dim3 b(g.nc >= 512 ? 256 : 64, 1, 1);
@@ -420,6 +383,7 @@ void launch_apply(hipStream_t s, KGrid g, KOp op, KVec src, KVec dst, const doub
 }
 
 bool launch_ritz_pair(hipStream_t s, KGrid g, KOp op, const double* x, const double* w, double* partials, double* out) {
+  if (op.point) return false;
   const bool aligned = (((uintptr_t)x | (uintptr_t)w) & 15) == 0;
   if (!(g.coarsen_rows && g.nr >= 2 && g.nc >= 2 && (g.nc & 1) == 0 && aligned && ((op.five_point && op.cn != 0.0) || (op.five_diag && op.ndiag <= 2))))
     return false;
@@ -438,6 +402,7 @@ bool launch_ritz_pair(hipStream_t s, KGrid g, KOp op, const double* x, const dou
 }
 
 void launch_wjacobi(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k) {
+  if (op.point) return launch_point_wjacobi(s, g, op, vin, f, vout, shifts, omega, k);
   const dim3 b = block_for(g.nr);
   hipLaunchKernelGGL(k_wjacobi, grid2d(g.nc, g.nr, k, b), b, 0, s, g, op, vin, f, vout, shifts, omega);
 }
@@ -445,11 +410,13 @@ void launch_wjacobi(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout,
 void launch_mc_colour(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, const double* shifts, double omega, int ca, int cb, int k) {
   const long rows = (g.nr - ca + 1) / 2, cols = (g.nc - cb + 1) / 2;
   if (rows <= 0 || cols <= 0) return;
+  if (op.point) return launch_point_mc_colour(s, g, op, v, f, shifts, omega, ca, cb, k);
   const dim3 b = block_for(g.nr);
   hipLaunchKernelGGL(k_mc_colour, grid2d(cols, rows, k, b), b, 0, s, g, op, v, f, shifts, omega, ca, cb);
 }
 
 void launch_residual(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, KVec r, const double* shifts, int k) {
+  if (op.point) return launch_point_residual(s, g, op, v, f, r, shifts, k);
   const dim3 b = block_for(g.nr);
   hipLaunchKernelGGL(k_residual, grid2d(g.nc, g.nr, k, b), b, 0, s, g, op, v, f, r, shifts);
 }

@@ -45,6 +45,13 @@ struct KOp {
   int one_d, tri_const;
   const double* tri;
   double t_lo, t_di, t_up, t_last;
+  // point: a per-point part on top of the Kronecker terms above (mgcmt_plan_create_pot; 2-D, whole grids).  1: a diagonal
+  // D(i, j) = pg[i * pld + j] (the fine level, stored in the level's padded row layout); 2: a 9-point stencil G (the
+  // Galerkin levels R D P): the coefficient of v(i + a - 1, j + b - 1) in row (i, j) is pg[(3 a + b) * pplane + i * pld + j],
+  // zero towards points outside the grid.  The flags above describe the Kronecker part alone.
+  int point;
+  const double* pg;
+  long pld, pplane;
 };
 
 // Operator of a 3-D level (kernels_3d.hip):  A = sum_m X_m (x) Y_m (x) Z_m  over z, y, x (shift applied separately).
@@ -84,6 +91,18 @@ void launch_mc_colour(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, const doub
 void launch_residual(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, KVec r, const double* shifts, int k);
 void launch_restrict(hipStream_t s, KGrid fine, KGrid coarse, KVec r, KVec rc, int k);
 void launch_prolong(hipStream_t s, KGrid fine, KGrid coarse, KVec e, KVec v, int accumulate, int k);
+// the same four for an operator with a per-point part (op.point; kernels_pointwise.hip) — the launchers above hand over —,
+// its entries added into the assembled band matrix of the coarsest level, and the Galerkin product of the per-point part:
+// coarse <- R G P for the nine planes (fine_planes = 9) or the diagonal (fine_planes = 1) of a fnr x fnc level, with the
+// transfers of launch_restrict / launch_prolong; the coarse level always has nine planes
+void launch_point_apply(hipStream_t s, KGrid g, KOp op, KVec src, KVec dst, const double* shifts, int k);
+void launch_point_wjacobi(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
+void launch_point_mc_colour(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, const double* shifts, double omega, int ca, int cb, int k);
+void launch_point_residual(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, KVec r, const double* shifts, int k);
+struct KBand;
+void launch_point_band_add(hipStream_t s, KGrid g, KOp op, const KBand& b, int k);
+void launch_point_coarsen(hipStream_t s, long fnr, long fnc, const double* fine, int fine_planes, long fld, long fplane, double* coarse, long cld,
+                          long cplane);
 // generalised lexicographic sweep (in place):
 //   v_k <- (alpha d_k v_k + beta f_k - wU sum_{j>k} a_kj v_j - wL sum_{j<k} a_kj v_j^new) / d_k
 void launch_lex_sweep(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, const double* shifts, double alpha, double beta,

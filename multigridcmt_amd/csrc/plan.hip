@@ -32,6 +32,18 @@ int unsupported_3d_massless(const mgcmt_plan* p, const char* what) {
   return MGCMT_OK;
 }
 
+int unsupported_point(const mgcmt_plan* p, const char* what) {
+  if (p && p->has_point) return fail(MGCMT_ERR_UNSUPPORTED, std::string(what) + " is not available on a plan with a point diagonal");
+  return MGCMT_OK;
+}
+
+int unsupported_point_smoother(const mgcmt_plan* p, int kind) {
+  if (p && p->has_point && (kind == MGCMT_GS_LEX || kind == MGCMT_SOR_LEX))
+    return fail(MGCMT_ERR_UNSUPPORTED,
+                "lexicographic smoothers are not available on a plan with a point diagonal (MGCMT_WJACOBI and MGCMT_GS_MC are)");
+  return MGCMT_OK;
+}
+
 int ensure_slot(mgcmt_plan* p, int l, int slot) {
   Level& L = p->levels[l];
   if (L.base[slot]) return MGCMT_OK;
@@ -455,6 +467,7 @@ int mgcmt_time_smoother(mgcmt_plan* p, int l, int kind, int nu, double omega, in
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_time_smoother"));
   MG_TRY(check_level(p, l));
   if (!ms_out || reps < 1) return fail(MGCMT_ERR_INVALID, "bad arguments");
+  MG_TRY(unsupported_point_smoother(p, kind));
   hipEvent_t a, b;
   MG_HIP(hipEventCreate(&a));
   MG_HIP(hipEventCreate(&b));

@@ -81,6 +81,7 @@ struct mgcmt_plan {
   double* d_rqhistory = nullptr;  // Rayleigh quotients recorded by mgcmt_rq_line_step (MGCMT_RQ_HISTORY numbers)
   std::vector<double> h_shifts;
   bool has_mass = false;
+  bool has_point = false;  // A carries a per-point part (mgcmt_plan_create_pot): KOp::point on every level
   bool use_fused = true;
   bool use_tail = true;   // levels of at most 32 x 32 points as one launch (kernels_tail.hip)
   bool use_tail_dense = true;  // ... and that launch as ONE dense product with the tail's matrix (formed once per shift set)
@@ -145,6 +146,10 @@ int fail(int code, const std::string& msg);
 // 3-D form; MGCMT_OK otherwise (a null plan included: the entry's own checks report it)
 int unsupported_3d(const mgcmt_plan* p, const char* what);
 int unsupported_3d_massless(const mgcmt_plan* p, const char* what);  // ... on a 3-D plan without a mass operator
+// MGCMT_ERR_UNSUPPORTED (naming the point diagonal and `what`) on a plan with a per-point part: the entries whose kernels
+// know Kronecker terms only; ..._smoother: the same for the lexicographic smoother kinds, MGCMT_OK for the others
+int unsupported_point(const mgcmt_plan* p, const char* what);
+int unsupported_point_smoother(const mgcmt_plan* p, int kind);
 int check_level(const mgcmt_plan* p, int l);
 int check_vec(const mgcmt_plan* p, int l, int slot, int vec);
 int check_k(const mgcmt_plan* p, int k);

@@ -15,6 +15,7 @@ extern "C" {
 
 int mgcmt_ritz_pair(mgcmt_plan* p, int l, int xs, int xv, int ws, int wv, int ss, int sv, double* out5, void* stream) {
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_ritz_pair"));
+  MG_TRY(mgcmt::unsupported_point(p, "mgcmt_ritz_pair"));
   MG_TRY(check_vec(p, l, xs, xv));
   MG_TRY(check_vec(p, l, ws, wv));
   MG_TRY(check_vec(p, l, ss, sv));
@@ -51,6 +52,7 @@ int mgcmt_ritz_pair(mgcmt_plan* p, int l, int xs, int xv, int ws, int wv, int ss
 
 int mgcmt_rayleigh_residual(mgcmt_plan* p, int l, int slot, int k, double* rq_out, double* res_out, void* stream) {
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_rayleigh_residual"));
+  MG_TRY(mgcmt::unsupported_point(p, "mgcmt_rayleigh_residual"));
   MG_TRY(check_vec(p, l, slot, 0));
   MG_TRY(check_k(p, k));
   if (slot == MGCMT_SLOT_W) return fail(MGCMT_ERR_INVALID, "rayleigh_residual uses slot W as its scratch");
@@ -183,6 +185,7 @@ static int rq_result(mgcmt_plan* p, double* rho_out, hipStream_t s) {
 
 int mgcmt_rqmin(mgcmt_plan* p, int l, int slot, const int* vecs, int nu, int robust, double* rho_out, void* stream) {
   MG_TRY(mgcmt::unsupported_3d_massless(p, "mgcmt_rqmin"));
+  MG_TRY(mgcmt::unsupported_point(p, "mgcmt_rqmin"));
   MG_TRY(rqmin_check(p, l, slot, vecs, nu));
   MG_TRY(rqmin_impl(p, l, slot, vecs, nu, robust, S(stream)));
   return rq_result(p, rho_out, S(stream));
@@ -193,6 +196,7 @@ int mgcmt_rqmin(mgcmt_plan* p, int l, int slot, const int* vecs, int nu, int rob
 int mgcmt_rq_line_step(mgcmt_plan* p, int l, const int* xv, const int* wv, const int* xoutv, const int* gv, const int* tmpv, int robust, int record,
                        void* stream) {
   MG_TRY(mgcmt::unsupported_3d_massless(p, "mgcmt_rq_line_step"));
+  MG_TRY(mgcmt::unsupported_point(p, "mgcmt_rq_line_step"));
   MG_TRY(check_level(p, l));
   if (!xv || !gv) return fail(MGCMT_ERR_INVALID, "rq_line_step: x and g are required");
   if (wv && !xoutv) return fail(MGCMT_ERR_INVALID, "rq_line_step: a step needs a vector for x + delta w");
@@ -284,6 +288,7 @@ static int rqmg_body(mgcmt_plan* p, int l, int slot, const int* vecs, int nu1, i
 
 int mgcmt_vcycle_rqmg(mgcmt_plan* p, int slot, const int* vecs, int nu1, int nu2, int robust, double* rho_out, void* stream) {
   MG_TRY(mgcmt::unsupported_3d_massless(p, "mgcmt_vcycle_rqmg"));
+  MG_TRY(mgcmt::unsupported_point(p, "mgcmt_vcycle_rqmg"));
   if (!p) return fail(MGCMT_ERR_INVALID, "null plan");
   if (nu1 < 0 || nu2 < 0) return fail(MGCMT_ERR_INVALID, "step counts must be >= 0");
   for (int l = 0; l < (int)p->levels.size(); ++l) MG_TRY(rqmin_check(p, l, slot, vecs, nu1));

@@ -531,6 +531,7 @@ static int comm_common(mgcmt_plan* p, int rank, int nranks, ShardComm** out) {
 
 int mgcmt_comm_init(mgcmt_plan* p, int rank, int nranks, const void* unique_id) {
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_comm_init"));
+  MG_TRY(mgcmt::unsupported_point(p, "mgcmt_comm_init"));
   if (!unique_id) return fail(MGCMT_ERR_INVALID, "null unique id");
   RcclApi* api = rccl();
   if (!api) return fail(MGCMT_ERR_UNSUPPORTED, "RCCL is not available in this process");
@@ -550,6 +551,7 @@ int mgcmt_comm_init(mgcmt_plan* p, int rank, int nranks, const void* unique_id) 
 int mgcmt_comm_init_external(mgcmt_plan* p, int rank, int nranks, mgcmt_p2p_fn p2p, mgcmt_allgather_fn allgather,
                              mgcmt_allreduce_fn allreduce, void* user) {
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_comm_init_external"));
+  MG_TRY(mgcmt::unsupported_point(p, "mgcmt_comm_init_external"));
   if (nranks > 1 && (!p2p || !allgather)) return fail(MGCMT_ERR_INVALID, "missing transport callbacks");
   ShardComm* c = nullptr;
   MG_TRY(comm_common(p, rank, nranks, &c));
@@ -676,6 +678,8 @@ int mgcmt_allreduce_sum(mgcmt_plan* p, double* host_inout, int n, void* stream) 
 int mgcmt_sharded_vcycle(mgcmt_plan* p, mgcmt_plan* coarse, int nu1, int nu2, int nu_coarse, int kind, double omega, int k, int flags,
                          void* stream) {
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_sharded_vcycle"));
+  MG_TRY(mgcmt::unsupported_point(p, "mgcmt_sharded_vcycle"));
+  MG_TRY(mgcmt::unsupported_point(coarse, "mgcmt_sharded_vcycle"));
   MG_TRY(check_comm(p));
   if (!coarse) return fail(MGCMT_ERR_INVALID, "null coarse plan");
   if (kind != MGCMT_WJACOBI && kind != MGCMT_GS_MC)

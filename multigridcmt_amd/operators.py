@@ -43,11 +43,22 @@ class StructuredOperator:
     Behaves like the sparse matrix it stands for where the reference's callers need it: scalar
     ``*`` and ``/``, unary minus, ``.shape``, ``.diagonal()``, ``.tocsr()``/``.toarray()`` (small
     sizes), and ``A.dot(x)`` / ``A * x`` / ``A @ x`` which run the HIP apply kernel.
+
+    ``point_diagonal`` (2-D only): a (g, g) array added to the diagonal, index [i, j] = row-major point i*g + j — an
+    arbitrary potential V(x, y) on top of the Kronecker terms (``potential_operator``, ``recognise_potential``).
     """
 
-    def __init__(self, dimension, g, terms):
+    def __init__(self, dimension, g, terms, point_diagonal=None):
         self.dimension = dimension
         self.g = int(g)
+        self.point_diagonal = None
+        if point_diagonal is not None:
+            if dimension != "2d":
+                raise ValueError("point_diagonal is a property of 2-D operators")
+            pd = np.ascontiguousarray(point_diagonal, dtype=np.float64)
+            if pd.size != self.g * self.g:
+                raise ValueError("point_diagonal must hold g x g = %d x %d values, not %r" % (self.g, self.g, pd.shape))
+            self.point_diagonal = pd.reshape(self.g, self.g)
         if dimension == "3d":
             # (X, Y, Z) per term: A = sum_m X_m (x) Y_m (x) Z_m over z, y, x (idx = z g^2 + y g + x)
             self.terms = [tuple(np.ascontiguousarray(a, dtype=np.float64) for a in t) for t in terms]
@@ -69,7 +80,8 @@ class StructuredOperator:
             return StructuredOperator("1d", self.g, [(None, y * c) for _, y in self.terms])
         if self.dimension == "3d":
             return StructuredOperator("3d", self.g, [(x, y, z * c) for x, y, z in self.terms])
-        return StructuredOperator("2d", self.g, [(x, y * c) for x, y in self.terms])
+        return StructuredOperator("2d", self.g, [(x, y * c) for x, y in self.terms],
+                                  point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c)
 
     def __mul__(self, other):
         if np.isscalar(other):
@@ -101,7 +113,7 @@ class StructuredOperator:
             terms[0][1][1] -= mu
         else:
             terms.append((tri_identity(self.g), tri_identity(self.g) * (-float(mu))))
-        return StructuredOperator(self.dimension, self.g, terms)
+        return StructuredOperator(self.dimension, self.g, terms, point_diagonal=self.point_diagonal)
 
     # -- views ----------------------------------------------------------------------------------
     def diagonal(self):
@@ -109,7 +121,8 @@ class StructuredOperator:
             return sum(y[1] for _, y in self.terms)
         if self.dimension == "3d":
             return sum(np.kron(x[1], np.kron(y[1], z[1])) for x, y, z in self.terms)
-        return sum(np.outer(x[1], y[1]) for x, y in self.terms).reshape(-1)
+        d = sum(np.outer(x[1], y[1]) for x, y in self.terms)
+        return (d if self.point_diagonal is None else d + self.point_diagonal).reshape(-1)
 
     def tocsr(self):
         if self.shape[0] > (1 << 22):
@@ -119,7 +132,10 @@ class StructuredOperator:
         if self.dimension == "3d":
             return sum(sp.kron(tri_to_sparse(x), sp.kron(tri_to_sparse(y), tri_to_sparse(z), format="csr"), format="csr")
                        for x, y, z in self.terms).tocsr()
-        return sum(sp.kron(tri_to_sparse(x), tri_to_sparse(y), format="csr") for x, y in self.terms).tocsr()
+        A = sum(sp.kron(tri_to_sparse(x), tri_to_sparse(y), format="csr") for x, y in self.terms).tocsr()
+        if self.point_diagonal is not None:
+            A = (A + sp.diags(self.point_diagonal.reshape(-1), 0, format="csr")).tocsr()
+        return A
 
     def tocsc(self):
         return self.tocsr().tocsc()
@@ -149,6 +165,9 @@ class StructuredOperator:
                 for a in t:
                     if a is not None:
                         h.update(a.tobytes())
+            if self.point_diagonal is not None:
+                h.update(b"point_diagonal")
+                h.update(self.point_diagonal.tobytes())
             self._fingerprint = h.hexdigest()
         return self._fingerprint
 
@@ -235,6 +254,19 @@ def potential_well_operator(g, depth, inner, scale=-1.0 / np.pi ** 2, dimension=
     return StructuredOperator("2d", g, [(tri_identity(g), y1), (L.copy(), tri_identity(g)), (dchi * (-float(depth)), dchi.copy())])
 
 
+def potential_operator(g, V, scale=-1.0 / np.pi ** 2, dimension="2d"):
+    """H = scale * laplacian(g, "2d") + diag(V) for ANY potential: V is a (g, g) array (or g*g values, row-major), V[i, j]
+    the value at grid point i*g + j.  Matrix-free: the scaled Laplacian as two Kronecker terms, V as the operator's
+    ``point_diagonal`` — for grids that cannot be assembled.  Nothing of V has to be separable (a circular dot, a double
+    well, a rotated oscillator, disorder); a V that IS a(x) + b(y) or one square well runs faster through
+    ``potential_well_operator`` / ``recognise``, whose plans take the fused kernels on every level."""
+    if dimension != "2d":
+        raise ValueError("potential_operator: dimension must be '2d' (any tridiagonal is a 1-D operator already; 3-D has no per-point diagonal)")
+    g = int(g)
+    L = tri_laplacian(g) * float(scale)
+    return StructuredOperator("2d", g, [(tri_identity(g), L), (L.copy(), tri_identity(g))], point_diagonal=V)
+
+
 class UnrecognisedOperator(ValueError):
     pass
 
@@ -282,6 +314,58 @@ def recognise(A, dimension=None):
             return _recognise_3d(A)
         except UnrecognisedOperator:
             raise e12
+
+
+def recognise_potential(A, dimension="2d"):
+    """StructuredOperator for a sparse 2-D 5-point matrix whose off-diagonals have the Kronecker form  I (x) Y + X (x) I
+    and whose diagonal is ARBITRARY: a scaled Laplacian plus diag(V) for any potential V.  What ``recognise`` maps — a
+    diagonal a(i) + b(j) plus at most one outer product, constant 9-point stencils — is returned as ``recognise`` returns
+    it; otherwise the off-diagonals and a constant diagonal (the median entry, so that a potential that vanishes on most
+    of the grid leaves mostly zeros) become two Kronecker terms and the rest of the diagonal the operator's
+    ``point_diagonal``.  Anything that is not such a 5-point matrix raises UnrecognisedOperator.  ``recognise`` itself
+    never returns an operator with a point diagonal."""
+    if dimension != "2d":
+        raise UnrecognisedOperator("recognise_potential: dimension must be '2d'")
+    try:
+        return recognise(A, "2d")
+    except UnrecognisedOperator:
+        if isinstance(A, StructuredOperator):
+            raise
+    if not sp.issparse(A):
+        A = sp.csr_matrix(np.asarray(A, dtype=np.float64))
+    key = ("potential",) + _cache_key(A)
+    hit = _CACHE.get(key)
+    if hit is not None and hit[0] is A:
+        return hit[1]
+    n = A.shape[0]
+    g = int(round(math.sqrt(n)))
+    if A.shape[0] != A.shape[1] or g * g != n or np.iscomplexobj(A):
+        raise UnrecognisedOperator("recognise_potential: a real square matrix on a g x g grid is needed")
+    M = sp.csr_matrix(A, dtype=np.float64, copy=True)
+    M.eliminate_zeros()
+    d0 = M.diagonal(0).reshape(g, g)
+    e, w, s, nn = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
+    e[:-1], w[1:] = M.diagonal(1), M.diagonal(-1)
+    if g < n:
+        s[:-g], nn[g:] = M.diagonal(g), M.diagonal(-g)
+    counted = sum(np.count_nonzero(a) for a in (d0, e, w, s, nn))
+    e, w, s, nn = e.reshape(g, g), w.reshape(g, g), s.reshape(g, g), nn.reshape(g, g)
+    ok = counted == M.nnz and not e[:, -1].any() and not w[:, 0].any()
+    ok = ok and np.array_equal(e, np.broadcast_to(e[0], (g, g))) and np.array_equal(w, np.broadcast_to(w[0], (g, g)))
+    ok = ok and np.array_equal(s, np.broadcast_to(s[:, :1], (g, g))) and np.array_equal(nn, np.broadcast_to(nn[:, :1], (g, g)))
+    if not ok:
+        raise UnrecognisedOperator(
+            "2-D operator is not a 5-point matrix  I (x) Y + X (x) I + diag(V): its off-diagonals do not have the Kronecker "
+            "form (an arbitrary potential may sit on the diagonal only)")
+    base = float(np.median(d0))
+    Y, X = np.zeros((3, g)), np.zeros((3, g))
+    Y[0], Y[1], Y[2] = w[0], 0.5 * base, e[0]
+    X[0], X[1], X[2] = nn[:, 0], base - 0.5 * base, s[:, 0]
+    op = StructuredOperator("2d", g, [(tri_identity(g), Y), (X, tri_identity(g))], point_diagonal=d0 - base)
+    if len(_CACHE) > 64:
+        _CACHE.clear()
+    _CACHE[key] = (A, op)
+    return op
 
 
 def _recognise_3d(A):

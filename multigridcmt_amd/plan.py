@@ -44,7 +44,20 @@ class Plan:
             keep += [mx, my]
         desc.nvec, desc.device = self.nvec, device
         desc.row_begin, desc.row_end, desc.strip_levels = row_begin, row_end, strip_levels
-        check(_lib.lib().mgcmt_plan_create(ctypes.byref(desc), ctypes.byref(self._h)))
+        pd = getattr(op, "point_diagonal", None)
+        if pd is not None:
+            # an arbitrary potential on the diagonal (operators.potential_operator): the per-point hierarchy R D P is built
+            # at creation; such plans are whole 2-D grids without a mass operator
+            if mass is not None:
+                raise ValueError("an operator with a point diagonal takes no mass operator: the Rayleigh-quotient routines (rqmin, "
+                                 "vcycle_rqmg, ...) do not run on it; vcycle / vcycle_matrix / fmg, the smoothers wjacobi and "
+                                 "gseidel_rb, apply and drivers.block_eigensolve do")
+            if row_begin or row_end or strip_levels:
+                raise ValueError("an operator with a point diagonal is not sharded")
+            pd = _f64(pd)
+            check(_lib.lib().mgcmt_plan_create_pot(ctypes.byref(desc), as_dp(pd), ctypes.byref(self._h)))
+        else:
+            check(_lib.lib().mgcmt_plan_create(ctypes.byref(desc), ctypes.byref(self._h)))
         del keep
         n = c_int(0)
         check(_lib.lib().mgcmt_plan_num_levels(self._h, ctypes.byref(n)))
@@ -106,6 +119,15 @@ class Plan:
         n = (self.g >> level) if (which == 1 or self.dim >= 2) else 1
         out = np.zeros((nterms, 3, n))
         check(_lib.lib().mgcmt_plan_get_factors(self._h, op, level, which, as_dp(out), out.size))
+        return out
+
+    def point_stencil(self, level):
+        """Host copy of the per-point part of `level` of a plan whose operator has a point diagonal: level 0 the diagonal,
+        array [rows, cols]; below it the 9-point stencil R D P, array [3, 3, rows, cols] — entry [a, b, i, j] is the
+        coefficient of point (i + a - 1, j + b - 1) in row (i, j)."""
+        r, c, _ = self.shapes[level]
+        out = np.zeros((r, c) if level == 0 else (3, 3, r, c))
+        check(_lib.lib().mgcmt_plan_get_point_stencil(self._h, level, as_dp(out), out.size))
         return out
 
     def level_halo(self, level):

@@ -15,7 +15,8 @@ import scipy.sparse as sp
 
 from . import _lib
 from ._lib import GS_LEX, GS_MC, OP_A, OP_M, SLOT_F, SLOT_T, SLOT_V, SLOT_W, SOR_LEX, WJACOBI
-from .operators import StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, recognise, tag_structured
+from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, recognise, recognise_potential,
+                        tag_structured)
 from .plan import get_plan
 from .processor import MGCMTProcessor
 from .stencil_maker import MGCMTStencilMaker
@@ -57,6 +58,30 @@ def _check_3d_smoother(kind):
                          "wjacobi, gseidel_rb (multicolour) and foreign smoother callables")
 
 
+def _recognise_2d_entry(A, dimension):
+    """``recognise`` for the 2-D entry points: a 5-point matrix with an arbitrary diagonal (a Hamiltonian with any
+    potential), which ``recognise`` refuses, is mapped by ``recognise_potential`` to an operator with a point diagonal;
+    what that refuses too raises ``recognise``'s error."""
+    try:
+        return recognise(A, dimension)
+    except UnrecognisedOperator as err:
+        if dimension != "2d" or isinstance(A, StructuredOperator):
+            raise
+        try:
+            return recognise_potential(A, "2d")
+        except UnrecognisedOperator:
+            raise err
+
+
+def _check_point_smoother(op, kind):
+    """An operator with a point diagonal has weighted Jacobi and multicolour Gauss-Seidel; a lexicographic smoother raises
+    instead of being replaced by another one."""
+    if getattr(op, "point_diagonal", None) is not None and kind in (GS_LEX, SOR_LEX):
+        raise ValueError("gseidel / sor (lexicographic) are not available for an operator with a point diagonal (an arbitrary "
+                         "potential V(x, y)); the supported smoothers are wjacobi, gseidel_rb (multicolour) and foreign "
+                         "smoother callables")
+
+
 class MGCMTSolver:
     """
     Same constructor as the reference (MGCMTSolver.py:13-15): owns a stencil maker and a processor.
@@ -74,11 +99,12 @@ class MGCMTSolver:
         if dimension == "3d":
             _check_3d_smoother(kind)
         try:
-            op = recognise(A, dimension)
+            op = _recognise_2d_entry(A, dimension)
         except UnrecognisedOperator:
             if dimension in ("2d", "3d"):
                 raise
             return self._smooth_general(v0, f, A, kind, nu, omega)
+        _check_point_smoother(op, kind)
         if op.dimension == "3d" and dimension is None and kind != WJACOBI:
             # a matrix recognised as 3-D only because no dimension was named: the lexicographic and multicolour orders
             # of the general path are what such calls ran before 3-D grids existed
@@ -212,6 +238,29 @@ class MGCMTSolver:
         xf = plan.factors(level, 0) if plan.dim == 2 else None
         yf = plan.factors(level, 1)
         terms = [((xf[m].copy() if xf is not None else None), yf[m].copy()) for m in range(yf.shape[0])]
+        if getattr(plan.op, "point_diagonal", None) is not None:
+            # the Kronecker part's level plus the per-point part the library formed: the diagonal on level 0, the 9-point
+            # stencil R D P below (a foreign smoother sees the true R A P - mu I)
+            gl = plan.g >> level
+            if level == 0:
+                op = StructuredOperator("2d", gl, terms, point_diagonal=plan.point_stencil(0))
+                if shift:
+                    op = op.shifted(float(shift))
+                return tag_structured(op.tocsr(), op)
+            G = plan.point_stencil(level)
+            i, j = np.meshgrid(np.arange(gl), np.arange(gl), indexing="ij")
+            rows, cols, vals = [], [], []
+            for a in range(3):
+                for b in range(3):
+                    ok = (i + a - 1 >= 0) & (i + a - 1 < gl) & (j + b - 1 >= 0) & (j + b - 1 < gl)
+                    rows.append((i * gl + j)[ok])
+                    cols.append(((i + a - 1) * gl + (j + b - 1))[ok])
+                    vals.append(G[a, b][ok])
+            P = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(gl * gl, gl * gl))
+            M = StructuredOperator("2d", gl, terms).tocsr() + P
+            if shift:
+                M = M - float(shift) * sp.identity(gl * gl, format="csr")
+            return M.tocsr()
         op = StructuredOperator("2d" if plan.dim == 2 else "1d", plan.g >> level, terms)
         if shift:
             op = op.shifted(float(shift))
@@ -302,11 +351,12 @@ class MGCMTSolver:
             return None
         g = int(g)
         try:
-            op = recognise(A, dimension)
+            op = _recognise_2d_entry(A, dimension)
         except UnrecognisedOperator:
             if dimension != "1d":
                 raise
             return self._vcycle_general(v0, f, A, kind, omega, int(nu1), int(nu2), int(nu_coarse), shift, int(lowest_level))
+        _check_point_smoother(op, kind)
         plan = get_plan(op, int(lowest_level), nvec=1)
         plan.set_shifts([float(shift)])
         v0 = np.asarray(v0, dtype=np.float64).reshape(-1)
@@ -342,7 +392,8 @@ class MGCMTSolver:
         g = self._grid(n, dimension)
         if not self._check_grid(g, lowest_level):
             return None
-        op = recognise(A, dimension)
+        op = _recognise_2d_entry(A, dimension)
+        _check_point_smoother(op, kind)
         plan = get_plan(op, int(lowest_level), nvec=1)
         plan.set_shifts([float(shift)])
         V, F = (SLOT_V, 0), (SLOT_F, 0)
@@ -372,7 +423,10 @@ class MGCMTSolver:
         g = int(g)
         if g < 4:
             raise ValueError("twogrid needs a fine grid of at least 4 points per direction")
-        op = recognise(A, dimension)
+        op = _recognise_2d_entry(A, dimension)
+        if getattr(op, "point_diagonal", None) is not None:
+            raise ValueError("twogrid is not available for an operator with a point diagonal; vcycle (with lowest_level = g / 2: "
+                             "the same two-grid cycle), vcycle_matrix and fmg are, with the smoothers wjacobi and gseidel_rb")
         plan = get_plan(op, g // 2, nvec=1)
         plan.set_shifts([float(shift)])
         plan.upload(0, SLOT_V, 0, np.asarray(v0, dtype=np.float64).reshape(-1))
@@ -405,7 +459,8 @@ class MGCMTSolver:
         if not self._check_grid(g, lowest_level):
             return None
         self._check_stencil_maker(stencil_maker, dimension)
-        op = recognise(A, dimension)
+        op = _recognise_2d_entry(A, dimension)
+        _check_point_smoother(op, kind)
         plan = get_plan(op, int(lowest_level), nvec=k)
         plan.set_shifts(shifts)
         zero_start = _all_zero(v0_matrix)         # the reference's callers pass zeros (1DPotMatrixVcycle.py:70): nothing to upload

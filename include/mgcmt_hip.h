@@ -71,7 +71,18 @@ typedef enum mgcmt_smoother {
                           (0,1),(1,0),(0,0),(1,1) = red-black on a 5-point operator                 */
 } mgcmt_smoother;
 
-/* vector slots of a level */
+/* vector slots of a level.
+ * What an entry writes (checked call by call in tests/test_memory_contract.py): the vectors its comment names as results,
+ * for the columns q < k it is given, and the scratch named here — nothing else.  Columns q >= k, the halo rows above and
+ * below every vector (exact zeros on a whole-grid plan, always) and the padding between columns are never written.
+ * Scratch: slot T of a level belongs to mgcmt_smooth, mgcmt_fused_pass, mgcmt_vcycle and mgcmt_twogrid on the levels they
+ * run on (columns q < k; they write the new iterate there and exchange the roles of V and T, so the address behind
+ * mgcmt_vec_ptr changes and T holds an older iterate afterwards) and to mgcmt_residual_restrict (the fine residual);
+ * slot W belongs to mgcmt_rayleigh_residual (columns q < k) and to no other entry; mgcmt_ritz_pair may write the scratch
+ * vector it is given.
+ * Left bit for bit: slot F of the level a cycle or mgcmt_twogrid starts on (the coarser levels' F and V are its
+ * workspace); slot W in every entry but mgcmt_rayleigh_residual, unless the caller names a vector of W as a result; every
+ * vector that an entry takes as an input only (mgcmt_apply, mgcmt_gram, mgcmt_block_gram, mgcmt_lincomb, ...). */
 typedef enum mgcmt_slot { MGCMT_SLOT_V = 0, MGCMT_SLOT_F = 1, MGCMT_SLOT_T = 2, MGCMT_SLOT_W = 3 } mgcmt_slot;
 
 /* which operator of the plan: A, or the mass operator M of rqmin (MGCMTSolver.py:17-57) */
@@ -179,9 +190,9 @@ int mgcmt_sync(void* stream);
 int mgcmt_host_alloc(int64_t bytes, void** host_ptr);
 int mgcmt_host_free(void* host_ptr);
 
-/* smoothers on V,F of `level` for vectors 0..k-1 (MGCMTSolver.py:182-246) */
+/* smoothers on V,F of `level` for vectors 0..k-1 (MGCMTSolver.py:182-246); slot T of the level is scratch */
 int mgcmt_smooth(mgcmt_plan* plan, int level, int kind, int nu, double omega, int k, void* stream);
-/* F[level+1] <- R (F - (A - mu I) V), V[level+1] <- 0   (MGCMTSolver.py:315-316) */
+/* F[level+1] <- R (F - (A - mu I) V), V[level+1] <- 0   (MGCMTSolver.py:315-316); T[level] is scratch (the residual) */
 int mgcmt_residual_restrict(mgcmt_plan* plan, int level, int k, void* stream);
 /* V[level] <- V[level] + P V[level+1]                    (MGCMTSolver.py:323-324) */
 int mgcmt_prolong_correct(mgcmt_plan* plan, int level, int k, void* stream);
@@ -197,10 +208,11 @@ int mgcmt_coarse_solve(mgcmt_plan* plan, int level, int k, void* stream);
 #define MGCMT_CYCLE_ZERO_START 2
 /* State after a cycle: V[level] holds the new iterate and F[l] of every coarser fused level the restricted residual;
  * the iterates V[l] of the coarser levels are scratch (a level run inside a two-level pass, MGCMT_OPT_TWO_LEVEL, is
- * never written).  A caller that wants a coarse iterate sets MGCMT_OPT_TWO_LEVEL to 0. */
+ * never written).  A caller that wants a coarse iterate sets MGCMT_OPT_TWO_LEVEL to 0.  Slots V, F and T of the coarser
+ * levels and slot T of `level` are the cycle's scratch (columns q < k); F[level] and every slot W are not touched. */
 int mgcmt_vcycle(mgcmt_plan* plan, int level, int nu1, int nu2, int nu_coarse, int kind, double omega, int k,
                  int cycle_flags, void* stream);
-/* twogrid (:331-371): exact solve of (R A P - mu I) on level+1 */
+/* twogrid (:331-371): exact solve of (R A P - mu I) on level+1; scratch: T[level] and V, F, T of level+1 */
 int mgcmt_twogrid(mgcmt_plan* plan, int level, int nu1, int nu2, int kind, double omega, int k, void* stream);
 
 /* dst <- (Op - with_shift*mu I) src        (sparse `*` / .dot, e.g. MGCMTSolver.py:19,315) */

@@ -9,6 +9,7 @@
 // Model: one workgroup at a time; its threads are fibers on one OS thread.  A fiber runs until it
 // reaches __syncthreads() / a wave shuffle (or returns); when every live fiber of the workgroup has
 // stopped there, all resume.  Waves are 64 consecutive threads, as on gfx950.
+// Guard mode (hipmock_guard_enable, off by default): hipMalloc blocks between red zones with a NaN-filled payload; see below.
 #pragma once
 
 #include <chrono>
@@ -114,6 +115,27 @@ inline void hipLaunchKernelGGL(void (*kernel)(KArgs...), dim3 grid, dim3 block, 
 inline void __threadfence() {}
 inline unsigned atomicAdd(unsigned* p, unsigned x) { const unsigned old = *p; *p = old + x; return old; }  // one fiber runs at a time
 
+// Guard mode of the allocator (hipmock_runtime.cpp), switched at run time by the tests through ctypes.  While it is on a
+// block gets a red zone on each side and a payload of 0xFF bytes; red-zone damage (found by hipFree and by
+// hipmock_guard_check_all), a host-initiated copy / memset whose device range leaves its payload, and a hipFree of what is
+// no live block are recorded — nothing aborts — and handed out, and cleared, by hipmock_guard_take.
+enum { HIPMOCK_VIOLATION_RED_ZONE = 1, HIPMOCK_VIOLATION_RANGE = 2, HIPMOCK_VIOLATION_BAD_FREE = 3 };
+struct hipmock_violation {
+  int kind;                  // HIPMOCK_VIOLATION_*
+  int side;                  // 0: below the payload, 1: above it, -1: no block involved
+  unsigned long long bytes;  // payload size of the block (0: none)
+  long long offset;          // of the first bad byte (red zone) / of the range's start, from the payload's start
+  unsigned long long seq;    // the block's allocation sequence number (hipMalloc calls count from 1)
+  unsigned long long length; // bytes of the refused range (RANGE), 1 otherwise
+};
+extern "C" {
+void hipmock_guard_enable(int on);
+int hipmock_guard_enabled();
+int hipmock_guard_red_zone_bytes();
+int hipmock_guard_live_blocks();                                 // guarded blocks not yet freed
+int hipmock_guard_check_all();                                   // walks every live guarded block; returns the records pending
+int hipmock_guard_take(hipmock_violation* out, int capacity);    // copies up to `capacity` records, clears all, returns how many there were
+}
 hipError_t hipMalloc(void** p, size_t bytes);
 hipError_t hipFree(void* p);
 hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind);

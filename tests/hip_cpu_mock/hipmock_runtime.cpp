@@ -3,6 +3,10 @@
 
 #include <sys/mman.h>
 
+#include <atomic>
+#include <map>
+#include <mutex>
+
 namespace hipmock {
 
 uint3_t g_threadIdx, g_blockIdx;
@@ -119,24 +123,183 @@ void run_grid(dim3 grid, dim3 block, const std::function<void()>& body) {
 
 }  // namespace hipmock
 
-hipError_t hipMalloc(void** p, size_t bytes) {
-  *p = malloc(bytes ? bytes : 1);
-  return *p ? hipSuccess : hipErrorOutOfMemory;
+// ---- guard mode (tests/test_memory_contract.py) ---------------------------------------------------------------------
+// Off (the default): hipMalloc is malloc, as ever.  On (hipmock_guard_enable(1), at run time, through ctypes): every new
+// block lies between two red zones of kRedZoneBytes holding kRedZoneByte, its payload starts as kPayloadByte (0xFF: a NaN
+// as a double, -1 as an integer: what a kernel reads that relies on fresh device memory being anything in particular),
+// and hipFree, hipmock_guard_check_all and the host-initiated copies / memsets record what they find, never abort.
+// Every live block is in g_blocks with its kind, so a block of either kind is freed the way it was allocated whatever
+// the mode is by then.
+namespace {
+
+constexpr size_t kRedZoneBytes = 64 * 1024;  // >= two rows of the widest 2-D level of the tests (256 doubles = 2 KiB a row)
+constexpr unsigned char kRedZoneByte = 0xA5;
+constexpr unsigned char kPayloadByte = 0xFF;  // fresh and freed payloads
+
+struct Block {
+  size_t bytes;
+  bool guarded;
+  unsigned long long seq;
+};
+
+std::mutex g_guard_mu;
+std::map<char*, Block> g_blocks;  // payload start -> block, both kinds
+std::atomic<bool> g_guard{false};  // (read by range_ok and hipmock_guard_enabled without the mutex)
+unsigned long long g_alloc_seq = 0;
+std::vector<hipmock_violation> g_violations;
+
+void record(int kind, int side, const Block* b, long long offset, size_t length) {
+  g_violations.push_back(hipmock_violation{kind, side, b ? (unsigned long long)b->bytes : 0ULL, offset, b ? b->seq : 0ULL, (unsigned long long)length});
 }
-hipError_t hipFree(void* p) {
-  free(p);
+
+// both red zones of a guarded block: the first bad byte of each side is recorded and the zone repaired (one record per damage)
+void check_zones(char* payload, const Block& b) {
+  char* zone[2] = {payload - kRedZoneBytes, payload + b.bytes};
+  for (int side = 0; side < 2; ++side)
+    for (size_t i = 0; i < kRedZoneBytes; ++i)
+      if ((unsigned char)zone[side][i] != kRedZoneByte) {
+        record(HIPMOCK_VIOLATION_RED_ZONE, side, &b, (long long)(zone[side] + i - payload), 1);
+        memset(zone[side], kRedZoneByte, kRedZoneBytes);
+        break;
+      }
+}
+
+// the live block whose payload or red zones hold p (null: none); start: its payload.  Caller holds g_guard_mu.
+const Block* block_near(const char* p, const char** start) {
+  auto above = g_blocks.upper_bound(const_cast<char*>(p));  // first payload that starts beyond p
+  if (above != g_blocks.begin()) {
+    auto below = std::prev(above);
+    if (p < below->first + below->second.bytes + (below->second.guarded ? kRedZoneBytes : 0)) {
+      *start = below->first;
+      return &below->second;
+    }
+  }
+  if (above != g_blocks.end() && above->second.guarded && p >= above->first - kRedZoneBytes) {
+    *start = above->first;
+    return &above->second;
+  }
+  return nullptr;
+}
+
+// a device-side range of a host-initiated copy or memset lies inside one live payload.  known_device = false (a side of
+// hipMemcpyDefault, which names none): the side is a device side if it points into a live block or its red zones.
+bool range_ok(const void* ptr, size_t bytes, bool known_device = true) {
+  if (!g_guard.load()) return true;
+  std::lock_guard<std::mutex> lock(g_guard_mu);
+  const char* p = (const char*)ptr;
+  const char* start = nullptr;
+  const Block* near = block_near(p, &start);
+  if (!near && !known_device) return true;  // host memory
+  if (near && p >= start && p + bytes <= start + near->bytes) return true;
+  record(HIPMOCK_VIOLATION_RANGE, near ? (p < start ? 0 : 1) : -1, near, near ? (long long)(p - start) : 0, bytes);
+  return false;
+}
+
+// a side of a copy: checked as device memory (1), resolved by looking the pointer up (hipMemcpyDefault: 0), host (-1)
+int device_side(hipMemcpyKind k, bool dst) {
+  if (k == hipMemcpyHostToHost) return -1;
+  if (k == hipMemcpyHostToDevice) return dst ? 1 : -1;
+  if (k == hipMemcpyDeviceToHost) return dst ? -1 : 1;
+  return k == hipMemcpyDeviceToDevice ? 1 : 0;
+}
+
+bool side_ok(hipMemcpyKind k, bool dst, const void* p, size_t bytes) {
+  const int side = device_side(k, dst);
+  return side < 0 || range_ok(p, bytes, side == 1);
+}
+
+}  // namespace
+
+extern "C" {
+void hipmock_guard_enable(int on) {
+  g_guard.store(on != 0);
+}
+int hipmock_guard_enabled() { return g_guard.load() ? 1 : 0; }
+int hipmock_guard_red_zone_bytes() { return (int)kRedZoneBytes; }
+int hipmock_guard_live_blocks() {
+  std::lock_guard<std::mutex> lock(g_guard_mu);
+  int n = 0;
+  for (auto& b : g_blocks) n += b.second.guarded ? 1 : 0;
+  return n;
+}
+int hipmock_guard_check_all() {
+  std::lock_guard<std::mutex> lock(g_guard_mu);
+  for (auto& b : g_blocks)
+    if (b.second.guarded) check_zones(b.first, b.second);
+  return (int)g_violations.size();
+}
+int hipmock_guard_take(hipmock_violation* out, int capacity) {
+  std::lock_guard<std::mutex> lock(g_guard_mu);
+  const int total = (int)g_violations.size();
+  for (int i = 0; i < total && i < capacity; ++i) out[i] = g_violations[i];
+  g_violations.clear();
+  return total;
+}
+}
+
+hipError_t hipMalloc(void** p, size_t bytes) {
+  if (bytes == 0) bytes = 1;
+  std::lock_guard<std::mutex> lock(g_guard_mu);
+  char* payload = nullptr;
+  const bool guarded = g_guard.load();
+  if (guarded) {
+    char* raw = (char*)malloc(bytes + 2 * kRedZoneBytes);
+    if (raw) {
+      payload = raw + kRedZoneBytes;
+      memset(raw, kRedZoneByte, kRedZoneBytes);
+      memset(payload, kPayloadByte, bytes);
+      memset(payload + bytes, kRedZoneByte, kRedZoneBytes);
+    }
+  } else {
+    payload = (char*)malloc(bytes);
+  }
+  *p = payload;
+  if (!payload) return hipErrorOutOfMemory;
+  g_blocks[payload] = Block{bytes, guarded, ++g_alloc_seq};
   return hipSuccess;
 }
-hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) {
+hipError_t hipFree(void* p) {
+  if (!p) return hipSuccess;
+  std::lock_guard<std::mutex> lock(g_guard_mu);
+  auto it = g_blocks.find((char*)p);
+  if (it == g_blocks.end()) {  // not a live block: freed already, an interior pointer, or never ours
+    if (!g_guard.load()) {
+      free(p);  // (mode off: free() as ever)
+      return hipSuccess;
+    }
+    record(HIPMOCK_VIOLATION_BAD_FREE, -1, nullptr, 0, 1);
+    return hipErrorInvalidValue;
+  }
+  const Block b = it->second;
+  g_blocks.erase(it);
+  if (!b.guarded) {
+    free(p);
+    return hipSuccess;
+  }
+  check_zones((char*)p, b);
+  memset(p, kPayloadByte, b.bytes);  // a use after free reads NaN
+  free((char*)p - kRedZoneBytes);
+  return hipSuccess;
+}
+hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind k) {
+  if (bytes && (!side_ok(k, true, dst, bytes) || !side_ok(k, false, src, bytes))) return hipErrorInvalidValue;
   memmove(dst, src, bytes);
   return hipSuccess;
 }
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind k, hipStream_t) { return hipMemcpy(dst, src, bytes, k); }
 hipError_t hipMemset(void* dst, int value, size_t bytes) {
+  if (bytes && !range_ok(dst, bytes)) return hipErrorInvalidValue;
   memset(dst, value, bytes);
   return hipSuccess;
 }
 hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t) { return hipMemset(dst, value, bytes); }
+// the allocator for a ctypes caller (the C++ names above are mangled): the guard's own test plants its errors through these
+extern "C" {
+int hipmock_malloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+int hipmock_free(void* p) { return hipFree(p); }
+int hipmock_memset(void* dst, int value, size_t bytes) { return hipMemset(dst, value, bytes); }
+int hipmock_memcpy(void* dst, const void* src, size_t bytes, int kind) { return hipMemcpy(dst, src, bytes, (hipMemcpyKind)kind); }
+}
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetDevice(int* d) {
   *d = 0;

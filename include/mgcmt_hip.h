@@ -39,6 +39,7 @@
  *     levels then minimise with R I P, as the reference does).  The entries with no 3-D form (lexicographic smoothers,
  *     twogrid, ritz_pair, rayleigh_residual, sharding, fused-pass and timing entries) return MGCMT_ERR_UNSUPPORTED on
  *     a 3-D plan.
+ *     A 3-D operator may carry an arbitrary diagonal on top of its Kronecker terms (mgcmt_plan_create3d_pot).
  */
 #ifndef MGCMT_HIP_H
 #define MGCMT_HIP_H
@@ -156,6 +157,27 @@ int mgcmt_plan_create_pot(const mgcmt_plan_desc* desc, const double* point_diag,
 /* host copy of the per-point part of `level` of such a plan: level 0 rows x cols numbers (point_diag); a level below nine
  * planes of rows x cols, plane 3 a + b = the coefficient of v(i + a - 1, j + b - 1) in row (i, j), zero towards points
  * outside the grid.  The level's matrix is the one assembled from mgcmt_plan_get_factors plus these. */
+/* A 3-D plan whose operator carries an arbitrary diagonal on top of its Kronecker terms:
+ *     A = sum_m X_m (x) Y_m (x) Z_m + diag(point_diag)  - shift * I,
+ * point_diag = g^3 numbers on the host, index [z * g^2 + y * g + x]: H = -c Laplacian + V(x, y, z) with any potential V (a
+ * spherical well, a lens, coupled dots, disorder).  desc as for mgcmt_plan_create3d; there is no mass operator, so the
+ * Rayleigh-quotient entries keep returning their "no mass operator" refusal on such a plan.  The Galerkin levels are the
+ * Kronecker part's usual levels plus a 27-point stencil with per-point coefficients, R diag(point_diag) P, formed on the
+ * device at creation.  Storage: the diagonal is one level-0 vector (8 B per point); every level below holds 27 planes, summed
+ * over the levels 27/7 (about 3.9) fine vectors — about 4 GiB at 512^3.  Such a plan runs what any 3-D plan runs
+ * (mgcmt_vcycle with HIP-graph replay, Gram-Schmidt, per-column shifts and MGCMT_CYCLE_ZERO_START; mgcmt_smooth with
+ * MGCMT_WJACOBI and MGCMT_GS_MC; mgcmt_apply, the transfers, the coarse solve, the vector algebra): a fine level whose
+ * Kronecker part is a constant 7-point operator on marching kernels with the diagonal as a fourth stream (grid sizes that
+ * are multiples of 64; the environment variable MGCMT_3D_POINT_MARCH=0, read at creation, selects the flat kernels, which
+ * give the same bits per sweep), the levels below as one launch per operation (csrc/kernels_3d_point.hip).
+ * mgcmt_plan_get_point_stencil on such a plan: level 0 g^3 numbers; a level below 27 planes of g_l^3, plane 9 a + 3 b + c = the
+ * coefficient of v(z + a - 1, y + b - 1, x + c - 1) in row (z, y, x), exactly zero towards points outside the grid. */
+int mgcmt_plan_create3d_pot(const mgcmt_plan3d_desc* desc, const double* point_diag, mgcmt_plan** out);
+/* Which kernels `level` of a 3-D plan runs on.  kind: 0 general Kronecker terms, 1 constant 7-point, 2 constant 7-point plus a
+ * point diagonal, 3 Kronecker terms plus 27 planes, 4 general Kronecker terms plus a point diagonal (a fine level whose
+ * factors are not Toeplitz: flat kernels); marching: whether the level's smoothing and transfer passes take the
+ * marching kernels (1) or the flat ones (0).  Either output may be NULL.  (mgcmt_level_operator_kind describes 1-D / 2-D plans.) */
+int mgcmt_plan3d_level_path(const mgcmt_plan* plan, int level, int* kind, int* marching);
 int mgcmt_plan_get_point_stencil(const mgcmt_plan* plan, int level, double* out, int64_t capacity);
 int mgcmt_plan_num_levels(const mgcmt_plan* plan, int* levels);
 int mgcmt_plan_level_shape(const mgcmt_plan* plan, int level, int64_t* rows, int64_t* cols, int64_t* row_begin);

@@ -285,7 +285,7 @@ struct PlanSpec {
   const double* m_fac[3];
   int64_t row_begin, row_end;  // a 2-D plan's rows of level 0, (0, 0) = all; ignored otherwise
   int strip_levels;
-  const double* point_diag = nullptr;  // 2-D: g x g numbers added to the diagonal of A (mgcmt_plan_create_pot), host
+  const double* point_diag = nullptr;  // g x g (2-D, mgcmt_plan_create_pot) or g^3 (3-D, mgcmt_plan_create3d_pot) numbers added to the diagonal of A, host
 };
 
 // The per-point part of A on every level (kernels_pointwise.hip): the diagonal D on level 0 in the level's padded row
@@ -318,6 +318,37 @@ int build_point_part(mgcmt_plan* p, const double* point_diag) {
     k.pg = q;
     k.pld = L.gc;
     k.pplane = L.nr * L.gc;
+  }
+  MG_HIP(hipDeviceSynchronize());
+  p->has_point = true;
+  return MGCMT_OK;
+}
+
+// The same on a 3-D plan (kernels_3d_point.hip): D as g^3 numbers at the index of the right-hand side (no halo planes: the
+// kernels predicate all three directions), below it the 27 planes of R D P, R (R D P) P, ...
+int build_point_part3(mgcmt_plan* p, const double* point_diag) {
+  const char* e = getenv("MGCMT_3D_POINT_MARCH");  // "0": the fine level on the flat kernels (A/B tests)
+  const int march = !(e && e[0] == '0');
+  for (size_t l = 0; l < p->levels.size(); ++l) {
+    Level& L = p->levels[l];
+    K3Op& k = L.dA.k3;
+    const size_t N = (size_t)L.nr * L.gc;
+    double* q = nullptr;
+    MG_HIP(hipMalloc((void**)&q, (l == 0 ? 1 : 27) * N * sizeof(double)));
+    L.dA.owned.push_back(q);
+    k.pg = q;
+    k.pmarch = march;
+    if (l == 0) {
+      MG_HIP(hipMemcpy(q, point_diag, N * sizeof(double), hipMemcpyHostToDevice));
+      k.point = 1;
+      k.pplane = 0;
+      continue;
+    }
+    const K3Op& kf = p->levels[l - 1].dA.k3;
+    launch3p_coarsen(nullptr, kf.n, kf.pg, kf.point == 1 ? 1 : 27, kf.pplane, q, (long)N);
+    MG_TRY(post_launch());
+    k.point = 2;
+    k.pplane = (long)N;
   }
   MG_HIP(hipDeviceSynchronize());
   p->has_point = true;
@@ -426,7 +457,7 @@ int build_plan(const PlanSpec& d, mgcmt_plan** out) {
     }
   }
   if (d.point_diag) {
-    const int rc = build_point_part(p, d.point_diag);
+    const int rc = d.dim == 3 ? build_point_part3(p, d.point_diag) : build_point_part(p, d.point_diag);
     if (rc != MGCMT_OK) {
       mgcmt_plan_destroy(p);
       return rc;
@@ -472,6 +503,13 @@ int mgcmt_plan_get_point_stencil(const mgcmt_plan* p, int l, double* out, int64_
   MG_TRY(check_level(p, l));
   if (!p->has_point) return fail(MGCMT_ERR_INVALID, "plan has no point diagonal");
   const Level& L = p->levels[l];
+  if (p->dim == 3) {
+    const K3Op& k3 = L.dA.k3;
+    const int64_t N = L.nr * L.gc, need3 = k3.point == 1 ? N : 27 * N;
+    if (!out || capacity < need3) return fail(MGCMT_ERR_INVALID, "point stencil buffer too small");
+    MG_HIP(hipMemcpy(out, k3.pg, (size_t)need3 * sizeof(double), hipMemcpyDeviceToHost));
+    return MGCMT_OK;
+  }
   const KOp& k = L.dA.k;
   const int64_t plane = L.nr * L.gc, need = k.point == 1 ? plane : 9 * plane;
   if (!out || capacity < need) return fail(MGCMT_ERR_INVALID, "point stencil buffer too small");
@@ -492,6 +530,25 @@ static int create3d(const mgcmt_plan3d_desc* d, int32_t m_nterms, const double* 
 }
 
 int mgcmt_plan_create3d(const mgcmt_plan3d_desc* d, mgcmt_plan** out) { return create3d(d, 0, nullptr, nullptr, nullptr, out); }
+
+int mgcmt_plan_create3d_pot(const mgcmt_plan3d_desc* d, const double* point_diag, mgcmt_plan** out) {
+  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!point_diag) return fail(MGCMT_ERR_INVALID, "null point diagonal");
+  if (d->lowest > 16) return fail(MGCMT_ERR_INVALID, "lowest must be at most 16 on a 3-D plan (the coarsest level is solved directly)");
+  PlanSpec spec{3, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->zfac, d->yfac, d->xfac}, {nullptr, nullptr, nullptr}, 0, 0, 0};
+  spec.point_diag = point_diag;
+  return build_plan(spec, out);
+}
+
+int mgcmt_plan3d_level_path(const mgcmt_plan* p, int l, int* kind, int* marching) {
+  MG_TRY(check_level(p, l));
+  if (p->dim != 3) return fail(MGCMT_ERR_INVALID, "mgcmt_plan3d_level_path needs a 3-D plan");
+  const K3Op& k = p->levels[l].dA.k3;
+  if (kind) *kind = k.point == 2 ? 3 : k.seven ? (k.point == 1 ? 2 : 1) : (k.point == 1 ? 4 : 0);
+  if (marching) *marching = k.point ? (point3_marching(k) ? 1 : 0) : (k.seven && k.n >= 64 && k.n % 64 == 0 ? 1 : 0);
+  return MGCMT_OK;
+}
 
 int mgcmt_plan_create3d_mass(const mgcmt_plan3d_desc* d, int32_t m_nterms, const double* m_zfac, const double* m_yfac, const double* m_xfac,
                              mgcmt_plan** out) {

@@ -14,16 +14,17 @@
 //     columns and marches a chunk of z-planes, each thread keeping its column's planes z-1, z, z+1 in registers, so that
 //     every plane of v is read from HBM once per pass (plus the two halo planes of each chunk); the x-y neighbours are
 //     the neighbouring threads' centre loads of the same plane (L1 / L2 hits).
+// A level with a per-point part (K3Op::point) is kernels_3d_point.hip's: the launchers below hand over.
 #include <cstdint>
 
+#include "kernels_3d_common.h"
 #include "mgcmt_internal.h"
 
 namespace mgcmt {
 
 namespace {
 
-constexpr int kFlatThreads = 256;
-constexpr int kTileX = 64, kTileY = 4, kChunkZ = 32;  // marching kernels: x-y tile per workgroup, z-planes per chunk
+using namespace k3;
 
 struct Coef3 {
   double sum;   // sum_j a_ij v_j over the stencil (centre included, unshifted)
@@ -172,47 +173,6 @@ __global__ void __launch_bounds__(kFlatThreads) k3_restrict(K3Op op, int residua
   }
   fc.p[q * fc.stride + I] = acc;
   if (zero_coarse) vc.p[q * vc.stride + I] = 0.0;
-}
-
-// (P e)(z, y, x) of the trilinear interpolation P = S (x) S (x) S: fine 2J+1 takes coarse J with weight 1, fine 2J takes
-// coarse J-1 and J with weight 1/2 each (where they exist)
-__device__ __forceinline__ double prolong_at(const double* __restrict__ e, long nc, long z, long y, long x) {
-  long jz[2], jy[2], jx[2];
-  double wz[2], wy[2], wx[2];
-  int nz = 0, ny = 0, nx = 0;
-  auto split = [nc](long i, long* j, double* w, int& cnt) {
-    if (i & 1) {
-      j[0] = i >> 1;
-      w[0] = 1.0;
-      cnt = 1;
-      return;
-    }
-    cnt = 0;
-    const long h = i >> 1;
-    if (h - 1 >= 0) {
-      j[cnt] = h - 1;
-      w[cnt++] = 0.5;
-    }
-    if (h < nc) {
-      j[cnt] = h;
-      w[cnt++] = 0.5;
-    }
-  };
-  split(z, jz, wz, nz);
-  split(y, jy, wy, ny);
-  split(x, jx, wx, nx);
-  double acc = 0.0;
-  for (int a = 0; a < nz; ++a) {
-    double pa = 0.0;
-    for (int b = 0; b < ny; ++b) {
-      const double* row = e + (jz[a] * nc + jy[b]) * nc;
-      double pb = 0.0;
-      for (int c = 0; c < nx; ++c) pb += wx[c] * row[jx[c]];
-      pa += wy[b] * pb;
-    }
-    acc += wz[a] * pa;
-  }
-  return acc;
 }
 
 // mode 0: dst = P e; 1: dst += P e
@@ -411,8 +371,6 @@ __global__ void __launch_bounds__(kTileX* kTileY) k3m_prolong_jacobi(K3Op op, KV
 
 bool marching(const K3Op& op) { return op.seven && op.n >= kTileX && op.n % kTileX == 0; }
 
-dim3 flat_grid(long points, int k) { return dim3((unsigned)((points + kFlatThreads - 1) / kFlatThreads), (unsigned)k, 1); }
-
 __global__ void k3_band_assemble(K3Op op, const double* __restrict__ shifts, KBand b) {
   const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= b.n) return;
@@ -443,10 +401,12 @@ __global__ void k3_band_assemble(K3Op op, const double* __restrict__ shifts, KBa
 }  // namespace
 
 void launch3_apply(hipStream_t s, const K3Op& op, KVec src, KVec dst, const double* shifts, int k) {
+  if (op.point) return launch3p_apply(s, op, src, dst, shifts, k);
   hipLaunchKernelGGL(k3_apply, flat_grid(op.n * op.n * op.n, k), dim3(kFlatThreads), 0, s, op, src, dst, shifts);
 }
 
 void launch3_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k) {
+  if (op.point) return launch3p_wjacobi(s, op, vin, f, vout, shifts, omega, k);
   if (marching(op)) {
     const int nch = (int)(op.n / kChunkZ);
     hipLaunchKernelGGL(k3m_sweep<0>, dim3((unsigned)(op.n / kTileX), (unsigned)(op.n / kTileY), (unsigned)(nch * k)), dim3(kTileX, kTileY), 0, s,
@@ -457,6 +417,7 @@ void launch3_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout,
 }
 
 void launch3_mc_sweep(hipStream_t s, const K3Op& op, KVec v, KVec f, const double* shifts, double omega, int k) {
+  if (op.point) return launch3p_mc_sweep(s, op, v, f, shifts, omega, k);
   // odd coordinate sum first: (0,0,1), (0,1,0), (1,0,0), (1,1,1), then (0,0,0), (0,1,1), (1,0,1), (1,1,0)
   static const int order[8][3] = {{0, 0, 1}, {0, 1, 0}, {1, 0, 0}, {1, 1, 1}, {0, 0, 0}, {0, 1, 1}, {1, 0, 1}, {1, 1, 0}};
   if (op.seven) {  // the four odd colours do not couple on a 7-point operator, nor the four even ones: two stages
@@ -477,6 +438,7 @@ void launch3_mc_sweep(hipStream_t s, const K3Op& op, KVec v, KVec f, const doubl
 }
 
 void launch3_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k) {
+  if (op.point) return launch3p_residual_restrict(s, op, v, f, fc, vc, shifts, k);
   const long nc = op.n / 2;
   if (marching(op)) {
     const int nch = (int)(op.n / kChunkZ);
@@ -497,6 +459,7 @@ void launch3_prolong(hipStream_t s, long n, KVec e, KVec dst, int accumulate, in
 }
 
 void launch3_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k) {
+  if (op.point) return launch3p_prolong_jacobi(s, op, e, vin, f, vout, shifts, omega, k);
   if (marching(op)) {
     const int nch = (int)(op.n / kChunkZ);
     hipLaunchKernelGGL(k3m_prolong_jacobi, dim3((unsigned)(op.n / kTileX), (unsigned)(op.n / kTileY), (unsigned)(nch * k)), dim3(kTileX, kTileY), 0, s,
@@ -508,6 +471,7 @@ void launch3_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVe
 
 void launch3_band_assemble(hipStream_t s, const K3Op& op, const double* shifts, KBand b, int k) {
   hipLaunchKernelGGL(k3_band_assemble, dim3((unsigned)((b.n + 127) / 128), (unsigned)k, 1), dim3(128), 0, s, op, shifts, b);
+  if (op.point) launch3p_band_add(s, op, b, k);  // the per-point entries, on top of the Kronecker part's
 }
 
 }  // namespace mgcmt

@@ -65,6 +65,15 @@ struct K3Op {
   const double* Z[kMaxTerms];
   int seven;
   double c0, czm, czp, cym, cyp, cxm, cxp;
+  // point: a per-point part on top of the Kronecker terms above (mgcmt_plan_create3d_pot; kernels_3d_point.hip).  1: a
+  // diagonal D(z, y, x) = pg[idx] (the fine level, g^3 numbers at the index of the right-hand side); 2: a 27-point stencil G
+  // (the Galerkin levels R D P): the coefficient of v(z + a - 1, y + b - 1, x + c - 1) in row idx is
+  // pg[(9 a + 3 b + c) * pplane + idx], zero towards points outside the grid.  The flags above describe the Kronecker part
+  // alone.  pmarch: a constant 7-point level with a diagonal takes the marching kernels where its size allows
+  // (MGCMT_3D_POINT_MARCH, read at plan creation).
+  int point, pmarch;
+  const double* pg;
+  long pplane;
 };
 
 // A batch of vectors on one level: interior pointer of vector 0, elements between vectors.
@@ -269,6 +278,18 @@ void launch3_prolong(hipStream_t s, long n, KVec e, KVec dst, int accumulate, in
 // vout <- one weighted-Jacobi sweep from w = vin + P e (w is not stored)
 void launch3_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
 void launch3_band_assemble(hipStream_t s, const K3Op& op, const double* shifts, KBand b, int k);
+// the same for a level with a per-point part (op.point; kernels_3d_point.hip) — the launchers above hand over —: flat
+// kernels for the 27-plane Galerkin levels, flat and marching ones for the constant 7-point fine level with a diagonal; the
+// per-point entries added into the assembled band matrix of the coarsest level; and the Galerkin product of the per-point
+// part: coarse <- R G P for the 27 planes (fine_planes = 27) or the diagonal (fine_planes = 1) of a level of fn^3 points
+bool point3_marching(const K3Op& op);
+void launch3p_apply(hipStream_t s, const K3Op& op, KVec src, KVec dst, const double* shifts, int k);
+void launch3p_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
+void launch3p_mc_sweep(hipStream_t s, const K3Op& op, KVec v, KVec f, const double* shifts, double omega, int k);
+void launch3p_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k);
+void launch3p_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
+void launch3p_band_add(hipStream_t s, const K3Op& op, const KBand& b, int k);
+void launch3p_coarsen(hipStream_t s, long fn, const double* fine, int fine_planes, long fplane, double* coarse, long cplane);
 
 // Rayleigh-quotient passes on 3-D levels (kernels_rq3d.hip), the protocol of launch_rq_pass1 / launch_rq_pass2 /
 // launch_rq_scalars2 and the same state words: pass 1 ends with the step's scalars; pass 2 returns the number of partial

@@ -44,8 +44,9 @@ class StructuredOperator:
     ``*`` and ``/``, unary minus, ``.shape``, ``.diagonal()``, ``.tocsr()``/``.toarray()`` (small
     sizes), and ``A.dot(x)`` / ``A * x`` / ``A @ x`` which run the HIP apply kernel.
 
-    ``point_diagonal`` (2-D only): a (g, g) array added to the diagonal, index [i, j] = row-major point i*g + j — an
-    arbitrary potential V(x, y) on top of the Kronecker terms (``potential_operator``, ``recognise_potential``).
+    ``point_diagonal`` (2-D and 3-D): a (g, g) array added to the diagonal, index [i, j] = row-major point i*g + j — an
+    arbitrary potential V(x, y) on top of the Kronecker terms (``potential_operator``, ``recognise_potential``); in 3-D a
+    (g, g, g) array, index [z, y, x] = point z*g^2 + y*g + x.
     """
 
     def __init__(self, dimension, g, terms, point_diagonal=None):
@@ -53,12 +54,17 @@ class StructuredOperator:
         self.g = int(g)
         self.point_diagonal = None
         if point_diagonal is not None:
-            if dimension != "2d":
-                raise ValueError("point_diagonal is a property of 2-D operators")
+            if dimension not in ("2d", "3d"):
+                raise ValueError("point_diagonal is a property of 2-D and 3-D operators")
             pd = np.ascontiguousarray(point_diagonal, dtype=np.float64)
-            if pd.size != self.g * self.g:
-                raise ValueError("point_diagonal must hold g x g = %d x %d values, not %r" % (self.g, self.g, pd.shape))
-            self.point_diagonal = pd.reshape(self.g, self.g)
+            if dimension == "3d":
+                if pd.size != self.g ** 3:
+                    raise ValueError("point_diagonal must hold g^3 = %d^3 values, not %r" % (self.g, pd.shape))
+                self.point_diagonal = pd.reshape(self.g, self.g, self.g)
+            else:
+                if pd.size != self.g * self.g:
+                    raise ValueError("point_diagonal must hold g x g = %d x %d values, not %r" % (self.g, self.g, pd.shape))
+                self.point_diagonal = pd.reshape(self.g, self.g)
         if dimension == "3d":
             # (X, Y, Z) per term: A = sum_m X_m (x) Y_m (x) Z_m over z, y, x (idx = z g^2 + y g + x)
             self.terms = [tuple(np.ascontiguousarray(a, dtype=np.float64) for a in t) for t in terms]
@@ -79,7 +85,8 @@ class StructuredOperator:
         if self.dimension == "1d":
             return StructuredOperator("1d", self.g, [(None, y * c) for _, y in self.terms])
         if self.dimension == "3d":
-            return StructuredOperator("3d", self.g, [(x, y, z * c) for x, y, z in self.terms])
+            return StructuredOperator("3d", self.g, [(x, y, z * c) for x, y, z in self.terms],
+                                      point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c)
         return StructuredOperator("2d", self.g, [(x, y * c) for x, y in self.terms],
                                   point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c)
 
@@ -107,7 +114,7 @@ class StructuredOperator:
         if self.dimension == "3d":
             i = tri_identity(self.g)
             terms = [tuple(a.copy() for a in t) for t in self.terms] + [(i, i.copy(), i * (-float(mu)))]
-            return StructuredOperator("3d", self.g, terms)
+            return StructuredOperator("3d", self.g, terms, point_diagonal=self.point_diagonal)
         terms = [(None if x is None else x.copy(), y.copy()) for x, y in self.terms]
         if self.dimension == "1d":
             terms[0][1][1] -= mu
@@ -120,7 +127,8 @@ class StructuredOperator:
         if self.dimension == "1d":
             return sum(y[1] for _, y in self.terms)
         if self.dimension == "3d":
-            return sum(np.kron(x[1], np.kron(y[1], z[1])) for x, y, z in self.terms)
+            d = sum(np.kron(x[1], np.kron(y[1], z[1])) for x, y, z in self.terms)
+            return d if self.point_diagonal is None else d + self.point_diagonal.reshape(-1)
         d = sum(np.outer(x[1], y[1]) for x, y in self.terms)
         return (d if self.point_diagonal is None else d + self.point_diagonal).reshape(-1)
 
@@ -130,8 +138,11 @@ class StructuredOperator:
         if self.dimension == "1d":
             return sum(tri_to_sparse(y) for _, y in self.terms).tocsr()
         if self.dimension == "3d":
-            return sum(sp.kron(tri_to_sparse(x), sp.kron(tri_to_sparse(y), tri_to_sparse(z), format="csr"), format="csr")
-                       for x, y, z in self.terms).tocsr()
+            A = sum(sp.kron(tri_to_sparse(x), sp.kron(tri_to_sparse(y), tri_to_sparse(z), format="csr"), format="csr")
+                    for x, y, z in self.terms).tocsr()
+            if self.point_diagonal is not None:
+                A = (A + sp.diags(self.point_diagonal.reshape(-1), 0, format="csr")).tocsr()
+            return A
         A = sum(sp.kron(tri_to_sparse(x), tri_to_sparse(y), format="csr") for x, y in self.terms).tocsr()
         if self.point_diagonal is not None:
             A = (A + sp.diags(self.point_diagonal.reshape(-1), 0, format="csr")).tocsr()
@@ -259,10 +270,17 @@ def potential_operator(g, V, scale=-1.0 / np.pi ** 2, dimension="2d"):
     the value at grid point i*g + j.  Matrix-free: the scaled Laplacian as two Kronecker terms, V as the operator's
     ``point_diagonal`` — for grids that cannot be assembled.  Nothing of V has to be separable (a circular dot, a double
     well, a rotated oscillator, disorder); a V that IS a(x) + b(y) or one square well runs faster through
-    ``potential_well_operator`` / ``recognise``, whose plans take the fused kernels on every level."""
-    if dimension != "2d":
-        raise ValueError("potential_operator: dimension must be '2d' (any tridiagonal is a 1-D operator already; 3-D has no per-point diagonal)")
+    ``potential_well_operator`` / ``recognise``, whose plans take the fused kernels on every level.
+
+    dimension="3d": H = scale * laplacian(g, "3d") + diag(V) on g^3 points, V a (g, g, g) array (or g^3 values), V[z, y, x]
+    the value at point z*g^2 + y*g + x: three Kronecker terms plus the point diagonal (a spherical dot, a lens, coupled
+    dots, disorder)."""
     g = int(g)
+    if dimension == "3d":
+        i, L = tri_identity(g), tri_laplacian(g) * float(scale)
+        return StructuredOperator("3d", g, [(i, i.copy(), L), (i.copy(), L.copy(), i.copy()), (L.copy(), i.copy(), i.copy())], point_diagonal=V)
+    if dimension != "2d":
+        raise ValueError("potential_operator: dimension must be '2d' or '3d' (any tridiagonal is a 1-D operator already)")
     L = tri_laplacian(g) * float(scale)
     return StructuredOperator("2d", g, [(tri_identity(g), L), (L.copy(), tri_identity(g))], point_diagonal=V)
 
@@ -323,9 +341,14 @@ def recognise_potential(A, dimension="2d"):
     it; otherwise the off-diagonals and a constant diagonal (the median entry, so that a potential that vanishes on most
     of the grid leaves mostly zeros) become two Kronecker terms and the rest of the diagonal the operator's
     ``point_diagonal``.  Anything that is not such a 5-point matrix raises UnrecognisedOperator.  ``recognise`` itself
-    never returns an operator with a point diagonal."""
+    never returns an operator with a point diagonal.
+
+    dimension="3d": the same for a 7-point matrix on a g^3 grid whose six off-diagonal bands have the form
+    X (x) I (x) I + I (x) Y (x) I + I (x) I (x) Z (``_recognise_3d``'s checks)."""
+    if dimension == "3d":
+        return _recognise_potential_3d(A)
     if dimension != "2d":
-        raise UnrecognisedOperator("recognise_potential: dimension must be '2d'")
+        raise UnrecognisedOperator("recognise_potential: dimension must be '2d' or '3d'")
     try:
         return recognise(A, "2d")
     except UnrecognisedOperator:
@@ -368,19 +391,39 @@ def recognise_potential(A, dimension="2d"):
     return op
 
 
-def _recognise_3d(A):
-    """X (x) I (x) I + I (x) Y (x) I + I (x) I (x) Z on a g^3 grid (idx = z g^2 + y g + x): scaled and shifted 3-D
-    Laplacians and additively separable diagonals.  The off-diagonals along each axis must depend on that axis' index
-    only; the diagonal is split into three parts and the result verified by re-assembly."""
+def _recognise_potential_3d(A):
+    """recognise_potential on g^3 grids: what ``recognise(A, "3d")`` maps is returned as it returns it; otherwise the six
+    bands (``_bands_3d``'s checks) and the median diagonal entry become three Toeplitz-diagonal Kronecker terms and the rest
+    of the diagonal the operator's ``point_diagonal``."""
+    try:
+        return recognise(A, "3d")
+    except UnrecognisedOperator:
+        if isinstance(A, StructuredOperator):
+            raise
     if not sp.issparse(A):
         A = sp.csr_matrix(np.asarray(A, dtype=np.float64))
-    tagged = getattr(A, "_mgcmt_structured", None)
-    if tagged is not None and tagged[1] == _digest(A) and tagged[0].dimension == "3d":
-        return tagged[0]
-    key = _cache_key(A)
+    key = ("potential3d",) + _cache_key(A)
     hit = _CACHE.get(key)
-    if hit is not None and hit[0] is A and hit[1].dimension == "3d":
+    if hit is not None and hit[0] is A:
         return hit[1]
+    g, M, d0, xs, ys, zs = _bands_3d(A)
+    base = float(np.median(d0))
+    Zt, Yt, Xt = np.zeros((3, g)), np.zeros((3, g)), np.zeros((3, g))
+    Zt[0], Zt[1], Zt[2] = zs[1], base / 3.0, zs[0]
+    Yt[0], Yt[1], Yt[2] = ys[1], base / 3.0, ys[0]
+    Xt[0], Xt[1], Xt[2] = xs[1], base - 2.0 * (base / 3.0), xs[0]
+    i = tri_identity(g)
+    op = StructuredOperator("3d", g, [(i, i.copy(), Xt), (i.copy(), Yt, i.copy()), (Zt, i.copy(), i.copy())], point_diagonal=d0 - base)
+    if len(_CACHE) > 64:
+        _CACHE.clear()
+    _CACHE[key] = (A, op)
+    return op
+
+
+def _bands_3d(A):
+    """(g, M, d0, xs, ys, zs) of a sparse 7-point matrix on a g^3 grid whose off-diagonal bands along each axis depend on
+    that axis' index only: the diagonal as a [z, y, x] array and per axis the (upper, lower) band as a function of the index.
+    Anything else raises UnrecognisedOperator."""
     n = A.shape[0]
     if A.shape[0] != A.shape[1]:
         raise UnrecognisedOperator("operator must be square")
@@ -420,6 +463,23 @@ def _recognise_3d(A):
     zs = [along(bands[g * g], 0), along(bands[-g * g], 0)]
     if any(a is None for a in xs + ys + zs):
         raise UnrecognisedOperator("3-D operator's off-diagonals are not of the form X (x) I (x) I + I (x) Y (x) I + I (x) I (x) Z")
+    return g, M, d0, xs, ys, zs
+
+
+def _recognise_3d(A):
+    """X (x) I (x) I + I (x) Y (x) I + I (x) I (x) Z on a g^3 grid (idx = z g^2 + y g + x): scaled and shifted 3-D
+    Laplacians and additively separable diagonals.  The off-diagonals along each axis must depend on that axis' index
+    only; the diagonal is split into three parts and the result verified by re-assembly."""
+    if not sp.issparse(A):
+        A = sp.csr_matrix(np.asarray(A, dtype=np.float64))
+    tagged = getattr(A, "_mgcmt_structured", None)
+    if tagged is not None and tagged[1] == _digest(A) and tagged[0].dimension == "3d":
+        return tagged[0]
+    key = _cache_key(A)
+    hit = _CACHE.get(key)
+    if hit is not None and hit[0] is A and hit[1].dimension == "3d":
+        return hit[1]
+    g, M, d0, xs, ys, zs = _bands_3d(A)
     c = d0[0, 0, 0] / 3.0
     Zt, Yt, Xt = np.zeros((3, g)), np.zeros((3, g)), np.zeros((3, g))
     Zt[0], Zt[1], Zt[2] = zs[1], d0[:, 0, 0] - 2.0 * c, zs[0]
@@ -567,6 +627,26 @@ def _constant_nine_point(M, g):
     if D.nnz and np.abs(D.data).max() != 0.0:
         return None
     return StructuredOperator("2d", g, terms)
+
+
+def planes_to_csr(G):
+    """The sparse matrix of a per-point stencil as ``Plan.point_stencil`` returns it below level 0: G[a, b, i, j] (2-D, nine
+    planes) or G[a, b, c, z, y, x] (3-D, 27 planes) is the coefficient of the neighbour at offset (a - 1, b - 1[, c - 1]) in
+    the row of the point.  Entries towards points outside the grid are dropped (the library stores zeros there)."""
+    G = np.asarray(G)
+    d = G.ndim // 2
+    gl = G.shape[-1]
+    idx = np.meshgrid(*([np.arange(gl)] * d), indexing="ij")
+    flat = lambda coords: sum(c * gl ** (d - 1 - k) for k, c in enumerate(coords))
+    rows, cols, vals = [], [], []
+    for off in np.ndindex(*([3] * d)):
+        nb = [i + o - 1 for i, o in zip(idx, off)]
+        ok = np.logical_and.reduce([(c >= 0) & (c < gl) for c in nb])
+        rows.append(flat(idx)[ok])
+        cols.append(flat(nb)[ok])
+        vals.append(G[off][ok])
+    n = gl ** d
+    return sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n))
 
 
 def tag_structured(matrix, op):

@@ -79,7 +79,16 @@ class Plan:
         desc.nterms, desc.nvec, desc.g, desc.lowest = nterms, self.nvec, self.g, self.lowest
         desc.zfac, desc.yfac, desc.xfac = as_dp(zfac), as_dp(yfac), as_dp(xfac)
         desc.device = self.device
-        if mass is None:
+        pd = getattr(op, "point_diagonal", None)
+        if pd is not None:
+            # an arbitrary potential V(x, y, z) on the diagonal: the per-point hierarchy R D P (27 planes per level) is built at creation
+            if mass is not None:
+                raise ValueError("a 3-D operator with a point diagonal takes no mass operator: the Rayleigh-quotient routines (rqmin, "
+                                 "vcycle_rqmg, ...) do not run on it; vcycle / vcycle_matrix, the smoothers wjacobi and gseidel_rb, "
+                                 "apply and drivers.block_eigensolve do")
+            pd = _f64(pd)
+            check(_lib.lib().mgcmt_plan_create3d_pot(ctypes.byref(desc), as_dp(pd), ctypes.byref(self._h)))
+        elif mass is None:
             check(_lib.lib().mgcmt_plan_create3d(ctypes.byref(desc), ctypes.byref(self._h)))
         else:
             mt, mz, my, mx = mass.factor_blocks()
@@ -124,11 +133,23 @@ class Plan:
     def point_stencil(self, level):
         """Host copy of the per-point part of `level` of a plan whose operator has a point diagonal: level 0 the diagonal,
         array [rows, cols]; below it the 9-point stencil R D P, array [3, 3, rows, cols] — entry [a, b, i, j] is the
-        coefficient of point (i + a - 1, j + b - 1) in row (i, j)."""
+        coefficient of point (i + a - 1, j + b - 1) in row (i, j).  3-D: [g, g, g] on level 0 and the 27-point stencil
+        [3, 3, 3, g_l, g_l, g_l] below — entry [a, b, c, z, y, x] is the coefficient of point (z + a - 1, y + b - 1, x + c - 1)."""
+        if self.dim == 3:
+            gl = self.g >> level
+            out = np.zeros((gl, gl, gl) if level == 0 else (3, 3, 3, gl, gl, gl))
+            check(_lib.lib().mgcmt_plan_get_point_stencil(self._h, level, as_dp(out), out.size))
+            return out
         r, c, _ = self.shapes[level]
         out = np.zeros((r, c) if level == 0 else (3, 3, r, c))
         check(_lib.lib().mgcmt_plan_get_point_stencil(self._h, level, as_dp(out), out.size))
         return out
+
+    def level_path_3d(self, level):
+        """(kind, marching) of a 3-D plan's level: one of _lib.PATH3D_* and whether the marching kernels run it."""
+        kind, marching = c_int(0), c_int(0)
+        check(_lib.lib().mgcmt_plan3d_level_path(self._h, level, ctypes.byref(kind), ctypes.byref(marching)))
+        return kind.value, bool(marching.value)
 
     def level_halo(self, level):
         """(halo rows kept around every vector of `level`, how many of them a sharded cycle exchanges and reads)"""

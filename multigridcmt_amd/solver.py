@@ -15,7 +15,7 @@ import scipy.sparse as sp
 
 from . import _lib
 from ._lib import GS_LEX, GS_MC, OP_A, OP_M, SLOT_F, SLOT_T, SLOT_V, SLOT_W, SOR_LEX, WJACOBI
-from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, recognise, recognise_potential,
+from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, planes_to_csr, recognise, recognise_potential,
                         tag_structured)
 from .plan import get_plan
 from .processor import MGCMTProcessor
@@ -58,17 +58,17 @@ def _check_3d_smoother(kind):
                          "wjacobi, gseidel_rb (multicolour) and foreign smoother callables")
 
 
-def _recognise_2d_entry(A, dimension):
-    """``recognise`` for the 2-D entry points: a 5-point matrix with an arbitrary diagonal (a Hamiltonian with any
-    potential), which ``recognise`` refuses, is mapped by ``recognise_potential`` to an operator with a point diagonal;
-    what that refuses too raises ``recognise``'s error."""
+def _recognise_entry(A, dimension):
+    """``recognise`` for the 2-D and 3-D entry points: a 5-point (7-point) matrix with an arbitrary diagonal (a Hamiltonian
+    with any potential), which ``recognise`` refuses, is mapped by ``recognise_potential`` to an operator with a point
+    diagonal; what that refuses too raises ``recognise``'s error."""
     try:
         return recognise(A, dimension)
     except UnrecognisedOperator as err:
-        if dimension != "2d" or isinstance(A, StructuredOperator):
+        if dimension not in ("2d", "3d") or isinstance(A, StructuredOperator):
             raise
         try:
-            return recognise_potential(A, "2d")
+            return recognise_potential(A, dimension)
         except UnrecognisedOperator:
             raise err
 
@@ -78,8 +78,8 @@ def _check_point_smoother(op, kind):
     instead of being replaced by another one."""
     if getattr(op, "point_diagonal", None) is not None and kind in (GS_LEX, SOR_LEX):
         raise ValueError("gseidel / sor (lexicographic) are not available for an operator with a point diagonal (an arbitrary "
-                         "potential V(x, y)); the supported smoothers are wjacobi, gseidel_rb (multicolour) and foreign "
-                         "smoother callables")
+                         "potential V(x, y) or V(x, y, z)); the supported smoothers are wjacobi, gseidel_rb (multicolour) and "
+                         "foreign smoother callables")
 
 
 class MGCMTSolver:
@@ -99,7 +99,7 @@ class MGCMTSolver:
         if dimension == "3d":
             _check_3d_smoother(kind)
         try:
-            op = _recognise_2d_entry(A, dimension)
+            op = _recognise_entry(A, dimension)
         except UnrecognisedOperator:
             if dimension in ("2d", "3d"):
                 raise
@@ -231,7 +231,17 @@ class MGCMTSolver:
         the Galerkin operator R*A*P of that level (:318), rebuilt from the plan's Kronecker factors."""
         if plan.dim == 3:
             fs = [plan.factors(level, w) for w in range(3)]
-            op = StructuredOperator("3d", plan.g >> level, [tuple(f[m].copy() for f in fs) for m in range(fs[0].shape[0])])
+            gl = plan.g >> level
+            terms = [tuple(f[m].copy() for f in fs) for m in range(fs[0].shape[0])]
+            if getattr(plan.op, "point_diagonal", None) is not None and level > 0:
+                # the Kronecker part's level plus the 27 planes of R D P the library formed
+                n = gl ** 3
+                M = StructuredOperator("3d", gl, terms).tocsr() + planes_to_csr(plan.point_stencil(level))
+                if shift:
+                    M = M - float(shift) * sp.identity(n, format="csr")
+                return M.tocsr()
+            pd = plan.point_stencil(0) if getattr(plan.op, "point_diagonal", None) is not None else None
+            op = StructuredOperator("3d", gl, terms, point_diagonal=pd)
             if shift:
                 op = op.shifted(float(shift))
             return tag_structured(op.tocsr(), op)
@@ -247,17 +257,7 @@ class MGCMTSolver:
                 if shift:
                     op = op.shifted(float(shift))
                 return tag_structured(op.tocsr(), op)
-            G = plan.point_stencil(level)
-            i, j = np.meshgrid(np.arange(gl), np.arange(gl), indexing="ij")
-            rows, cols, vals = [], [], []
-            for a in range(3):
-                for b in range(3):
-                    ok = (i + a - 1 >= 0) & (i + a - 1 < gl) & (j + b - 1 >= 0) & (j + b - 1 < gl)
-                    rows.append((i * gl + j)[ok])
-                    cols.append(((i + a - 1) * gl + (j + b - 1))[ok])
-                    vals.append(G[a, b][ok])
-            P = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(gl * gl, gl * gl))
-            M = StructuredOperator("2d", gl, terms).tocsr() + P
+            M = StructuredOperator("2d", gl, terms).tocsr() + planes_to_csr(plan.point_stencil(level))
             if shift:
                 M = M - float(shift) * sp.identity(gl * gl, format="csr")
             return M.tocsr()
@@ -351,7 +351,7 @@ class MGCMTSolver:
             return None
         g = int(g)
         try:
-            op = _recognise_2d_entry(A, dimension)
+            op = _recognise_entry(A, dimension)
         except UnrecognisedOperator:
             if dimension != "1d":
                 raise
@@ -392,7 +392,7 @@ class MGCMTSolver:
         g = self._grid(n, dimension)
         if not self._check_grid(g, lowest_level):
             return None
-        op = _recognise_2d_entry(A, dimension)
+        op = _recognise_entry(A, dimension)
         _check_point_smoother(op, kind)
         plan = get_plan(op, int(lowest_level), nvec=1)
         plan.set_shifts([float(shift)])
@@ -423,7 +423,7 @@ class MGCMTSolver:
         g = int(g)
         if g < 4:
             raise ValueError("twogrid needs a fine grid of at least 4 points per direction")
-        op = _recognise_2d_entry(A, dimension)
+        op = _recognise_entry(A, dimension)
         if getattr(op, "point_diagonal", None) is not None:
             raise ValueError("twogrid is not available for an operator with a point diagonal; vcycle (with lowest_level = g / 2: "
                              "the same two-grid cycle), vcycle_matrix and fmg are, with the smoothers wjacobi and gseidel_rb")
@@ -459,7 +459,7 @@ class MGCMTSolver:
         if not self._check_grid(g, lowest_level):
             return None
         self._check_stencil_maker(stencil_maker, dimension)
-        op = _recognise_2d_entry(A, dimension)
+        op = _recognise_entry(A, dimension)
         _check_point_smoother(op, kind)
         plan = get_plan(op, int(lowest_level), nvec=k)
         plan.set_shifts(shifts)

@@ -52,6 +52,10 @@ extern "C" {
 
 #define MGCMT_ABI_VERSION 7
 #define MGCMT_MAX_TERMS 4
+#define MGCMT_MAX_STORE_VEC 80   /* vectors a plan may keep per slot (nvec); an entry that takes a column count k batches at most 32, and
+                                    only columns 0..31 have a shift (mgcmt_apply with_shift) */
+#define MGCMT_BLOCK_WIDE_MAX 48  /* vectors of mgcmt_block_pencil, inputs of mgcmt_block_combine_wide */
+#define MGCMT_BLOCK_WIDE_OUT 16  /* outputs of mgcmt_block_combine_wide */
 #define MGCMT_HALO_ROWS 16 /* rows of halo kept above and below every vector of a 2-D level (a 1-D level keeps one: its
                               "row" is the whole vector); how many of them a sharded cycle fills: mgcmt_plan_level_halo */
 
@@ -304,6 +308,18 @@ int mgcmt_block_gram(mgcmt_plan* plan, int level, int na, const int* a_slots, co
                      const int* b_vecs, double* out, void* stream);
 int mgcmt_block_combine(mgcmt_plan* plan, int level, int nin, const int* in_slots, const int* in_vecs, int nout, const int* out_slots,
                         const int* out_vecs, const double* coeffs, void* stream);
+/* The same for wide blocks (up to 16 states: S = [X, W, P] of 48 vectors).  block_pencil: h_out = S^T AS and g_out = S^T MS
+ * (ms_slots = ms_vecs = NULL: M = I, g_out = S^T S) as full m x m row-major host matrices, 1 <= m <= MGCMT_BLOCK_WIDE_MAX, every
+ * named vector read once in one pass on the matrix cores; bit-reproducible from call to call; synchronises.  S and AS (and MS)
+ * are independent lists: nothing is assumed symmetric.  block_combine_wide: OUT_j = sum_i coeffs[i * nout + j] IN_i for
+ * nin <= MGCMT_BLOCK_WIDE_MAX inputs and nout <= MGCMT_BLOCK_WIDE_OUT distinct outputs, every input read once; an output may
+ * be one of the inputs; stream-ordered (coeffs may be reused on return).  Both entries work through scratch of the plan's
+ * own (partial tiles, the coefficient table), as the reductions do: the wide entries of one plan run on one stream at a time.
+ * Level vectors are 16-byte aligned and hold an even number of points; anything else is MGCMT_ERR_INVALID. */
+int mgcmt_block_pencil(mgcmt_plan* plan, int level, int m, const int* s_slots, const int* s_vecs, const int* as_slots, const int* as_vecs,
+                       const int* ms_slots, const int* ms_vecs, double* h_out, double* g_out, void* stream);
+int mgcmt_block_combine_wide(mgcmt_plan* plan, int level, int nin, const int* in_slots, const int* in_vecs, int nout, const int* out_slots,
+                             const int* out_vecs, const double* coeffs, void* stream);
 /* in-place Gram-Schmidt of vectors 0..k-1 of `slot`: modified != 0 -> MGS (:44-50), else CGS (:34-42) */
 int mgcmt_gramschmidt(mgcmt_plan* plan, int level, int slot, int k, int modified, void* stream);
 /* columns scaled to unit 2-norm (normalize, :52-63) */

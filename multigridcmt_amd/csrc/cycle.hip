@@ -225,9 +225,10 @@ int ensure_coarse_ready(mgcmt_plan* p, int l, int k, hipStream_t s) {
     B.b.width = 3 * kl + 1;
     B.b.ab_stride = n * B.b.width;
     B.b.piv_stride = n;
-    MG_HIP(hipMalloc((void**)&B.b.ab, sizeof(double) * B.b.ab_stride * p->nvec));
-    MG_HIP(hipMalloc((void**)&B.b.piv, sizeof(int) * B.b.piv_stride * p->nvec));
-    if (n <= 1024) MG_HIP(hipMalloc((void**)&B.inv, sizeof(double) * n * n * p->nvec));
+    const int cols = p->nvec < kMaxVec ? p->nvec : kMaxVec;  // (a solve batches at most kMaxVec columns: check_k)
+    MG_HIP(hipMalloc((void**)&B.b.ab, sizeof(double) * B.b.ab_stride * cols));
+    MG_HIP(hipMalloc((void**)&B.b.piv, sizeof(int) * B.b.piv_stride * cols));
+    if (n <= 1024) MG_HIP(hipMalloc((void**)&B.inv, sizeof(double) * n * n * cols));
   }
   bool same = B.valid && B.k >= k;
   if (same)

@@ -378,7 +378,7 @@ int build_plan(const PlanSpec& d, mgcmt_plan** out) {
   const int first_axis = d.dim == 1 ? 1 : 0, naxes = d.dim == 3 ? 3 : 2;
   for (int a = first_axis; a < naxes; ++a)
     if (!d.fac[a]) return fail(MGCMT_ERR_INVALID, "missing factor arrays");
-  if (d.nvec < 1 || d.nvec > kMaxVec) return fail(MGCMT_ERR_INVALID, "nvec out of range (1..32)");
+  if (d.nvec < 1 || d.nvec > kMaxStoreVec) return fail(MGCMT_ERR_INVALID, "nvec out of range (1..80)");
   const int64_t rows = d.dim == 1 ? 1 : d.g;
   int64_t rb = d.row_begin, re = d.row_end;
   if (d.dim != 2 || (rb == 0 && re == 0)) {
@@ -572,6 +572,9 @@ int mgcmt_plan_destroy(mgcmt_plan* p) {
     if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
   if (p->capture_stream) (void)hipStreamDestroy(p->capture_stream);
   if (p->d_rq) (void)hipFree(p->d_rq);
+  if (p->d_wide_partials) (void)hipFree(p->d_wide_partials);
+  if (p->d_wide_out) (void)hipFree(p->d_wide_out);
+  if (p->d_wide_table) (void)hipFree(p->d_wide_table);
   if (p->d_rqstate) (void)hipFree(p->d_rqstate);
   if (p->d_rqhistory) (void)hipFree(p->d_rqhistory);
   if (p->d_mgs) (void)hipFree(p->d_mgs);

@@ -1,0 +1,294 @@
+// Wide block operations of the blocked Rayleigh-Ritz eigen-solver (drivers.block_eigensolve with more than four states;
+// DESIGN.md par. 4.11b): the pencil H = S^T AS, G = S^T MS of up to 48 trial vectors in ONE pass over them, accumulated on
+// the matrix cores (v_mfma_f64_16x16x4_f64), and the tall-skinny product OUT = IN C with up to 48 inputs and 16 outputs.
+//
+// Pencil.  The contracted index of S^T AS is the grid point, so a 16 x 16 tile of H is a chain of 16x16x4 products over runs
+// of four points: A[i][k] = S_(16 I + i)(p + k), B[k][j] = AS_(16 J + j)(p + k).  Lane l of a wave holds A[l & 15][l >> 4] and
+// B[l >> 4][l & 15]: the vector index is l & 15 and the point index l >> 4 in BOTH operands, so one register of S serves
+// as A (of H and of G) and, when M = I, as B of G.  A sum over points has no prescribed order: each of the four K lane
+// groups streams its own run of kRun = 4 contiguous points per block step (two 16-byte loads per lane and vector; the four
+// groups of a wave cover 128 contiguous bytes of every vector), and the S and AS operands of one product see the same
+// point.  m is padded to whole tiles with zero operands; vectors the call did not name are never read.
+// Deterministic: a fixed point -> (block, wave, lane, trip) map, waves summed 0..3 through LDS, blocks summed 0..nb-1 by
+// k_pencil_final.
+#include <cstring>
+
+#include "mgcmt_internal.h"
+
+namespace mgcmt {
+namespace {
+
+constexpr int kWideThreads = 256, kWideWaves = kWideThreads / 64;
+constexpr int kRun = 4;                                // points per lane and block step
+constexpr int kStepPoints = kWideWaves * 4 * kRun;     // points per block step: 64
+constexpr int kPencilMaxBlocks = 512;
+constexpr int kTile = 16, kTileWords = kTile * kTile;
+
+// D += A B on one 16 x 16 x 4 tile; c[r] is D[(lane >> 4) + 4 r][lane & 15].  The host-side build (the CPU emulation of
+// the tests, and the host pass of hipcc, which never runs it) has no matrix cores: the same lane <-> element maps on wave
+// shuffles, the four products of an entry summed k = 0..3.
+__device__ __forceinline__ void mfma_f64_16x16x4(double a, double b, double (&c)[4]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef double v4d __attribute__((ext_vector_type(4)));
+  v4d cv = {c[0], c[1], c[2], c[3]};
+  cv = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, cv, 0, 0, 0);
+  c[0] = cv[0];
+  c[1] = cv[1];
+  c[2] = cv[2];
+  c[3] = cv[3];
+#else
+  const int lane = threadIdx.x & 63;
+  double bk[4];
+  for (int k = 0; k < 4; ++k) bk[k] = __shfl(b, (lane & 15) + 16 * k);  // B[k][col]
+  for (int r = 0; r < 4; ++r) {
+    const int row = (lane >> 4) + 4 * r;
+    for (int k = 0; k < 4; ++k) c[r] = fma(__shfl(a, row + 16 * k), bk[k], c[r]);  // A[row][k]
+  }
+#endif
+}
+
+// x[q] = v[p + q] for the points below n, zero beyond them and for a padding lane (v == nullptr); v is 16-byte aligned
+// and p a multiple of kRun (the launcher refuses anything else)
+__device__ __forceinline__ void load_run(const double* v, long p, long n, double (&x)[kRun]) {
+  if (v != nullptr && p + kRun <= n) {
+    const double2 a = reinterpret_cast<const double2*>(v + p)[0], b = reinterpret_cast<const double2*>(v + p)[1];
+    x[0] = a.x;
+    x[1] = a.y;
+    x[2] = b.x;
+    x[3] = b.y;
+  } else {
+#pragma unroll
+    for (int q = 0; q < kRun; ++q) x[q] = (v != nullptr && p + q < n) ? v[p + q] : 0.0;
+  }
+}
+
+struct PencilArgs {
+  const double* s[kBlockWideMax];
+  const double* as[kBlockWideMax];
+  const double* ms[kBlockWideMax];  // (MASS only)
+};
+
+// tiles of one launch, in the order of the partial sums: H (I, J) row-major, then G (I, J) row-major — all of them with a
+// mass operator, the upper triangle J >= I without (G = S^T S is symmetric to the last bit; the host mirrors it)
+__host__ __device__ constexpr int pencil_tiles(int t, bool mass) { return t * t + (mass ? t * t : t * (t + 1) / 2); }
+
+// T: tiles per side (m <= 16 T)
+template <int T, bool MASS>
+__global__ void __launch_bounds__(kWideThreads) k_block_pencil(long n, PencilArgs g, int m, double* __restrict__ partials) {
+  __shared__ double s_red[kWideWaves - 1][kTileWords];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, kg = lane >> 4;
+  const double *ps[T], *pa[T], *pm[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    const int v = kTile * t + col;
+    ps[t] = v < m ? g.s[v] : nullptr;
+    pa[t] = v < m ? g.as[v] : nullptr;
+    pm[t] = (MASS && v < m) ? g.ms[v] : nullptr;
+  }
+  double acc_h[T][T][4], acc_g[T][T][4];
+#pragma unroll
+  for (int i = 0; i < T; ++i)
+#pragma unroll
+    for (int j = 0; j < T; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc_h[i][j][r] = acc_g[i][j][r] = 0.0;
+
+  const long nsteps = (n + kStepPoints - 1) / kStepPoints;
+  const long lane_off = (long)(wave * 4 + kg) * kRun;
+  double xs[T][kRun], xa[T][kRun], xm[T][kRun], ys[T][kRun], ya[T][kRun], ym[T][kRun];
+  long step = blockIdx.x;  // (every wave of a block takes the same trips: the emulation's shuffles need whole workgroups)
+  if (step < nsteps) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      load_run(ps[t], step * kStepPoints + lane_off, n, xs[t]);
+      load_run(pa[t], step * kStepPoints + lane_off, n, xa[t]);
+      if (MASS) load_run(pm[t], step * kStepPoints + lane_off, n, xm[t]);
+    }
+  }
+  for (; step < nsteps; step += gridDim.x) {
+    const long next = step + gridDim.x;
+    if (next < nsteps) {  // the next step's operands are in flight while this step's products run
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        load_run(ps[t], next * kStepPoints + lane_off, n, ys[t]);
+        load_run(pa[t], next * kStepPoints + lane_off, n, ya[t]);
+        if (MASS) load_run(pm[t], next * kStepPoints + lane_off, n, ym[t]);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < kRun; ++q)
+#pragma unroll
+      for (int i = 0; i < T; ++i)
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+          mfma_f64_16x16x4(xs[i][q], xa[j][q], acc_h[i][j]);
+          if (MASS) mfma_f64_16x16x4(xs[i][q], xm[j][q], acc_g[i][j]);
+          else if (j >= i) mfma_f64_16x16x4(xs[i][q], xs[j][q], acc_g[i][j]);
+        }
+    if (next < nsteps) {
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int q = 0; q < kRun; ++q) {
+          xs[t][q] = ys[t][q];
+          xa[t][q] = ya[t][q];
+          if (MASS) xm[t][q] = ym[t][q];
+        }
+    }
+  }
+
+  // waves 1..3 hand their tile to wave 0 through LDS, one tile at a time; wave 0 adds them in wave order and stores the
+  // block's partial tile row-major: partials[(tile * gridDim.x + block) * 256 + row * 16 + col]
+  int tile = 0;
+#pragma unroll
+  for (int which = 0; which < 2; ++which)
+#pragma unroll
+    for (int i = 0; i < T; ++i)
+#pragma unroll
+      for (int j = 0; j < T; ++j) {
+        if (which == 1 && !MASS && j < i) continue;
+        const double(&acc)[4] = which == 0 ? acc_h[i][j] : acc_g[i][j];
+        if (wave > 0) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s_red[wave - 1][r * 64 + lane] = acc[r];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            double tot = acc[r];
+            for (int w = 0; w < kWideWaves - 1; ++w) tot += s_red[w][r * 64 + lane];
+            partials[((long)tile * gridDim.x + blockIdx.x) * kTileWords + (kg + 4 * r) * kTile + col] = tot;
+          }
+        }
+        __syncthreads();
+        ++tile;
+      }
+}
+
+// out[tile * 256 + e] = sum over blocks b = 0..nb-1, in that order, of partials[(tile * nb + b) * 256 + e]
+__global__ void __launch_bounds__(kTileWords) k_pencil_final(int nb, const double* __restrict__ partials, double* __restrict__ out) {
+  const double* src = partials + (long)blockIdx.x * nb * kTileWords + threadIdx.x;
+  double tot = 0.0;
+  for (int b = 0; b < nb; ++b) tot += src[(long)b * kTileWords];
+  out[(long)blockIdx.x * kTileWords + threadIdx.x] = tot;
+}
+
+// The table of a wide combine in device memory (48 x 16 coefficients do not fit the kernel arguments): kWideCoefWords
+// coefficients c[t][j] (rows of 16, zero beyond nout), then the input and the output pointers.  Filled stream-ordered by
+// k_wide_stage from chunks that travel as kernel arguments, so nothing depends on the lifetime of host memory.
+constexpr int kWideCoefWords = kBlockWideMax * kBlockWideOut;
+constexpr int kStageWords = 416;  // (half the table: 3.3 KB of kernel arguments)
+struct StageArgs {
+  unsigned long long w[kStageWords];
+};
+__global__ void __launch_bounds__(kWideThreads) k_wide_stage(unsigned long long* __restrict__ table, int offset, int count, StageArgs a) {
+  for (int t = threadIdx.x; t < count; t += blockDim.x) table[offset + t] = a.w[t];
+}
+
+// OUT_j = sum_t c[t][j] IN_t on the vector ALUs (about 3 flop per byte moved: far below what they sustain per byte of
+// HBM traffic, and a thread that owns its points keeps "all inputs of a point are read before any output of it is
+// written" true by construction, so an output may be one of the inputs).  The coefficients and pointers are wave-uniform:
+// they come through the scalar cache.  Two points per thread and 16-byte accesses (n even, every vector 16-byte aligned:
+// the launcher refuses anything else).
+__global__ void __launch_bounds__(kWideThreads) k_block_combine_wide(long n2, const unsigned long long* __restrict__ table, int nin, int nout) {
+  const double* __restrict__ coef = reinterpret_cast<const double*>(table);
+  const double* const* in = reinterpret_cast<const double* const*>(table + kWideCoefWords);
+  double* const* out = reinterpret_cast<double* const*>(table + kWideCoefWords + kBlockWideMax);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x) {
+    double2 acc[kBlockWideOut];
+#pragma unroll
+    for (int j = 0; j < kBlockWideOut; ++j) acc[j] = make_double2(0.0, 0.0);
+#pragma unroll 4
+    for (int t = 0; t < nin; ++t) {
+      const double* c = coef + t * kBlockWideOut;
+      const double2 x = reinterpret_cast<const double2*>(in[t])[i];
+#pragma unroll
+      for (int j = 0; j < kBlockWideOut; ++j) {
+        acc[j].x = fma(c[j], x.x, acc[j].x);
+        acc[j].y = fma(c[j], x.y, acc[j].y);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kBlockWideOut; ++j)
+      if (j < nout) reinterpret_cast<double2*>(out[j])[i] = acc[j];
+  }
+}
+
+}  // namespace
+
+int block_pencil_blocks(long n) {
+  long b = (n + kStepPoints - 1) / kStepPoints;
+  if (b > kPencilMaxBlocks) b = kPencilMaxBlocks;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+int block_pencil_tiles(int m, bool mass) { return pencil_tiles((m + kTile - 1) / kTile, mass); }
+
+long block_wide_table_words() { return kWideCoefWords + kBlockWideMax + kBlockWideOut; }
+
+// out (device) = the tiles of H then G, 256 numbers each, row-major inside a tile, in the order of pencil_tiles;
+// `partials` holds block_pencil_tiles(m, ms != nullptr) * block_pencil_blocks(n) * 256 doubles.  false (nothing launched): a
+// vector is not 16-byte aligned — no level of a plan has such vectors
+bool launch_block_pencil(hipStream_t s, long n, int m, const double* const* sv, const double* const* as, const double* const* ms, double* partials,
+                         double* out) {
+  PencilArgs g{};
+  uintptr_t bits = 0;
+  for (int t = 0; t < kBlockWideMax; ++t) {
+    g.s[t] = sv[t < m ? t : 0];
+    g.as[t] = as[t < m ? t : 0];
+    g.ms[t] = ms ? ms[t < m ? t : 0] : nullptr;
+    if (t < m) bits |= (reinterpret_cast<uintptr_t>(sv[t]) | reinterpret_cast<uintptr_t>(as[t]) | (ms ? reinterpret_cast<uintptr_t>(ms[t]) : 0)) & 15;
+  }
+  if (bits != 0) return false;
+  const int blocks = block_pencil_blocks(n), tiles = (m + kTile - 1) / kTile;
+  const dim3 grid(blocks), block(kWideThreads);
+  if (ms) {
+    if (tiles == 1) hipLaunchKernelGGL((k_block_pencil<1, true>), grid, block, 0, s, n, g, m, partials);
+    else if (tiles == 2) hipLaunchKernelGGL((k_block_pencil<2, true>), grid, block, 0, s, n, g, m, partials);
+    else hipLaunchKernelGGL((k_block_pencil<3, true>), grid, block, 0, s, n, g, m, partials);
+  } else {
+    if (tiles == 1) hipLaunchKernelGGL((k_block_pencil<1, false>), grid, block, 0, s, n, g, m, partials);
+    else if (tiles == 2) hipLaunchKernelGGL((k_block_pencil<2, false>), grid, block, 0, s, n, g, m, partials);
+    else hipLaunchKernelGGL((k_block_pencil<3, false>), grid, block, 0, s, n, g, m, partials);
+  }
+  hipLaunchKernelGGL(k_pencil_final, dim3(pencil_tiles(tiles, ms != nullptr)), dim3(kTileWords), 0, s, blocks, partials, out);
+  return true;
+}
+
+// out_j = sum_t c[t * nout + j] in_t; `table`: block_wide_table_words() words of device memory.  false (nothing launched): n is
+// odd or a vector is not 16-byte aligned — no level of a plan has such vectors
+bool launch_block_combine_wide(hipStream_t s, long n, const double* const* in, int nin, double* const* out, int nout, const double* c,
+                               unsigned long long* table) {
+  const int words = (int)block_wide_table_words();
+  unsigned long long host[kWideCoefWords + kBlockWideMax + kBlockWideOut];
+  uintptr_t bits = (uintptr_t)(n & 1);
+  for (int t = 0; t < kBlockWideMax; ++t) {
+    for (int j = 0; j < kBlockWideOut; ++j) {
+      const double v = (t < nin && j < nout) ? c[t * nout + j] : 0.0;
+      memcpy(&host[t * kBlockWideOut + j], &v, sizeof(double));
+    }
+    host[kWideCoefWords + t] = reinterpret_cast<uintptr_t>(in[t < nin ? t : 0]);
+    if (t < nin) bits |= reinterpret_cast<uintptr_t>(in[t]) & 15;
+  }
+  for (int j = 0; j < kBlockWideOut; ++j) {
+    host[kWideCoefWords + kBlockWideMax + j] = reinterpret_cast<uintptr_t>(out[j < nout ? j : 0]);
+    if (j < nout) bits |= reinterpret_cast<uintptr_t>(out[j]) & 15;
+  }
+  if (bits != 0) return false;
+  for (int off = 0; off < words; off += kStageWords) {
+    StageArgs a{};
+    const int count = words - off < kStageWords ? words - off : kStageWords;
+    memcpy(a.w, host + off, sizeof(unsigned long long) * count);
+    hipLaunchKernelGGL(k_wide_stage, dim3(1), dim3(kWideThreads), 0, s, table, off, count, a);
+  }
+  const long n2 = n / 2;
+  long blocks = (n2 + kWideThreads - 1) / kWideThreads;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_block_combine_wide, dim3((unsigned)blocks), dim3(kWideThreads), 0, s, n2, table, nin, nout);
+  return true;
+}
+
+}  // namespace mgcmt

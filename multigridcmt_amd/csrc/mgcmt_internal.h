@@ -12,6 +12,7 @@ namespace mgcmt {
 constexpr int kHalo = MGCMT_HALO_ROWS;
 constexpr int kMaxTerms = MGCMT_MAX_TERMS;
 constexpr int kMaxVec = 32;  // upper bound on simultaneous vectors of one launch
+constexpr int kMaxStoreVec = MGCMT_MAX_STORE_VEC;  // ... and on the vectors a plan keeps per slot (only the block entries see those beyond kMaxVec)
 
 // Operator of one level as the kernels see it:  A = sum_m X_m (x) Y_m  (shift applied separately).
 // X[m] / Y[m] point at element 0 of the `lower` array; `diag` is at +ldx, `upper` at +2*ldx.
@@ -185,6 +186,15 @@ constexpr int kBlockMaxA = 12, kBlockMaxB = 4;  // block operations: up to 12 x 
 void launch_probe_issue(hipStream_t s, int what, int iters, int blocks, double* sink);  // kinds 20..23 of mgcmt_bandwidth_probe
 void launch_block_gram(hipStream_t s, long n, const double* const* a, int na, const double* const* b, int nb, double* partials, double* out);
 void launch_block_combine(hipStream_t s, long n, const double* const* in, int nin, double* const* out, int nout, const double* c);
+// wide block operations (kernels_blockwide.hip): the pencil of up to 48 vectors on the matrix cores, OUT = IN C for 48 -> 16
+constexpr int kBlockWideMax = MGCMT_BLOCK_WIDE_MAX, kBlockWideOut = MGCMT_BLOCK_WIDE_OUT;
+int block_pencil_blocks(long n);
+int block_pencil_tiles(int m, bool mass);
+long block_wide_table_words();
+bool launch_block_pencil(hipStream_t s, long n, int m, const double* const* sv, const double* const* as, const double* const* ms, double* partials,
+                         double* out);
+bool launch_block_combine_wide(hipStream_t s, long n, const double* const* in, int nin, double* const* out, int nout, const double* c,
+                               unsigned long long* table);
 void launch_gram(hipStream_t s, long n, const double* const* v, int nv, double* partials, double* out);
 void launch_lincomb(hipStream_t s, long n, const double* const* v, const double* c, int nt, double* dst);
 bool mgs_small_fits(long n);

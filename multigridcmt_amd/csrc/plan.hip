@@ -69,6 +69,8 @@ int check_vec(const mgcmt_plan* p, int l, int slot, int vec) {
 
 int check_k(const mgcmt_plan* p, int k) {
   if (k < 1 || k > p->nvec) return fail(MGCMT_ERR_INVALID, "k must be in 1..nvec");
+  // (a plan may store more vectors than one launch batches: the shifts, the reduction results and the kernels' static arrays hold kMaxVec)
+  if (k > kMaxVec) return fail(MGCMT_ERR_INVALID, "k must be at most 32: a plan stores up to 80 vectors per slot, an entry batches 32 columns");
   return MGCMT_OK;
 }
 
@@ -167,6 +169,8 @@ int mgcmt_apply(mgcmt_plan* p, int op, int l, int src_slot, int src_vec, int dst
   MG_TRY(check_vec(p, l, dst_slot, dst_vec));
   if (src_slot == dst_slot && src_vec == dst_vec) return fail(MGCMT_ERR_INVALID, "apply cannot run in place");
   if (op == MGCMT_OP_M && !p->has_mass) return fail(MGCMT_ERR_INVALID, "plan has no mass operator");
+  // (the shift of column src_vec: the plan holds kMaxVec of them however many vectors it stores)
+  if (with_shift && src_vec >= kMaxVec) return fail(MGCMT_ERR_INVALID, "apply with_shift: only columns 0..31 have a shift");
   MG_TRY(ensure_slot(p, l, src_slot));
   MG_TRY(ensure_slot(p, l, dst_slot));
   const KOp& k = op == MGCMT_OP_M ? p->levels[l].dM.k : p->levels[l].dA.k;
@@ -303,6 +307,80 @@ int mgcmt_block_combine(mgcmt_plan* p, int l, int nin, const int* in_slots, cons
       if (out[i] == out[j]) return fail(MGCMT_ERR_INVALID, "block_combine: an output vector named twice");
   }
   launch_block_combine(S(stream), p->interior(l), in, nin, out, nout, coeffs);
+  return post_launch();
+}
+
+// (slot, vec) pairs of a wide block entry -> device pointers
+static int wide_vectors(mgcmt_plan* p, int l, int count, const int* slots, const int* vecs, double** out) {
+  for (int t = 0; t < count; ++t) {
+    MG_TRY(check_vec(p, l, slots[t], vecs[t]));
+    MG_TRY(ensure_slot(p, l, slots[t]));
+    out[t] = p->kvec(l, slots[t], vecs[t]).p;
+  }
+  return MGCMT_OK;
+}
+
+int mgcmt_block_pencil(mgcmt_plan* p, int l, int m, const int* s_slots, const int* s_vecs, const int* as_slots, const int* as_vecs,
+                       const int* ms_slots, const int* ms_vecs, double* h_out, double* g_out, void* stream) {
+  MG_TRY(check_level(p, l));
+  if (!s_slots || !s_vecs || !as_slots || !as_vecs || !h_out || !g_out || (ms_slots == nullptr) != (ms_vecs == nullptr) || m < 1 || m > kBlockWideMax)
+    return fail(MGCMT_ERR_INVALID, "block_pencil: 1..48 vectors, non-null arguments (ms_slots and ms_vecs both null: M = I)");
+  const bool mass = ms_slots != nullptr;
+  double *sv[kBlockWideMax], *as[kBlockWideMax], *ms[kBlockWideMax];
+  MG_TRY(wide_vectors(p, l, m, s_slots, s_vecs, sv));
+  MG_TRY(wide_vectors(p, l, m, as_slots, as_vecs, as));
+  if (mass) MG_TRY(wide_vectors(p, l, m, ms_slots, ms_vecs, ms));
+  const long n = p->interior(l);
+  const int tiles = block_pencil_tiles(m, mass), side = (m + 15) / 16;
+  const size_t need = (size_t)tiles * block_pencil_blocks(n) * 256;
+  if (need > p->wide_partials_doubles) {
+    MG_HIP(hipStreamSynchronize(S(stream)));  // (an earlier pencil on this stream may still read the old buffer)
+    if (p->d_wide_partials) (void)hipFree(p->d_wide_partials);
+    p->d_wide_partials = nullptr;
+    p->wide_partials_doubles = 0;
+    MG_HIP(hipMalloc((void**)&p->d_wide_partials, sizeof(double) * need));
+    p->wide_partials_doubles = need;
+  }
+  constexpr int kMaxTiles = 2 * 3 * 3;
+  if (!p->d_wide_out) MG_HIP(hipMalloc((void**)&p->d_wide_out, sizeof(double) * kMaxTiles * 256));
+  if (!launch_block_pencil(S(stream), n, m, sv, as, mass ? ms : nullptr, p->d_wide_partials, p->d_wide_out))
+    return fail(MGCMT_ERR_INVALID, "block_pencil: a vector is not 16-byte aligned");
+  MG_TRY(post_launch());
+  std::vector<double> packed((size_t)tiles * 256);
+  MG_HIP(hipMemcpyAsync(packed.data(), p->d_wide_out, sizeof(double) * packed.size(), hipMemcpyDeviceToHost, S(stream)));
+  MG_HIP(hipStreamSynchronize(S(stream)));
+  // tiles of H (I, J) row-major, then of G: all of them with a mass operator, the upper triangle J >= I (mirrored here) without
+  const double* t = packed.data();
+  for (int which = 0; which < 2; ++which) {
+    double* out = which == 0 ? h_out : g_out;
+    for (int I = 0; I < side; ++I)
+      for (int J = 0; J < side; ++J) {
+        if (which == 1 && !mass && J < I) continue;
+        for (int r = 0; r < 16 && 16 * I + r < m; ++r)
+          for (int c = 0; c < 16 && 16 * J + c < m; ++c) {
+            out[(16 * I + r) * m + 16 * J + c] = t[r * 16 + c];
+            if (which == 1 && !mass && J > I) out[(16 * J + c) * m + 16 * I + r] = t[r * 16 + c];
+          }
+        t += 256;
+      }
+  }
+  return MGCMT_OK;
+}
+
+int mgcmt_block_combine_wide(mgcmt_plan* p, int l, int nin, const int* in_slots, const int* in_vecs, int nout, const int* out_slots,
+                             const int* out_vecs, const double* coeffs, void* stream) {
+  MG_TRY(check_level(p, l));
+  if (!in_slots || !in_vecs || !out_slots || !out_vecs || !coeffs || nin < 1 || nin > kBlockWideMax || nout < 1 || nout > kBlockWideOut)
+    return fail(MGCMT_ERR_INVALID, "block_combine_wide: 1..48 inputs, 1..16 outputs, non-null arguments");
+  double *in[kBlockWideMax], *out[kBlockWideOut];
+  MG_TRY(wide_vectors(p, l, nin, in_slots, in_vecs, in));
+  MG_TRY(wide_vectors(p, l, nout, out_slots, out_vecs, out));
+  for (int j = 0; j < nout; ++j)
+    for (int i = 0; i < j; ++i)
+      if (out[i] == out[j]) return fail(MGCMT_ERR_INVALID, "block_combine_wide: an output vector named twice");
+  if (!p->d_wide_table) MG_HIP(hipMalloc((void**)&p->d_wide_table, sizeof(unsigned long long) * block_wide_table_words()));
+  if (!launch_block_combine_wide(S(stream), p->interior(l), in, nin, out, nout, coeffs, p->d_wide_table))
+    return fail(MGCMT_ERR_INVALID, "block_combine_wide: an odd number of points or a vector that is not 16-byte aligned");
   return post_launch();
 }
 

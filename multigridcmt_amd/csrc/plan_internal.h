@@ -73,6 +73,12 @@ struct mgcmt_plan {
   double* d_zero = nullptr;     // [kMaxVec] zeros (apply without shift)
   double* d_partials = nullptr; // reduction scratch
   double* d_scalars = nullptr;  // [4*kMaxVec] reduction results
+  // wide block operations (kernels_blockwide.hip), allocated on first use: per-workgroup partial tiles of the pencil, its
+  // summed tiles, and the coefficient / pointer table of the wide combine
+  double* d_wide_partials = nullptr;
+  size_t wide_partials_doubles = 0;
+  double* d_wide_out = nullptr;
+  unsigned long long* d_wide_table = nullptr;
   double* d_rq = nullptr;       // Gram results of mgcmt_rayleigh_residual, one block per column
   double* d_rqstate = nullptr;  // scalars of the device-resident Rayleigh-quotient minimisation (kernels_rq.hip)
   double* d_mgs = nullptr;  // the blocked Gram-Schmidt's R^-1 and gate word (kernels_blas.hip)

@@ -588,6 +588,8 @@ int mgcmt_comm_set_option(mgcmt_plan* p, int option, int value) {
 }
 
 int mgcmt_halo_exchange(mgcmt_plan* p, int l, int slot_mask, void* stream) {
+  // (a plan may store more vectors than a launch batches — the shifts and the reduction buffers hold kMaxVec —: refused first)
+  if (((slot_mask >> 16) & 0xff) > kMaxVec) return fail(MGCMT_ERR_INVALID, "halo_exchange: at most 32 columns per call");
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_halo_exchange"));
   MG_TRY(check_comm(p));
   if (l < 0 || l >= (int)p->levels.size()) return fail(MGCMT_ERR_INVALID, "level out of range");
@@ -604,6 +606,8 @@ int mgcmt_halo_exchange(mgcmt_plan* p, int l, int slot_mask, void* stream) {
 }
 
 int mgcmt_gather_coarse(mgcmt_plan* p, int l, int slot, mgcmt_plan* coarse, int dst_slot, int k, void* stream) {
+  // (a plan may store more vectors than a launch batches — the shifts and the reduction buffers hold kMaxVec —: refused first)
+  if (k > kMaxVec) return fail(MGCMT_ERR_INVALID, "gather_coarse: at most 32 columns per call");
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_gather_coarse"));
   MG_TRY(mgcmt::unsupported_3d(coarse, "mgcmt_gather_coarse"));
   MG_TRY(check_comm(p));
@@ -677,6 +681,8 @@ int mgcmt_allreduce_sum(mgcmt_plan* p, double* host_inout, int n, void* stream) 
 // arithmetic (the Gram-Schmidt's inner products are summed rank by rank: equal to rounding).
 int mgcmt_sharded_vcycle(mgcmt_plan* p, mgcmt_plan* coarse, int nu1, int nu2, int nu_coarse, int kind, double omega, int k, int flags,
                          void* stream) {
+  // (a plan may store more vectors than a launch batches — the shifts and the reduction buffers hold kMaxVec —: refused first)
+  if (k > kMaxVec) return fail(MGCMT_ERR_INVALID, "sharded_vcycle: at most 32 columns per call");
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_sharded_vcycle"));
   MG_TRY(mgcmt::unsupported_point(p, "mgcmt_sharded_vcycle"));
   MG_TRY(mgcmt::unsupported_point(coarse, "mgcmt_sharded_vcycle"));

@@ -271,7 +271,7 @@ class ShardedPlan:
         """|| F - (A - mu I) V ||_2 of column `vec` over all ranks."""
         P = self.plan
         if not self._v_halo_valid:
-            self.exchange_halo((0, SLOT_V), ring=self.emulate is not None, k=self.nvec)
+            self.exchange_halo((0, SLOT_V), ring=self.emulate is not None, k=min(self.nvec, _lib.MAX_VEC))
             self._v_halo_valid = True
         P.apply(0, (SLOT_V, vec), (SLOT_T, vec), with_shift=True)
         P.axpy(0, -1.0, (SLOT_F, vec), (SLOT_T, vec))

@@ -292,6 +292,9 @@ def potential_well_eigensolve(gridsize=2 ** 7, depth=50.0, inner=None, cycles=8,
     return rho, plan.download(0, X[0], X[1])
 
 
+BLOCK_EIGENSOLVE_MAX = 16   # states of block_eigensolve: S = [X, W, P] is then the 48 vectors of mgcmt_block_pencil
+
+
 def block_eigensolve(op, k=4, cycles=12, nu=2, lowest=8, smoother="rb", seed=0, guesses=None, history=None, residuals=None,
                      use_p=True, stats=None, mass=None):
     """SURVEY par. 8(f)4: the k lowest eigenpairs of a structured 2-D or 3-D operator — of the pencil (A, M) with ``mass`` — by
@@ -304,7 +307,10 @@ def block_eigensolve(op, k=4, cycles=12, nu=2, lowest=8, smoother="rb", seed=0, 
     from a zero start (k columns batched);  A W, M W;  Rayleigh-Ritz over S = [X, W, P] (P: the previous update directions;
     use_p=False gives blocked preconditioned steepest descent): the 3k x 3k pencil (S^T A S, S^T M S) from one-pass block
     Gram products, its k lowest pairs on the host, then X, P and their images under A and M updated by tall-skinny
-    products.  The host sees Gram matrices only.  k <= 4.  ``mass``: a StructuredOperator (None: the identity — nothing of
+    products.  The host sees Gram matrices only.  1 <= k <= 16: up to four states take the 12 x 4 block kernels
+    (mgcmt_block_gram / mgcmt_block_combine, several Gram products per pencil); more take the wide ones — the whole pencil of
+    S from ONE mgcmt_block_pencil call (matrix cores), the updates through mgcmt_block_combine_wide, the residual norms from
+    one call as well.  ``mass``: a StructuredOperator (None: the identity — nothing of
     M is then stored or applied).
 
     Returns (eigenvalues, eigenvectors[n, k]) with X^T M X = I; ``history`` receives the Ritz values after every iteration,
@@ -313,13 +319,14 @@ def block_eigensolve(op, k=4, cycles=12, nu=2, lowest=8, smoother="rb", seed=0, 
     from ._lib import OP_M
     from .plan import get_plan
     k = int(k)
-    if not 1 <= k <= 4:
-        raise ValueError("block_eigensolve handles 1..4 eigenpairs at a time")
+    if not 1 <= k <= BLOCK_EIGENSOLVE_MAX:
+        raise ValueError("block_eigensolve handles 1..%d eigenpairs at a time" % BLOCK_EIGENSOLVE_MAX)
+    wide = k > 4
     kind, omega = (_lib.GS_MC, 1.0) if smoother == "rb" else (_lib.WJACOBI, 2. / 3.)
     V, F, W = _lib.SLOT_V, _lib.SLOT_F, _lib.SLOT_W
     gen = mass is not None
     plan = get_plan(op, int(lowest), nvec=(5 if gen else 3) * k, mass=mass)
-    plan.set_shifts(np.zeros(plan.nvec))
+    plan.set_shifts(np.zeros(min(plan.nvec, _lib.MAX_VEC)))   # (a plan stores up to 5 k vectors; an entry batches at most MAX_VEC columns)
     n = plan.size(0)
     # what must survive a cycle lives in slot W and in the columns of slot F the cycle does not use (a cycle may exchange
     # the storage of slots V and T, and uses T as its scratch)
@@ -339,34 +346,39 @@ def block_eigensolve(op, k=4, cycles=12, nu=2, lowest=8, smoother="rb", seed=0, 
         plan.upload(0, W, j, rng.random_sample(n) if guesses is None else np.asarray(guesses)[:, j])
 
     def ritz(S, AS, MS, take):
-        """k lowest Ritz pairs of the pencil (S^T A S, S^T M S); blocks of at most four columns per Gram product"""
+        """k lowest Ritz pairs of the pencil (S^T A S, S^T M S): one wide pencil call, or (k <= 4) Gram products of at most
+        four columns each"""
         m = len(S)
-        G, H = np.zeros((m, m)), np.zeros((m, m))
-        for c in range(0, m, 4):
-            G[:, c:c + 4] = plan.block_gram(0, S, MS[c:c + 4])
-            H[:, c:c + 4] = plan.block_gram(0, S, AS[c:c + 4])
+        if wide:
+            H, G = plan.block_pencil(0, S, AS, MS if gen else None)
+        else:
+            G, H = np.zeros((m, m)), np.zeros((m, m))
+            for c in range(0, m, 4):
+                G[:, c:c + 4] = plan.block_gram(0, S, MS[c:c + 4])
+                H[:, c:c + 4] = plan.block_gram(0, S, AS[c:c + 4])
         G, H = 0.5 * (G + G.T), 0.5 * (H + H.T)
         d = 1.0 / np.sqrt(np.diag(G))                   # (scaling only: the pencil's eigenvectors are rescaled back)
         evals, evecs = scipy.linalg.eigh(H * np.outer(d, d), G * np.outer(d, d), subset_by_index=[0, take - 1])
         return evals, evecs * d[:, None]
 
+    combine = plan.block_combine_wide if wide else plan.block_combine
     import time
     for j in range(k):
         plan.apply(0, X[j], AX[j])
         if gen:
             plan.apply(0, X[j], MX[j], op=OP_M)
     rho, C = ritz(X, AX, MX, k)
-    plan.block_combine(0, X, X, C)
-    plan.block_combine(0, AX, AX, C)
+    combine(0, X, X, C)
+    combine(0, AX, AX, C)
     if gen:
-        plan.block_combine(0, MX, MX, C)
+        combine(0, MX, MX, C)
     have_p = False
     loop_start = time.perf_counter()
     for _ in range(int(cycles)):
         for j in range(k):
             plan.lincomb(0, [(1.0, AX[j]), (-float(rho[j]), MX[j])], R[j])
         if residuals is not None:
-            residuals.append(np.sqrt(np.diag(plan.block_gram(0, R, R))))
+            residuals.append(np.sqrt(np.diag(plan.block_pencil(0, R, R)[0] if wide else plan.block_gram(0, R, R))))
         plan.vcycle(nu, nu, kind, omega=omega, k=k, nu_coarse=nu, zero_start=True)
         for j in range(k):
             plan.apply(0, Wd[j], AW[j])
@@ -382,13 +394,13 @@ def block_eigensolve(op, k=4, cycles=12, nu=2, lowest=8, smoother="rb", seed=0, 
             S, AS, MS = X + Wd, AX + AW, MX + MW
             rho, C = ritz(S, AS, MS, k)
         # P' = [W, P] C_wp, X' = X C_x + P'  (and the same for their images under A and M): P is overwritten first, X uses the new P
-        plan.block_combine(0, S[k:], P, C[k:])
-        plan.block_combine(0, AS[k:], AP, C[k:])
-        plan.block_combine(0, X + P, X, np.vstack([C[:k], np.eye(k)]))
-        plan.block_combine(0, AX + AP, AX, np.vstack([C[:k], np.eye(k)]))
+        combine(0, S[k:], P, C[k:])
+        combine(0, AS[k:], AP, C[k:])
+        combine(0, X + P, X, np.vstack([C[:k], np.eye(k)]))
+        combine(0, AX + AP, AX, np.vstack([C[:k], np.eye(k)]))
         if gen:
-            plan.block_combine(0, MS[k:], MP, C[k:])
-            plan.block_combine(0, MX + MP, MX, np.vstack([C[:k], np.eye(k)]))
+            combine(0, MS[k:], MP, C[k:])
+            combine(0, MX + MP, MX, np.vstack([C[:k], np.eye(k)]))
         have_p = bool(use_p)
         if history is not None:
             history.append(np.array(rho))

@@ -315,6 +315,31 @@ class Plan:
                                              (ctypes.c_int * nout)(*[v[0] for v in outputs]), (ctypes.c_int * nout)(*[v[1] for v in outputs]),
                                              _lib.as_dp(c), stream))
 
+    def block_pencil(self, level, s, a_s, m_s=None, stream=None):
+        """(H, G) = (S^T AS, S^T MS) for lists of (slot, vec) pairs of equal length m <= 48 (m_s=None: M = I, G = S^T S): every
+        vector read once in one pass on the matrix cores (mgcmt_block_pencil); full m x m matrices; synchronises."""
+        m = len(s)
+        if len(a_s) != m or (m_s is not None and len(m_s) != m):
+            raise ValueError("block_pencil: S, AS and MS name the same number of vectors")
+
+        def ints(vs, which):
+            return (ctypes.c_int * m)(*[v[which] for v in vs])
+        H, G = np.zeros((m, m)), np.zeros((m, m))
+        check(_lib.lib().mgcmt_block_pencil(self._h, level, m, ints(s, 0), ints(s, 1), ints(a_s, 0), ints(a_s, 1),
+                                            None if m_s is None else ints(m_s, 0), None if m_s is None else ints(m_s, 1),
+                                            _lib.as_dp(H), _lib.as_dp(G), stream))
+        return H, G
+
+    def block_combine_wide(self, level, inputs, outputs, coeffs, stream=None):
+        """outputs[j] <- sum_i coeffs[i, j] * inputs[i] ((slot, vec) pairs; <= 48 inputs, <= 16 distinct outputs; an output
+        may be one of the inputs)."""
+        nin, nout = len(inputs), len(outputs)
+        c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.float64).reshape(nin, nout))
+        check(_lib.lib().mgcmt_block_combine_wide(self._h, level, nin, (ctypes.c_int * nin)(*[v[0] for v in inputs]),
+                                                  (ctypes.c_int * nin)(*[v[1] for v in inputs]), nout,
+                                                  (ctypes.c_int * nout)(*[v[0] for v in outputs]),
+                                                  (ctypes.c_int * nout)(*[v[1] for v in outputs]), _lib.as_dp(c), stream))
+
     def axpy(self, level, alpha, x, y, stream=None):
         check(_lib.lib().mgcmt_axpy(self._h, level, c_double(alpha), x[0], x[1], y[0], y[1], stream))
 

@@ -618,7 +618,7 @@ class MGCMTSolver:
         if opA.dimension == "3d" and lowest > 16:
             raise ValueError("nmin=%d: on 3-D grids the coarsest level of the cycle has at most 16^3 points (nmin <= 16)" % int(nmin))
         plan = get_plan(opA, lowest, nvec=max(self._RQ_REGS, nv), mass=self._mass_operator(M, opA))
-        plan.set_shifts(np.zeros(plan.nvec))
+        plan.set_shifts(np.zeros(min(plan.nvec, _lib.MAX_VEC)))   # (a cached plan may store more vectors than an entry batches)
         for i in range(nv):
             plan.upload(0, SLOT_W, i, k0[:, i])
         self._rqmg2_levels(plan, 0, nv, int(nu1), int(nu2), bool(repaired))

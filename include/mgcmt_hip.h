@@ -158,6 +158,22 @@ int mgcmt_plan_create3d_mass(const mgcmt_plan3d_desc* desc, int32_t m_nterms, co
  * mgcmt_rqmin / mgcmt_rq_line_step / mgcmt_vcycle_rqmg, mgcmt_ritz_pair, mgcmt_rayleigh_residual, mgcmt_comm_init /
  * mgcmt_comm_init_external and mgcmt_sharded_vcycle. */
 int mgcmt_plan_create_pot(const mgcmt_plan_desc* desc, const double* point_diag, mgcmt_plan** out);
+/* A 2-D plan whose operator carries per-point bonds as well: a symmetric 5-point matrix with ANY coefficients,
+ *     A = sum_m X_m (x) Y_m + diag(point_diag) + B(east, south)  - shift * I,
+ * east[i * g + j] is added to the two entries between the points (i, j) and (i, j + 1), south[i * g + j] to those between
+ * (i, j) and (i + 1, j) (g x g numbers each, on the host): H = -div(w grad) + V with a position-dependent inverse effective
+ * mass w(x, y) (BenDaniel-Duke), the Kronecker terms carrying a reference mass and the bonds the deviations.  The last
+ * column of east and the last row of south point outside the grid and must be zero (MGCMT_ERR_INVALID otherwise).  desc and
+ * the refusals are mgcmt_plan_create_pot's (dim = 2, no mass operator, no row strip; the entries listed there return
+ * MGCMT_ERR_UNSUPPORTED on such a plan too).  The Galerkin levels are the same nine planes per level as for a point diagonal.
+ * Level 0 (MGCMT_OPK_POINT_BONDS) keeps three planes D, E, S and runs kernels of its own (csrc/kernels_bonds.hip): where its
+ * Kronecker part is a constant 5-point operator and it has at least 128 columns, a row march with 16-byte accesses —
+ * the red-black sweep as two parity stages and residual + restriction in one pass —, otherwise one thread per point
+ * (csrc/kernels_pointwise.hip), as for the weighted-Jacobi sweep and mgcmt_apply, whose marching forms measured level with
+ * the flat ones.  The environment variable MGCMT_BONDS_MARCH, read at creation, overrides that: 1 = every pass marches, 0 =
+ * none does.  Both forms give the same bits.  The fused row-streaming passes do not take such a level (mgcmt_fused_max_sweeps: 0).
+ * mgcmt_plan_get_point_stencil(level 0) returns the three planes D, E, S, rows x cols numbers each. */
+int mgcmt_plan_create_bonds(const mgcmt_plan_desc* desc, const double* point_diag, const double* east, const double* south, mgcmt_plan** out);
 /* host copy of the per-point part of `level` of such a plan: level 0 rows x cols numbers (point_diag); a level below nine
  * planes of rows x cols, plane 3 a + b = the coefficient of v(i + a - 1, j + b - 1) in row (i, j), zero towards points
  * outside the grid.  The level's matrix is the one assembled from mgcmt_plan_get_factors plus these. */
@@ -353,6 +369,7 @@ int mgcmt_fused_max_recompute(const mgcmt_plan* plan, int level, int kind, int n
 #define MGCMT_OPK_NINE_VAR 4
 #define MGCMT_OPK_POINT_DIAG 5
 #define MGCMT_OPK_NINE_POINT 6
+#define MGCMT_OPK_POINT_BONDS 7 /* level 0 of mgcmt_plan_create_bonds: the Kronecker terms plus a per-point diagonal and bonds */
 int mgcmt_level_operator_kind(const mgcmt_plan* plan, int level, int* kind);
 
 /* ---- multi-GPU: row strips with neighbour halo exchange --------------------------------------------

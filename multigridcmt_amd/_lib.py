@@ -70,6 +70,7 @@ SHARDED_V_HALO_VALID, SHARDED_F_HALO_VALID, SHARDED_GRAM_SCHMIDT = 1, 2, 4
 CYCLE_GRAM_SCHMIDT, CYCLE_ZERO_START = 1, 2    # cycle_flags of mgcmt_vcycle
 OPK_GENERAL, OPK_FIVE_POINT, OPK_FIVE_DIAG, OPK_NINE_CONST, OPK_NINE_VAR = 0, 1, 2, 3, 4    # mgcmt_level_operator_kind
 OPK_POINT_DIAG, OPK_NINE_POINT = 5, 6          # ... on a plan with a point diagonal (mgcmt_plan_create_pot)
+OPK_POINT_BONDS = 7                            # ... level 0 of a plan with per-point bonds (mgcmt_plan_create_bonds)
 # mgcmt_plan3d_level_path: general terms, constant 7-point, constant 7-point + point diagonal, Kronecker terms + 27 planes
 PATH3D_GENERAL, PATH3D_SEVEN, PATH3D_SEVEN_POINT, PATH3D_PLANES = 0, 1, 2, 3
 PATH3D_GENERAL_POINT = 4        # ... general terms + point diagonal (a fine level whose factors are not Toeplitz)
@@ -84,6 +85,7 @@ _SIGNATURES = {
     "mgcmt_plan_create3d": (c_int, [POINTER(Plan3dDesc), POINTER(c_void_p)]),
     "mgcmt_plan_create3d_mass": (c_int, [POINTER(Plan3dDesc), c_int32, _dp, _dp, _dp, POINTER(c_void_p)]),
     "mgcmt_plan_create_pot": (c_int, [POINTER(PlanDesc), _dp, POINTER(c_void_p)]),
+    "mgcmt_plan_create_bonds": (c_int, [POINTER(PlanDesc), _dp, _dp, _dp, POINTER(c_void_p)]),
     "mgcmt_plan_create3d_pot": (c_int, [POINTER(Plan3dDesc), _dp, POINTER(c_void_p)]),
     "mgcmt_plan3d_level_path": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int)]),
     "mgcmt_plan_get_point_stencil": (c_int, [c_void_p, c_int, _dp, c_int64]),

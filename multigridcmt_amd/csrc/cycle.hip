@@ -152,9 +152,15 @@ int mgcmt::smooth_impl(mgcmt_plan* p, int l, int kind, int nu, double omega, int
     }
     case MGCMT_GS_MC: {
       static const int order[4][2] = {{0, 1}, {1, 0}, {0, 0}, {1, 1}};
-      for (int it = 0; it < nu; ++it)
+      for (int it = 0; it < nu; ++it) {
+        // a level with bonds on the marching kernels: the colours (0,1), (1,0) are one parity stage, (0,0), (1,1) the other
+        if (launch_bonds_parity(s, g, op, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->d_shifts, omega, 1, k)) {
+          launch_bonds_parity(s, g, op, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->d_shifts, omega, 0, k);
+          continue;
+        }
         for (int c = 0; c < 4; ++c)
           launch_mc_colour(s, g, op, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->d_shifts, omega, order[c][0], order[c][1], k);
+      }
       break;
     }
     case MGCMT_GS_LEX:
@@ -180,6 +186,12 @@ int mgcmt::smooth_impl(mgcmt_plan* p, int l, int kind, int nu, double omega, int
 
 namespace {
 
+// level l and the one below halve exactly, as the one-pass residual + restriction of a level with bonds assumes
+bool bonds_restrict_ok(const mgcmt_plan* p, int l) {
+  const Level &F = p->levels[l], &C = p->levels[l + 1];
+  return p->dim == 2 && F.dA.k.point == 3 && C.nr * 2 == F.nr && C.gc * 2 == F.gc;
+}
+
 int residual_restrict_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {
   if (l + 1 >= (int)p->levels.size()) return fail(MGCMT_ERR_INVALID, "no coarser level");
   MG_TRY(ensure_slot(p, l, MGCMT_SLOT_V));
@@ -192,6 +204,10 @@ int residual_restrict_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {
                               p->kvec(l + 1, MGCMT_SLOT_V), p->d_shifts, k);
     return post_launch();
   }
+  // a level with bonds on the marching kernels: one pass, F[l+1] and V[l+1] = 0 written, no fine residual stored
+  if (bonds_restrict_ok(p, l) && launch_bonds_residual_restrict(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F),
+                                                                p->kvec(l + 1, MGCMT_SLOT_F), p->kvec(l + 1, MGCMT_SLOT_V), p->d_shifts, k))
+    return post_launch();
   launch_residual(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, k);
   launch_restrict(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l, MGCMT_SLOT_T), p->kvec(l + 1, MGCMT_SLOT_F), k);
   for (int q = 0; q < k; ++q) launch_fill(s, p->kvec(l + 1, MGCMT_SLOT_V, q).p, p->interior(l + 1), 0.0);
@@ -300,6 +316,10 @@ int down_leg(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, bool z
     return post_launch();
   }
   MG_TRY(smooth_impl(p, l, kind, nu, omega, k, s));
+  // (V[l+1] is cleared by the level below, which starts from "zero, uncleared")
+  if (bonds_restrict_ok(p, l) && launch_bonds_residual_restrict(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F),
+                                                                p->kvec(l + 1, MGCMT_SLOT_F), KVec{nullptr, 0}, p->d_shifts, k))
+    return post_launch();
   launch_residual(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, k);
   launch_restrict(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l, MGCMT_SLOT_T), p->kvec(l + 1, MGCMT_SLOT_F), k);
   return post_launch();

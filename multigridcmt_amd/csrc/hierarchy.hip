@@ -286,16 +286,40 @@ struct PlanSpec {
   int64_t row_begin, row_end;  // a 2-D plan's rows of level 0, (0, 0) = all; ignored otherwise
   int strip_levels;
   const double* point_diag = nullptr;  // g x g (2-D, mgcmt_plan_create_pot) or g^3 (3-D, mgcmt_plan_create3d_pot) numbers added to the diagonal of A, host
+  const double* point_east = nullptr;  // 2-D, mgcmt_plan_create_bonds: g x g numbers each, added to the entries between (i, j) and
+  const double* point_south = nullptr;  // (i, j + 1) / (i + 1, j); both or neither
 };
 
 // The per-point part of A on every level (kernels_pointwise.hip): the diagonal D on level 0 in the level's padded row
 // layout (zero halo rows), below it the nine planes of R D P, R (R D P) P, ... formed on the device, one launch per level.
 // The Kronecker part's operators (upload_op) are in place; this adds the pointers to them.
-int build_point_part(mgcmt_plan* p, const double* point_diag) {
+// With bonds (east, south: mgcmt_plan_create_bonds) level 0 holds three such planes — D, E, S, each with its zero halo
+// rows — and KOp::point = 3; their Galerkin product is the same nine planes, so the levels below are what they always were.
+int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east, const double* south) {
+  // which passes of the fine level of a plan with bonds march (KOp::pmarch; kernels_bonds.hip).  Unset: those that measured
+  // faster than their flat form at 8192^2 — the parity stages and residual + restriction (bit 0); the weighted-Jacobi sweep
+  // and the applied operator measured level with it and stay flat.  "1": every pass (bit 1 as well); "0": none (A/B tests).
+  const char* e = getenv("MGCMT_BONDS_MARCH");
+  const int march = !e || !e[0] ? 1 : e[0] == '0' ? 0 : 3;
   for (size_t l = 0; l < p->levels.size(); ++l) {
     Level& L = p->levels[l];
     KOp& k = L.dA.k;
     double* q = nullptr;
+    if (l == 0 && east) {
+      const size_t padded = (size_t)(L.nr + 2 * L.halo) * L.gc, rows = (size_t)L.nr * L.gc, first = (size_t)L.halo * L.gc;
+      MG_HIP(hipMalloc((void**)&q, 3 * padded * sizeof(double)));
+      L.dA.owned.push_back(q);
+      MG_HIP(hipMemset(q, 0, 3 * padded * sizeof(double)));
+      MG_HIP(hipMemcpy(q + first, point_diag, rows * sizeof(double), hipMemcpyHostToDevice));
+      MG_HIP(hipMemcpy(q + padded + first, east, rows * sizeof(double), hipMemcpyHostToDevice));
+      MG_HIP(hipMemcpy(q + 2 * padded + first, south, rows * sizeof(double), hipMemcpyHostToDevice));
+      k.point = 3;
+      k.pmarch = march;
+      k.pg = q + first;
+      k.pld = L.gc;
+      k.pplane = (long)padded;
+      continue;
+    }
     if (l == 0) {
       const size_t padded = (size_t)(L.nr + 2 * L.halo) * L.gc;
       MG_HIP(hipMalloc((void**)&q, padded * sizeof(double)));
@@ -312,7 +336,7 @@ int build_point_part(mgcmt_plan* p, const double* point_diag) {
     const KOp& kf = F.dA.k;
     MG_HIP(hipMalloc((void**)&q, (size_t)9 * L.nr * L.gc * sizeof(double)));
     L.dA.owned.push_back(q);
-    launch_point_coarsen(nullptr, F.nr, F.gc, kf.pg, kf.point == 1 ? 1 : 9, kf.pld, kf.pplane, q, L.gc, L.nr * L.gc);
+    launch_point_coarsen(nullptr, F.nr, F.gc, kf.pg, kf.point == 1 ? 1 : kf.point == 3 ? 3 : 9, kf.pld, kf.pplane, q, L.gc, L.nr * L.gc);
     MG_TRY(post_launch());
     k.point = 2;
     k.pg = q;
@@ -457,7 +481,7 @@ int build_plan(const PlanSpec& d, mgcmt_plan** out) {
     }
   }
   if (d.point_diag) {
-    const int rc = d.dim == 3 ? build_point_part3(p, d.point_diag) : build_point_part(p, d.point_diag);
+    const int rc = d.dim == 3 ? build_point_part3(p, d.point_diag) : build_point_part(p, d.point_diag, d.point_east, d.point_south);
     if (rc != MGCMT_OK) {
       mgcmt_plan_destroy(p);
       return rc;
@@ -499,6 +523,25 @@ int mgcmt_plan_create_pot(const mgcmt_plan_desc* d, const double* point_diag, mg
   return build_plan(spec, out);
 }
 
+int mgcmt_plan_create_bonds(const mgcmt_plan_desc* d, const double* point_diag, const double* east, const double* south, mgcmt_plan** out) {
+  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!point_diag || !east || !south) return fail(MGCMT_ERR_INVALID, "null point diagonal or bond array");
+  if (d->dim != 2) return fail(MGCMT_ERR_INVALID, "a point diagonal with bonds needs a 2-D plan (dim = 2)");
+  if (d->m_nterms != 0) return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal takes no mass operator (the Rayleigh-quotient entries do not run on it)");
+  if (!((d->row_begin == 0 && d->row_end == 0) || (d->row_begin == 0 && d->row_end == d->g)))
+    return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal is a whole grid (no row strips)");
+  if (d->g >= 1)
+    for (int64_t i = 0; i < d->g; ++i)
+      if (east[i * d->g + d->g - 1] != 0.0 || south[(d->g - 1) * d->g + i] != 0.0)
+        return fail(MGCMT_ERR_INVALID, "bonds towards points outside the grid (the last column of east, the last row of south) must be zero");
+  PlanSpec spec{2, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->xfac, d->yfac, nullptr}, {nullptr, nullptr, nullptr}, 0, 0, 0};
+  spec.point_diag = point_diag;
+  spec.point_east = east;
+  spec.point_south = south;
+  return build_plan(spec, out);
+}
+
 int mgcmt_plan_get_point_stencil(const mgcmt_plan* p, int l, double* out, int64_t capacity) {
   MG_TRY(check_level(p, l));
   if (!p->has_point) return fail(MGCMT_ERR_INVALID, "plan has no point diagonal");
@@ -511,8 +554,12 @@ int mgcmt_plan_get_point_stencil(const mgcmt_plan* p, int l, double* out, int64_
     return MGCMT_OK;
   }
   const KOp& k = L.dA.k;
-  const int64_t plane = L.nr * L.gc, need = k.point == 1 ? plane : 9 * plane;
+  const int64_t plane = L.nr * L.gc, need = k.point == 1 ? plane : k.point == 3 ? 3 * plane : 9 * plane;
   if (!out || capacity < need) return fail(MGCMT_ERR_INVALID, "point stencil buffer too small");
+  if (k.point == 3) {  // D, E, S: the interior rows of each padded plane
+    for (int a = 0; a < 3; ++a) MG_HIP(hipMemcpy(out + a * plane, k.pg + a * k.pplane, (size_t)plane * sizeof(double), hipMemcpyDeviceToHost));
+    return MGCMT_OK;
+  }
   MG_HIP(hipMemcpy(out, k.pg, (size_t)need * sizeof(double), hipMemcpyDeviceToHost));  // (level 0: the interior rows are contiguous)
   return MGCMT_OK;
 }
@@ -633,7 +680,7 @@ int mgcmt_level_operator_kind(const mgcmt_plan* p, int l, int* kind) {
   if (!kind) return fail(MGCMT_ERR_INVALID, "null output");
   const KOp& k = p->levels[l].dA.k;
   if (k.point) {
-    *kind = k.point == 1 ? MGCMT_OPK_POINT_DIAG : MGCMT_OPK_NINE_POINT;
+    *kind = k.point == 1 ? MGCMT_OPK_POINT_DIAG : k.point == 3 ? MGCMT_OPK_POINT_BONDS : MGCMT_OPK_NINE_POINT;
     return MGCMT_OK;
   }
   *kind = k.five_point ? MGCMT_OPK_FIVE_POINT : k.five_diag ? MGCMT_OPK_FIVE_DIAG : k.nine_const ? MGCMT_OPK_NINE_CONST : k.nine_var ? MGCMT_OPK_NINE_VAR : MGCMT_OPK_GENERAL;

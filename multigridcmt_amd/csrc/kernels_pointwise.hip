@@ -12,6 +12,7 @@
 // with the per-point part evaluated beside the Kronecker terms — and the per-point entries of the coarsest level's band
 // matrix.  They run the variable 9-point levels of a cycle and are the A/B reference (MGCMT_OPT_FUSED = 0) of the fused
 // pass of the fine level (Op5P, fused_kernel.h), whose bits they reproduce.  Restriction and prolongation do not see the operator.
+#include "bonds_point.h"
 #include "fused_kernel.h"
 #include "mgcmt_internal.h"
 
@@ -39,8 +40,25 @@ __device__ __forceinline__ PointOp eval_five_diag(const KOp& op, const double* _
   return r;
 }
 
-// Any other level: the Kronecker terms and the per-point part (nine planes of G, or D) evaluated from ONE set of
-// neighbour registers, rows north to south.
+// Fine level of a plan with per-point bonds (point == 3): constant 5-point Kronecker part plus the planes D, E, S.  The
+// expressions are bonds_point.h's, which the marching kernels (kernels_bonds.hip) share: the same bits in either form.
+// Row -1 of the plane S is a halo row of zeros; column -1 is predicated.
+__device__ __forceinline__ PointOp eval_five_bonds(const KOp& op, const double* __restrict__ v, long nc, long i, long j, double mu) {
+  const double* c = v + i * nc + j;
+  const bool hw = j > 0, he = j + 1 < nc;
+  const double w = hw ? c[-1] : 0.0, e = he ? c[1] : 0.0;
+  const double* __restrict__ g = op.pg + i * op.pld + j;
+  const double* __restrict__ ge = g + op.pplane;
+  const double* __restrict__ gs = g + 2 * op.pplane;
+  PointOp r;
+  r.off = bonds::neighbour_sum(op.cw, op.cn, hw ? ge[-1] : 0.0, ge[0], gs[-op.pld], gs[0], w, e, c[-nc], c[nc]);
+  r.dg = bonds::diagonal(op.c0 - mu, g[0]);
+  r.inv = fused::fast_reciprocal(r.dg);
+  return r;
+}
+
+// Any other level: the Kronecker terms and the per-point part (nine planes of G, or D, or D with the bonds E, S)
+// evaluated from ONE set of neighbour registers, rows north to south.
 __device__ __forceinline__ PointOp eval_general(const KOp& op, const double* __restrict__ v, long nc, long i, long j, double mu) {
   const double* c = v + i * nc + j;
   const bool hw = j > 0, he = j + 1 < nc;
@@ -63,6 +81,11 @@ __device__ __forceinline__ PointOp eval_general(const KOp& op, const double* __r
   const double* __restrict__ g = op.pg + i * op.pld + j;
   if (op.point == 1) {
     diag += g[0];
+  } else if (op.point == 3) {
+    const double* __restrict__ ge = g + op.pplane;
+    const double* __restrict__ gs = g + 2 * op.pplane;
+    off += bonds::neighbour_sum(0.0, 0.0, hw ? ge[-1] : 0.0, ge[0], gs[-op.pld], gs[0], w, e, n, s);
+    diag += g[0];
   } else {
     const long pl = op.pplane;
     const double rn = g[0] * nw + g[pl] * n + g[2 * pl] * ne;
@@ -79,6 +102,7 @@ __device__ __forceinline__ PointOp eval_general(const KOp& op, const double* __r
 }
 
 __device__ __forceinline__ PointOp eval_point_pw(const KOp& op, const double* __restrict__ v, long nc, long i, long j, double mu) {
+  if (op.point == 3 && op.five_point) return eval_five_bonds(op, v, nc, i, j, mu);
   return (op.point == 1 && op.five_point) ? eval_five_diag(op, v, nc, i, j, mu) : eval_general(op, v, nc, i, j, mu);
 }
 
@@ -142,6 +166,16 @@ __global__ void k_pw_band_add(KGrid g, KOp op, KBand b) {
     ab[r * b.width + b.kl] += gp[0];
     return;
   }
+  if (op.point == 3) {  // a single-level plan: the diagonal and the four bonds of the row
+    const double* ge = gp + op.pplane;
+    const double* gs = gp + 2 * op.pplane;
+    ab[r * b.width + b.kl] += gp[0];
+    if (j > 0) ab[r * b.width + b.kl - 1] += ge[-1];
+    if (j + 1 < nc) ab[r * b.width + b.kl + 1] += ge[0];
+    if (i > 0) ab[r * b.width + b.kl - nc] += gs[-op.pld];
+    if (i + 1 < g.nr) ab[r * b.width + b.kl + nc] += gs[0];
+    return;
+  }
   for (int di = -1; di <= 1; ++di) {
     const long ii = i + di;
     if (ii < 0 || ii >= g.nr) continue;
@@ -153,7 +187,8 @@ __global__ void k_pw_band_add(KGrid g, KOp op, KBand b) {
   }
 }
 
-// coarse = R G P for the per-point part G of a fnr x fnc level (fp == 9: nine planes; fp == 1: a diagonal), one thread per
+// coarse = R G P for the per-point part G of a fnr x fnc level (fp == 9: nine planes; fp == 1: a diagonal; fp == 3: the
+// planes D, E, S of a level with bonds — west = E(i, j - 1), north = S(i - 1, j), no corner entries), one thread per
 // coarse point (I, J) and all nine of its coefficients.  R1 puts (1/4, 1/2, 1/4) on fine 2I .. 2I + 2 and P1 = 2 R1^T; the
 // last coarse row / column has no fine point 2I + 2 (the one-sided end of MGCMTStencilMaker.py:27-78), which the range
 // checks below are.  Fixed summation order: the result does not depend on the launch geometry.
@@ -178,8 +213,13 @@ __global__ void k_pw_coarsen(long fnr, long fnc, const double* __restrict__ fine
         if (ip < 0 || ip >= fnr || (fp == 1 && a != 1)) continue;
         for (int b = 0; b < 3; ++b) {
           const long jp = j + b - 1;
-          if (jp < 0 || jp >= fnc || (fp == 1 && b != 1)) continue;
-          const double gv = r * (fp == 1 ? fine[i * fld + j] : fine[(3 * a + b) * fplane + i * fld + j]);
+          if (jp < 0 || jp >= fnc || (fp == 1 && b != 1) || (fp == 3 && a != 1 && b != 1)) continue;
+          double fv;
+          if (fp == 1) fv = fine[i * fld + j];
+          else if (fp == 9) fv = fine[(3 * a + b) * fplane + i * fld + j];
+          else if (a == 1) fv = b == 1 ? fine[i * fld + j] : fine[fplane + i * fld + (b == 2 ? j : j - 1)];
+          else fv = fine[2 * fplane + (a == 2 ? i : i - 1) * fld + j];
+          const double gv = r * fv;
           for (int A = 0; A < 3; ++A) {
             const long Ip = I + A - 1, oi = ip - 2 * Ip;
             if (Ip < 0 || Ip >= cnr || oi < 0 || oi > 2) continue;
@@ -204,11 +244,13 @@ inline dim3 grid2d(long nc, long nr, int k, dim3 b) {
 }  // namespace
 
 void launch_point_apply(hipStream_t s, KGrid g, KOp op, KVec src, KVec dst, const double* shifts, int k) {
+  if (launch_bonds_apply(s, g, op, src, dst, shifts, k)) return;  // the marching form of a level with bonds
   const dim3 b(64, 4, 1);
   hipLaunchKernelGGL(k_pw_apply, grid2d(g.nc, g.nr, k, b), b, 0, s, g, op, src, dst, shifts);
 }
 
 void launch_point_wjacobi(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k) {
+  if (launch_bonds_wjacobi(s, g, op, vin, f, vout, shifts, omega, k)) return;
   const dim3 b(64, 4, 1);
   hipLaunchKernelGGL(k_pw_wjacobi, grid2d(g.nc, g.nr, k, b), b, 0, s, g, op, vin, f, vout, shifts, omega);
 }

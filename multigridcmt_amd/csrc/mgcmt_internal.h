@@ -49,8 +49,14 @@ struct KOp {
   // point: a per-point part on top of the Kronecker terms above (mgcmt_plan_create_pot; 2-D, whole grids).  1: a diagonal
   // D(i, j) = pg[i * pld + j] (the fine level, stored in the level's padded row layout); 2: a 9-point stencil G (the
   // Galerkin levels R D P): the coefficient of v(i + a - 1, j + b - 1) in row (i, j) is pg[(3 a + b) * pplane + i * pld + j],
-  // zero towards points outside the grid.  The flags above describe the Kronecker part alone.
-  int point;
+  // zero towards points outside the grid.  3: a diagonal and bonds (mgcmt_plan_create_bonds; the fine level): three planes
+  // in the level's padded row layout, pplane apart — D(i, j) = pg[i * pld + j], E(i, j) = pg[pplane + ...] added to the
+  // entry between (i, j) and (i, j + 1), S(i, j) = pg[2 * pplane + ...] to the one between (i, j) and (i + 1, j); the
+  // halo rows of every plane are zero, so S(-1, j) reads an exact zero; E(i, nc - 1) = S(nr - 1, j) = 0.  pmarch: which
+  // passes of such a level take the marching kernels where its size allows — bit 0 the parity stages and residual +
+  // restriction, bit 1 the Jacobi sweep and the applied operator (MGCMT_BONDS_MARCH, read at plan creation: hierarchy.hip).
+  // The flags above describe the Kronecker part alone.
+  int point, pmarch;
   const double* pg;
   long pld, pplane;
 };
@@ -113,6 +119,16 @@ struct KBand;
 void launch_point_band_add(hipStream_t s, KGrid g, KOp op, const KBand& b, int k);
 void launch_point_coarsen(hipStream_t s, long fnr, long fnc, const double* fine, int fine_planes, long fld, long fplane, double* coarse, long cld,
                           long cplane);
+// a level with per-point bonds (op.point == 3) as a row march (kernels_bonds.hip; bonds_marching: a constant 5-point
+// Kronecker part, at least 128 columns, even sizes, marching not switched off).  Every launcher returns false — nothing
+// launched — where the level or the vectors' alignment rule the march out; the flat kernels above take the level then.
+// parity: 1 = the colours (0,1), (1,0) of the multicolour order, 0 = (0,0), (1,1) — two launches are one sweep.
+// launch_bonds_residual_restrict: fc <- R (f - (A - mu) v) in one pass (the fine residual is not stored); vc.p != null: vc <- 0.
+bool bonds_marching(const KGrid& g, const KOp& op);
+bool launch_bonds_apply(hipStream_t s, KGrid g, KOp op, KVec src, KVec dst, const double* shifts, int k);
+bool launch_bonds_wjacobi(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
+bool launch_bonds_parity(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, const double* shifts, double omega, int parity, int k);
+bool launch_bonds_residual_restrict(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k);
 // generalised lexicographic sweep (in place):
 //   v_k <- (alpha d_k v_k + beta f_k - wU sum_{j>k} a_kj v_j - wL sum_{j<k} a_kj v_j^new) / d_k
 void launch_lex_sweep(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, const double* shifts, double alpha, double beta,

@@ -47,12 +47,35 @@ class StructuredOperator:
     ``point_diagonal`` (2-D and 3-D): a (g, g) array added to the diagonal, index [i, j] = row-major point i*g + j — an
     arbitrary potential V(x, y) on top of the Kronecker terms (``potential_operator``, ``recognise_potential``); in 3-D a
     (g, g, g) array, index [z, y, x] = point z*g^2 + y*g + x.
+
+    ``point_bonds`` (2-D only): a pair (E, S) of (g, g) arrays — E[i, j] is added to the two matrix entries between the
+    points (i, j) and (i, j + 1), S[i, j] to those between (i, j) and (i + 1, j), on top of the Kronecker terms: a symmetric
+    5-point operator with ANY coefficients, e.g. -div(w grad) + V with a position-dependent inverse effective mass w
+    (``variable_mass_operator``, ``recognise_five_point``).  E[:, g-1] and S[g-1, :] point outside the grid and must be zero.
+    An operator with bonds always has a ``point_diagonal`` (zeros if none was given).
     """
 
-    def __init__(self, dimension, g, terms, point_diagonal=None):
+    def __init__(self, dimension, g, terms, point_diagonal=None, point_bonds=None):
         self.dimension = dimension
         self.g = int(g)
         self.point_diagonal = None
+        self.point_bonds = None
+        if point_bonds is not None:
+            if dimension != "2d":
+                raise ValueError("point_bonds is a property of 2-D operators")
+            if len(point_bonds) != 2:
+                raise ValueError("point_bonds is a pair (E, S) of g x g arrays")
+            bonds = []
+            for name, b in zip(("E", "S"), point_bonds):
+                b = np.array(b, dtype=np.float64, order="C")
+                if b.size != self.g * self.g:
+                    raise ValueError("point_bonds %s must hold g x g = %d x %d values, not %r" % (name, self.g, self.g, b.shape))
+                bonds.append(b.reshape(self.g, self.g))
+            if bonds[0][:, -1].any() or bonds[1][-1, :].any():
+                raise ValueError("point_bonds: E[:, g-1] and S[g-1, :] are bonds towards points outside the grid and must be zero")
+            self.point_bonds = tuple(bonds)
+            if point_diagonal is None:
+                point_diagonal = np.zeros((self.g, self.g))
         if point_diagonal is not None:
             if dimension not in ("2d", "3d"):
                 raise ValueError("point_diagonal is a property of 2-D and 3-D operators")
@@ -88,7 +111,8 @@ class StructuredOperator:
             return StructuredOperator("3d", self.g, [(x, y, z * c) for x, y, z in self.terms],
                                       point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c)
         return StructuredOperator("2d", self.g, [(x, y * c) for x, y in self.terms],
-                                  point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c)
+                                  point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c,
+                                  point_bonds=None if self.point_bonds is None else tuple(b * c for b in self.point_bonds))
 
     def __mul__(self, other):
         if np.isscalar(other):
@@ -120,7 +144,7 @@ class StructuredOperator:
             terms[0][1][1] -= mu
         else:
             terms.append((tri_identity(self.g), tri_identity(self.g) * (-float(mu))))
-        return StructuredOperator(self.dimension, self.g, terms, point_diagonal=self.point_diagonal)
+        return StructuredOperator(self.dimension, self.g, terms, point_diagonal=self.point_diagonal, point_bonds=self.point_bonds)
 
     # -- views ----------------------------------------------------------------------------------
     def diagonal(self):
@@ -146,6 +170,8 @@ class StructuredOperator:
         A = sum(sp.kron(tri_to_sparse(x), tri_to_sparse(y), format="csr") for x, y in self.terms).tocsr()
         if self.point_diagonal is not None:
             A = (A + sp.diags(self.point_diagonal.reshape(-1), 0, format="csr")).tocsr()
+        if self.point_bonds is not None:
+            A = (A + _bonds_to_sparse(*self.point_bonds)).tocsr()
         return A
 
     def tocsc(self):
@@ -179,8 +205,21 @@ class StructuredOperator:
             if self.point_diagonal is not None:
                 h.update(b"point_diagonal")
                 h.update(self.point_diagonal.tobytes())
+            if self.point_bonds is not None:
+                for name, b in zip((b"point_bonds_east", b"point_bonds_south"), self.point_bonds):
+                    h.update(name)
+                    h.update(b.tobytes())
             self._fingerprint = h.hexdigest()
         return self._fingerprint
+
+
+def _bonds_to_sparse(E, S):
+    """The symmetric matrix with E[i, j] between (i, j) and (i, j + 1) and S[i, j] between (i, j) and (i + 1, j) (zero diagonal)."""
+    g = E.shape[0]
+    n = g * g
+    e = E.reshape(-1)[:n - 1]                  # (E[:, g-1] = 0: nothing wraps into the next row)
+    s = S.reshape(-1)[:n - g]
+    return sp.diags([s, e, e, s], [-g, -1, 1, g], shape=(n, n), format="csr")
 
 
 def laplacian_operator(n, dimension="1d"):
@@ -285,6 +324,63 @@ def potential_operator(g, V, scale=-1.0 / np.pi ** 2, dimension="2d"):
     return StructuredOperator("2d", g, [(tri_identity(g), L), (L.copy(), tri_identity(g))], point_diagonal=V)
 
 
+def _mean_bond(a, b, mean):
+    if mean == "harmonic":
+        return 2.0 * a * b / (a + b)
+    if mean == "arithmetic":
+        return 0.5 * (a + b)
+    raise ValueError("variable_mass_operator: mean must be 'harmonic' or 'arithmetic', not %r" % (mean,))
+
+
+def variable_mass_operator(g, inv_mass, V=None, scale=-1.0 / np.pi ** 2, mean="harmonic"):
+    """H = scale * div(w grad) + diag(V) on the g x g grid of ``laplacian(g, "2d")`` with a position-dependent inverse
+    effective mass w = inv_mass (a (g, g) array, positive): the BenDaniel-Duke form of the kinetic term across the
+    interfaces of a heterostructure.  Matrix-free.  With t = scale * L[0, 1] the neighbour entry of the uniform operator, the
+    entry between neighbours a, b is t * m(w_a, w_b) — m the harmonic mean 2ab/(a+b) (flux-conserving; the default) or the
+    arithmetic mean — and the diagonal is -t * (the sum of the point's four bond values) + V; a bond towards a ghost point
+    outside the grid takes the point's own w, so w = 1, V = 0 is scale * laplacian(g, "2d") exactly.
+
+    The Kronecker terms carry w_ref * scale * Laplacian with w_ref = median(w); ``point_bonds`` and ``point_diagonal`` carry
+    the deviations, so a uniform region stores zeros and level 0 keeps a constant 5-point Kronecker part.  A uniform w
+    returns what ``potential_operator`` / ``laplacian_operator`` (scaled) would return: no bonds."""
+    g = int(g)
+    w = np.ascontiguousarray(inv_mass, dtype=np.float64)
+    if w.size != g * g:
+        raise ValueError("variable_mass_operator: inv_mass must hold g x g = %d x %d values, not %r" % (g, g, w.shape))
+    w = w.reshape(g, g)
+    if not (w > 0).all():
+        raise ValueError("variable_mass_operator: the inverse mass must be positive everywhere")
+    _mean_bond(1.0, 1.0, mean)
+    if V is not None:
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        if V.size != g * g:
+            raise ValueError("variable_mass_operator: V must hold g x g = %d x %d values, not %r" % (g, g, V.shape))
+        V = V.reshape(g, g)
+    w_ref = float(np.median(w))
+    L = tri_laplacian(g) * float(scale)
+    if (w == w_ref).all():
+        Lr = L * w_ref
+        if V is None:
+            return StructuredOperator("2d", g, [(tri_identity(g), Lr), (Lr.copy(), tri_identity(g))])
+        return StructuredOperator("2d", g, [(tri_identity(g), Lr), (Lr.copy(), tri_identity(g))], point_diagonal=V)
+    t = float(L[2, 0])
+    # bond values (multiples of t) towards east / west / south / north; ghosts take the point's own w
+    be, bs = w.copy(), w.copy()
+    be[:, :-1] = _mean_bond(w[:, :-1], w[:, 1:], mean)
+    bs[:-1, :] = _mean_bond(w[:-1, :], w[1:, :], mean)
+    bw, bn = w.copy(), w.copy()
+    bw[:, 1:] = be[:, :-1]
+    bn[1:, :] = bs[:-1, :]
+    E, S = np.zeros((g, g)), np.zeros((g, g))
+    E[:, :-1] = t * be[:, :-1] - t * w_ref
+    S[:-1, :] = t * bs[:-1, :] - t * w_ref
+    Lr = L * w_ref
+    D = -t * (be + bw + bs + bn) - 2.0 * float(Lr[1, 0])
+    if V is not None:
+        D = D + V
+    return StructuredOperator("2d", g, [(tri_identity(g), Lr), (Lr.copy(), tri_identity(g))], point_diagonal=D, point_bonds=(E, S))
+
+
 class UnrecognisedOperator(ValueError):
     pass
 
@@ -385,6 +481,54 @@ def recognise_potential(A, dimension="2d"):
     Y[0], Y[1], Y[2] = w[0], 0.5 * base, e[0]
     X[0], X[1], X[2] = nn[:, 0], base - 0.5 * base, s[:, 0]
     op = StructuredOperator("2d", g, [(tri_identity(g), Y), (X, tri_identity(g))], point_diagonal=d0 - base)
+    if len(_CACHE) > 64:
+        _CACHE.clear()
+    _CACHE[key] = (A, op)
+    return op
+
+
+def recognise_five_point(A):
+    """StructuredOperator for ANY symmetric 5-point matrix on a g x g grid (a Hamiltonian with a position-dependent effective
+    mass assembled as a sparse matrix).  What ``recognise`` or ``recognise_potential`` accepts is returned as they return
+    it; otherwise the median east / south off-diagonal and the median diagonal go into two Toeplitz Kronecker terms — so
+    that a uniform region leaves zeros — and the rest into the operator's ``point_bonds`` and ``point_diagonal``.
+    Unsymmetric matrices and anything wider than the 5-point stencil raise UnrecognisedOperator."""
+    try:
+        return recognise_potential(A, "2d")
+    except UnrecognisedOperator:
+        if isinstance(A, StructuredOperator):
+            raise
+    if not sp.issparse(A):
+        A = sp.csr_matrix(np.asarray(A, dtype=np.float64))
+    key = ("five_point",) + _cache_key(A)
+    hit = _CACHE.get(key)
+    if hit is not None and hit[0] is A:
+        return hit[1]
+    n = A.shape[0]
+    g = int(round(math.sqrt(n)))
+    if A.shape[0] != A.shape[1] or g * g != n or g < 2 or np.iscomplexobj(A):
+        raise UnrecognisedOperator("recognise_five_point: a real square matrix on a g x g grid is needed")
+    M = sp.csr_matrix(A, dtype=np.float64, copy=True)
+    M.eliminate_zeros()
+    d0 = M.diagonal(0).reshape(g, g)
+    e, w, s, nn = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
+    e[:-1], w[1:] = M.diagonal(1), M.diagonal(-1)
+    s[:-g], nn[g:] = M.diagonal(g), M.diagonal(-g)
+    counted = sum(np.count_nonzero(a) for a in (d0, e, w, s, nn))
+    e, w, s, nn = e.reshape(g, g), w.reshape(g, g), s.reshape(g, g), nn.reshape(g, g)
+    if counted != M.nnz or e[:, -1].any() or w[:, 0].any():
+        raise UnrecognisedOperator("2-D operator is not a 5-point matrix: it has entries off the stencil (or across the row ends)")
+    if not (np.array_equal(e[:, :-1], w[:, 1:]) and np.array_equal(s[:-1, :], nn[1:, :])):
+        raise UnrecognisedOperator("2-D 5-point operator is not symmetric: per-point bonds describe symmetric matrices only")
+    base = float(np.median(d0))
+    ce, cs = float(np.median(e[:, :-1])), float(np.median(s[:-1, :]))
+    Y, X = np.zeros((3, g)), np.zeros((3, g))
+    Y[0, 1:], Y[1], Y[2, :-1] = ce, 0.5 * base, ce
+    X[0, 1:], X[1], X[2, :-1] = cs, base - 0.5 * base, cs
+    E, S = np.zeros((g, g)), np.zeros((g, g))
+    E[:, :-1] = e[:, :-1] - ce
+    S[:-1, :] = s[:-1, :] - cs
+    op = StructuredOperator("2d", g, [(tri_identity(g), Y), (X, tri_identity(g))], point_diagonal=d0 - base, point_bonds=(E, S))
     if len(_CACHE) > 64:
         _CACHE.clear()
     _CACHE[key] = (A, op)

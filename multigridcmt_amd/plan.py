@@ -55,7 +55,13 @@ class Plan:
             if row_begin or row_end or strip_levels:
                 raise ValueError("an operator with a point diagonal is not sharded")
             pd = _f64(pd)
-            check(_lib.lib().mgcmt_plan_create_pot(ctypes.byref(desc), as_dp(pd), ctypes.byref(self._h)))
+            bonds = getattr(op, "point_bonds", None)
+            if bonds is not None:
+                # per-point bonds as well (operators.variable_mass_operator): level 0 keeps the planes D, E, S
+                east, south = _f64(bonds[0]), _f64(bonds[1])
+                check(_lib.lib().mgcmt_plan_create_bonds(ctypes.byref(desc), as_dp(pd), as_dp(east), as_dp(south), ctypes.byref(self._h)))
+            else:
+                check(_lib.lib().mgcmt_plan_create_pot(ctypes.byref(desc), as_dp(pd), ctypes.byref(self._h)))
         else:
             check(_lib.lib().mgcmt_plan_create(ctypes.byref(desc), ctypes.byref(self._h)))
         del keep
@@ -133,7 +139,8 @@ class Plan:
     def point_stencil(self, level):
         """Host copy of the per-point part of `level` of a plan whose operator has a point diagonal: level 0 the diagonal,
         array [rows, cols]; below it the 9-point stencil R D P, array [3, 3, rows, cols] — entry [a, b, i, j] is the
-        coefficient of point (i + a - 1, j + b - 1) in row (i, j).  3-D: [g, g, g] on level 0 and the 27-point stencil
+        coefficient of point (i + a - 1, j + b - 1) in row (i, j).  Level 0 of an operator with ``point_bonds``: the three
+        planes D, E, S, array [3, rows, cols].  3-D: [g, g, g] on level 0 and the 27-point stencil
         [3, 3, 3, g_l, g_l, g_l] below — entry [a, b, c, z, y, x] is the coefficient of point (z + a - 1, y + b - 1, x + c - 1)."""
         if self.dim == 3:
             gl = self.g >> level
@@ -141,7 +148,8 @@ class Plan:
             check(_lib.lib().mgcmt_plan_get_point_stencil(self._h, level, as_dp(out), out.size))
             return out
         r, c, _ = self.shapes[level]
-        out = np.zeros((r, c) if level == 0 else (3, 3, r, c))
+        bonds = getattr(self.op, "point_bonds", None) is not None
+        out = np.zeros(((3, r, c) if bonds else (r, c)) if level == 0 else (3, 3, r, c))
         check(_lib.lib().mgcmt_plan_get_point_stencil(self._h, level, as_dp(out), out.size))
         return out
 

@@ -15,7 +15,7 @@ import scipy.sparse as sp
 
 from . import _lib
 from ._lib import GS_LEX, GS_MC, OP_A, OP_M, SLOT_F, SLOT_T, SLOT_V, SLOT_W, SOR_LEX, WJACOBI
-from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, planes_to_csr, recognise, recognise_potential,
+from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, planes_to_csr, recognise, recognise_five_point, recognise_potential,
                         tag_structured)
 from .plan import get_plan
 from .processor import MGCMTProcessor
@@ -61,7 +61,8 @@ def _check_3d_smoother(kind):
 def _recognise_entry(A, dimension):
     """``recognise`` for the 2-D and 3-D entry points: a 5-point (7-point) matrix with an arbitrary diagonal (a Hamiltonian
     with any potential), which ``recognise`` refuses, is mapped by ``recognise_potential`` to an operator with a point
-    diagonal; what that refuses too raises ``recognise``'s error."""
+    diagonal; in 2-D a symmetric 5-point matrix whose off-diagonals vary too (a position-dependent effective mass) is mapped
+    last by ``recognise_five_point`` to an operator with point bonds; what that refuses too raises ``recognise``'s error."""
     try:
         return recognise(A, dimension)
     except UnrecognisedOperator as err:
@@ -69,6 +70,11 @@ def _recognise_entry(A, dimension):
             raise
         try:
             return recognise_potential(A, dimension)
+        except UnrecognisedOperator:
+            if dimension != "2d":
+                raise err
+        try:
+            return recognise_five_point(A)
         except UnrecognisedOperator:
             raise err
 
@@ -252,6 +258,12 @@ class MGCMTSolver:
             # the Kronecker part's level plus the per-point part the library formed: the diagonal on level 0, the 9-point
             # stencil R D P below (a foreign smoother sees the true R A P - mu I)
             gl = plan.g >> level
+            if level == 0 and getattr(plan.op, "point_bonds", None) is not None:
+                G = plan.point_stencil(0)                      # D, E, S: the true matrix with its bonds
+                op = StructuredOperator("2d", gl, terms, point_diagonal=G[0], point_bonds=(G[1], G[2]))
+                if shift:
+                    op = op.shifted(float(shift))
+                return tag_structured(op.tocsr(), op)
             if level == 0:
                 op = StructuredOperator("2d", gl, terms, point_diagonal=plan.point_stencil(0))
                 if shift:

@@ -437,7 +437,8 @@ int mgcmt_sharded_vcycle(mgcmt_plan* plan, mgcmt_plan* coarse, int nu1, int nu2,
  * complex numbers (values = interleaved re, im), cycled as ONE 1-D grid of its full length with the reference's 1-D
  * transfer operators (MGCMTStencilMaker.py:27-78).  The plan builds the Galerkin hierarchy R*A*P (MGCMTSolver.py:318)
  * on the device; vectors are complex (interleaved), slots V, F, T as for mgcmt_plan.  n and lowest are powers of two,
- * lowest <= 64 (the coarsest level is solved by a dense LU with row pivoting, :305-308). */
+ * lowest <= 64 (the coarsest level is solved by a dense LU with row pivoting, :305-308).  Rows need not be sorted, and
+ * stored duplicates of an entry are summed (as scipy treats them): level 0's nnz is the merged count. */
 typedef struct mgcmt_csr_plan mgcmt_csr_plan;
 int mgcmt_csr_plan_create(int device, int64_t n, int64_t lowest, const int64_t* indptr, const int32_t* indices, const double* values,
                           mgcmt_csr_plan** out);

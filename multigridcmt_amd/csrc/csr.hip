@@ -13,8 +13,8 @@
 // Lexicographic sweeps: rows are processed in chunks of C consecutive rows by one workgroup.  C is the largest power of
 // two (<= 1024) for which every row's strictly-lower entries other than k-1 lie BEFORE the row's chunk — true for the
 // block matrices above with C = block size — so that inside a chunk the sweep is the first-order recurrence
-// x_k = p_k + q_k x_{k-1}, solved by a scan over complex affine maps; matrices without that structure get C = 1, the
-// plain sequential sweep.
+// x_k = p_k + q_k x_{k-1}, solved by a scan over complex affine maps; matrices without that structure get C = 2 (inside
+// an aligned pair of rows the only strictly-lower entry is k-1, so every matrix admits it): the sweep pair by pair.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -387,7 +387,8 @@ int check(const mgcmt_csr_plan* p, int level) {
 
 int lex_sweep(mgcmt_csr_plan* p, int l, int slot, double mu, double alpha, double beta, double wU, double wL, hipStream_t s) {
   CsrLevel& L = p->levels[l];
-  hipLaunchKernelGGL(k_csr_lex, dim3(1), dim3(kCsrLexThreads), 0, s, kcsr(L), L.vec[slot], L.vec[MGCMT_SLOT_F], mu, alpha, beta, wU, wL, L.chunk);
+  // (one thread per row of a chunk, in whole waves: a short chunk does not take 1024 threads through every barrier)
+  hipLaunchKernelGGL(k_csr_lex, dim3(1), dim3(std::max(64, L.chunk)), 0, s, kcsr(L), L.vec[slot], L.vec[MGCMT_SLOT_F], mu, alpha, beta, wU, wL, L.chunk);
   return post_launch();
 }
 
@@ -457,21 +458,36 @@ int mgcmt_csr_plan_create(int device, int64_t n, int64_t lowest, const int64_t* 
   std::vector<int> idx(indices, indices + ptr[n]);
   std::vector<cplx> val((size_t)ptr[n]);
   for (long e = 0; e < ptr[n]; ++e) val[e] = cmake(values[2 * e], values[2 * e + 1]);
-  for (long k = 0; k < n; ++k) {
+  // sort every row by column and sum the stored duplicates of an entry (scipy, and so the reference, treats them as
+  // summed; the kernels take "the" diagonal and "the" sub-diagonal of a row)
+  {
+    std::vector<long> mptr(n + 1, 0);
+    long w = 0;  // (w <= e throughout: the merged rows are written in place, behind the read position)
     std::vector<std::pair<int, long>> order;
-    for (long e = ptr[k]; e < ptr[k + 1]; ++e) {
-      if (idx[e] < 0 || idx[e] >= n) return bail(fail(MGCMT_ERR_INVALID, "column index out of range"));
-      order.push_back({idx[e], e});
-    }
-    std::sort(order.begin(), order.end());
-    std::vector<int> ci;
     std::vector<cplx> cv;
-    for (auto& o : order) {
-      ci.push_back(o.first);
-      cv.push_back(val[o.second]);
+    for (long k = 0; k < n; ++k) {
+      order.clear();
+      for (long e = ptr[k]; e < ptr[k + 1]; ++e) {
+        if (idx[e] < 0 || idx[e] >= n) return bail(fail(MGCMT_ERR_INVALID, "column index out of range"));
+        order.push_back({idx[e], e});
+      }
+      std::sort(order.begin(), order.end());
+      cv.clear();
+      for (auto& o : order) cv.push_back(val[o.second]);
+      for (size_t t = 0; t < order.size(); ++t) {
+        if (t > 0 && order[t].first == order[t - 1].first) {
+          val[w - 1] = cmake(val[w - 1].x + cv[t].x, val[w - 1].y + cv[t].y);
+        } else {
+          idx[w] = order[t].first;
+          val[w] = cv[t];
+          ++w;
+        }
+      }
+      mptr[k + 1] = w;
     }
-    std::copy(ci.begin(), ci.end(), idx.begin() + ptr[k]);
-    std::copy(cv.begin(), cv.end(), val.begin() + ptr[k]);
+    ptr = mptr;
+    idx.resize(w);
+    val.resize(w);
   }
   for (int l = 0; l < nlev; ++l) {
     CsrLevel& L = p->levels[l];

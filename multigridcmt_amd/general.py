@@ -26,10 +26,18 @@ def _digest(A):
     return h.digest()
 
 
+def _private_csr(A):
+    """A canonical CSR copy of the caller's matrix: stored duplicates of an entry summed (as scipy and the reference treat
+    them), columns sorted.  The caller's matrix is never modified."""
+    A = sp.csr_matrix(A, copy=True)
+    A.sum_duplicates()
+    A.sort_indices()
+    return A
+
+
 class CsrPlan:
     def __init__(self, A, lowest, device=0):
-        A = sp.csr_matrix(A)
-        A.sort_indices()
+        A = _private_csr(A)
         n = A.shape[0]
         if A.shape[0] != A.shape[1]:
             raise ValueError("operator must be square")
@@ -96,8 +104,7 @@ _MAX_PLANS = 4
 
 def get_csr_plan(A, lowest):
     """A cached device hierarchy for (matrix content, coarsest size)."""
-    A = sp.csr_matrix(A)
-    A.sort_indices()
+    A = _private_csr(A)
     key = (A.shape, A.nnz, _digest(A), int(lowest))
     plan = _PLANS.get(key)
     if plan is not None:

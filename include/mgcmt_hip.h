@@ -39,7 +39,8 @@
  *     levels then minimise with R I P, as the reference does).  The entries with no 3-D form (lexicographic smoothers,
  *     twogrid, ritz_pair, rayleigh_residual, sharding, fused-pass and timing entries) return MGCMT_ERR_UNSUPPORTED on
  *     a 3-D plan.
- *     A 3-D operator may carry an arbitrary diagonal on top of its Kronecker terms (mgcmt_plan_create3d_pot).
+ *     A 3-D operator may carry an arbitrary diagonal on top of its Kronecker terms (mgcmt_plan_create3d_pot), and per-point
+ *     bonds as well: any symmetric 7-point matrix (mgcmt_plan_create3d_bonds).
  */
 #ifndef MGCMT_HIP_H
 #define MGCMT_HIP_H
@@ -193,9 +194,25 @@ int mgcmt_plan_create_bonds(const mgcmt_plan_desc* desc, const double* point_dia
  * mgcmt_plan_get_point_stencil on such a plan: level 0 g^3 numbers; a level below 27 planes of g_l^3, plane 9 a + 3 b + c = the
  * coefficient of v(z + a - 1, y + b - 1, x + c - 1) in row (z, y, x), exactly zero towards points outside the grid. */
 int mgcmt_plan_create3d_pot(const mgcmt_plan3d_desc* desc, const double* point_diag, mgcmt_plan** out);
+/* A 3-D plan whose operator carries per-point bonds as well: a symmetric 7-point matrix with ANY coefficients,
+ *     A = sum_m X_m (x) Y_m (x) Z_m + diag(point_diag) + B(bx, by, bz)  - shift * I,
+ * g^3 numbers each on the host, index [z * g^2 + y * g + x]: bx is added to the two entries between the points (z, y, x) and
+ * (z, y, x + 1), by to those between (z, y, x) and (z, y + 1, x), bz to those between (z, y, x) and (z + 1, y, x) —
+ * H = -div(w grad) + V with a position-dependent inverse effective mass w(x, y, z) (BenDaniel-Duke: a GaAs dot or lens in an
+ * AlGaAs barrier), the Kronecker terms carrying a reference mass and the bonds the deviations.  bx at x = g - 1, by at
+ * y = g - 1 and bz at z = g - 1 point outside the grid and must be zero (MGCMT_ERR_INVALID otherwise).  desc, what runs and
+ * the refusals are mgcmt_plan_create3d_pot's.  The Galerkin levels are the same 27 planes per level as for a point diagonal.
+ * Level 0 keeps four planes D, Bx, By, Bz (32 B per point, about 4 GiB at 512^3) and runs kernels of its own: where its
+ * Kronecker part is a constant 7-point operator and g is a multiple of 64, marching kernels with the four planes as streams
+ * (csrc/kernels_3d_bonds.hip), otherwise — and with MGCMT_3D_POINT_MARCH=0 — one thread per point
+ * (csrc/kernels_3d_point.hip); both forms give the same bits per sweep.  mgcmt_apply runs flat.
+ * mgcmt_plan_get_point_stencil(level 0) returns the four planes D, Bx, By, Bz, g^3 numbers each. */
+int mgcmt_plan_create3d_bonds(const mgcmt_plan3d_desc* desc, const double* point_diag, const double* bx, const double* by, const double* bz,
+                              mgcmt_plan** out);
 /* Which kernels `level` of a 3-D plan runs on.  kind: 0 general Kronecker terms, 1 constant 7-point, 2 constant 7-point plus a
  * point diagonal, 3 Kronecker terms plus 27 planes, 4 general Kronecker terms plus a point diagonal (a fine level whose
- * factors are not Toeplitz: flat kernels); marching: whether the level's smoothing and transfer passes take the
+ * factors are not Toeplitz: flat kernels), 5 constant 7-point plus a point diagonal and bonds, 6 general Kronecker terms
+ * plus a point diagonal and bonds (flat kernels); marching: whether the level's smoothing and transfer passes take the
  * marching kernels (1) or the flat ones (0).  Either output may be NULL.  (mgcmt_level_operator_kind describes 1-D / 2-D plans.) */
 int mgcmt_plan3d_level_path(const mgcmt_plan* plan, int level, int* kind, int* marching);
 int mgcmt_plan_get_point_stencil(const mgcmt_plan* plan, int level, double* out, int64_t capacity);

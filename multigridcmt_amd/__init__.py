@@ -5,7 +5,7 @@ kernels for gfx950 behind the C-ABI of include/mgcmt_hip.h (libmgcmt_hip.so, bou
 """
 from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator,
                         potential_operator, potential_well_operator, recognise, recognise_five_point, recognise_potential,
-                        variable_mass_operator)
+                        recognise_seven_point, variable_mass_operator)
 from .plan import Plan, get_plan, release_plans
 from .processor import MGCMTProcessor
 from .solver import MGCMTSolver
@@ -13,4 +13,4 @@ from .stencil_maker import MGCMTStencilMaker
 
 __all__ = ["MGCMTSolver", "MGCMTStencilMaker", "MGCMTProcessor", "StructuredOperator", "UnrecognisedOperator",
            "laplacian_operator", "identity_operator", "potential_well_operator", "potential_operator", "recognise",
-           "recognise_potential", "variable_mass_operator", "recognise_five_point", "Plan", "get_plan", "release_plans"]
+           "recognise_potential", "variable_mass_operator", "recognise_five_point", "recognise_seven_point", "Plan", "get_plan", "release_plans"]

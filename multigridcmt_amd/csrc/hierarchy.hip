@@ -288,6 +288,7 @@ struct PlanSpec {
   const double* point_diag = nullptr;  // g x g (2-D, mgcmt_plan_create_pot) or g^3 (3-D, mgcmt_plan_create3d_pot) numbers added to the diagonal of A, host
   const double* point_east = nullptr;  // 2-D, mgcmt_plan_create_bonds: g x g numbers each, added to the entries between (i, j) and
   const double* point_south = nullptr;  // (i, j + 1) / (i + 1, j); both or neither
+  const double* point_bonds3[3] = {nullptr, nullptr, nullptr};  // 3-D, mgcmt_plan_create3d_bonds: Bx, By, Bz, g^3 numbers each; all or none
 };
 
 // The per-point part of A on every level (kernels_pointwise.hip): the diagonal D on level 0 in the level's padded row
@@ -350,18 +351,30 @@ int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east
 
 // The same on a 3-D plan (kernels_3d_point.hip): D as g^3 numbers at the index of the right-hand side (no halo planes: the
 // kernels predicate all three directions), below it the 27 planes of R D P, R (R D P) P, ...
-int build_point_part3(mgcmt_plan* p, const double* point_diag) {
+// With bonds (mgcmt_plan_create3d_bonds) level 0 holds four such planes — D, Bx, By, Bz — and K3Op::point = 3; their Galerkin
+// product is the same 27 planes, so the levels below are what they always were.
+int build_point_part3(mgcmt_plan* p, const double* point_diag, const double* const* bonds) {
   const char* e = getenv("MGCMT_3D_POINT_MARCH");  // "0": the fine level on the flat kernels (A/B tests)
   const int march = !(e && e[0] == '0');
+  // the passes of a fine level with bonds that march (kernels_3d_bonds.hip): those that measured faster than their flat form at 256^3
+  const int march_bonds = march ? (kBonds3Jacobi | kBonds3Parity | kBonds3Residual | kBonds3Prolong) : 0;
   for (size_t l = 0; l < p->levels.size(); ++l) {
     Level& L = p->levels[l];
     K3Op& k = L.dA.k3;
     const size_t N = (size_t)L.nr * L.gc;
     double* q = nullptr;
-    MG_HIP(hipMalloc((void**)&q, (l == 0 ? 1 : 27) * N * sizeof(double)));
+    MG_HIP(hipMalloc((void**)&q, (l == 0 ? (bonds[0] ? 4 : 1) : 27) * N * sizeof(double)));
     L.dA.owned.push_back(q);
     k.pg = q;
     k.pmarch = march;
+    if (l == 0 && bonds[0]) {
+      MG_HIP(hipMemcpy(q, point_diag, N * sizeof(double), hipMemcpyHostToDevice));
+      for (int a = 0; a < 3; ++a) MG_HIP(hipMemcpy(q + (a + 1) * N, bonds[a], N * sizeof(double), hipMemcpyHostToDevice));
+      k.point = 3;
+      k.pmarch = march_bonds;
+      k.pplane = (long)N;
+      continue;
+    }
     if (l == 0) {
       MG_HIP(hipMemcpy(q, point_diag, N * sizeof(double), hipMemcpyHostToDevice));
       k.point = 1;
@@ -369,7 +382,7 @@ int build_point_part3(mgcmt_plan* p, const double* point_diag) {
       continue;
     }
     const K3Op& kf = p->levels[l - 1].dA.k3;
-    launch3p_coarsen(nullptr, kf.n, kf.pg, kf.point == 1 ? 1 : 27, kf.pplane, q, (long)N);
+    launch3p_coarsen(nullptr, kf.n, kf.pg, kf.point == 1 ? 1 : kf.point == 3 ? 4 : 27, kf.pplane, q, (long)N);
     MG_TRY(post_launch());
     k.point = 2;
     k.pplane = (long)N;
@@ -481,7 +494,7 @@ int build_plan(const PlanSpec& d, mgcmt_plan** out) {
     }
   }
   if (d.point_diag) {
-    const int rc = d.dim == 3 ? build_point_part3(p, d.point_diag) : build_point_part(p, d.point_diag, d.point_east, d.point_south);
+    const int rc = d.dim == 3 ? build_point_part3(p, d.point_diag, d.point_bonds3) : build_point_part(p, d.point_diag, d.point_east, d.point_south);
     if (rc != MGCMT_OK) {
       mgcmt_plan_destroy(p);
       return rc;
@@ -548,7 +561,7 @@ int mgcmt_plan_get_point_stencil(const mgcmt_plan* p, int l, double* out, int64_
   const Level& L = p->levels[l];
   if (p->dim == 3) {
     const K3Op& k3 = L.dA.k3;
-    const int64_t N = L.nr * L.gc, need3 = k3.point == 1 ? N : 27 * N;
+    const int64_t N = L.nr * L.gc, need3 = k3.point == 1 ? N : k3.point == 3 ? 4 * N : 27 * N;  // (D, Bx, By, Bz lie one behind the other)
     if (!out || capacity < need3) return fail(MGCMT_ERR_INVALID, "point stencil buffer too small");
     MG_HIP(hipMemcpy(out, k3.pg, (size_t)need3 * sizeof(double), hipMemcpyDeviceToHost));
     return MGCMT_OK;
@@ -588,12 +601,33 @@ int mgcmt_plan_create3d_pot(const mgcmt_plan3d_desc* d, const double* point_diag
   return build_plan(spec, out);
 }
 
+int mgcmt_plan_create3d_bonds(const mgcmt_plan3d_desc* d, const double* point_diag, const double* bx, const double* by, const double* bz,
+                              mgcmt_plan** out) {
+  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!point_diag || !bx || !by || !bz) return fail(MGCMT_ERR_INVALID, "null point diagonal or bond array");
+  if (d->lowest > 16) return fail(MGCMT_ERR_INVALID, "lowest must be at most 16 on a 3-D plan (the coarsest level is solved directly)");
+  const int64_t g = d->g;
+  if (g >= 1)
+    for (int64_t a = 0; a < g; ++a)
+      for (int64_t b = 0; b < g; ++b)
+        if (bx[(a * g + b) * g + g - 1] != 0.0 || by[(a * g + g - 1) * g + b] != 0.0 || bz[((g - 1) * g + a) * g + b] != 0.0)
+          return fail(MGCMT_ERR_INVALID,
+                      "bonds towards points outside the grid (bx at x = g - 1, by at y = g - 1, bz at z = g - 1) must be zero");
+  PlanSpec spec{3, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->zfac, d->yfac, d->xfac}, {nullptr, nullptr, nullptr}, 0, 0, 0};
+  spec.point_diag = point_diag;
+  spec.point_bonds3[0] = bx;
+  spec.point_bonds3[1] = by;
+  spec.point_bonds3[2] = bz;
+  return build_plan(spec, out);
+}
+
 int mgcmt_plan3d_level_path(const mgcmt_plan* p, int l, int* kind, int* marching) {
   MG_TRY(check_level(p, l));
   if (p->dim != 3) return fail(MGCMT_ERR_INVALID, "mgcmt_plan3d_level_path needs a 3-D plan");
   const K3Op& k = p->levels[l].dA.k3;
-  if (kind) *kind = k.point == 2 ? 3 : k.seven ? (k.point == 1 ? 2 : 1) : (k.point == 1 ? 4 : 0);
-  if (marching) *marching = k.point ? (point3_marching(k) ? 1 : 0) : (k.seven && k.n >= 64 && k.n % 64 == 0 ? 1 : 0);
+  if (kind) *kind = k.point == 2 ? 3 : k.point == 3 ? (k.seven ? 5 : 6) : k.seven ? (k.point == 1 ? 2 : 1) : (k.point == 1 ? 4 : 0);
+  if (marching) *marching = k.point == 3 ? (bonds3_marching(k) ? 1 : 0) : k.point ? (point3_marching(k) ? 1 : 0) : (k.seven && k.n >= 64 && k.n % 64 == 0 ? 1 : 0);
   return MGCMT_OK;
 }
 

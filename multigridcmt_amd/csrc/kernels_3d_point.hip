@@ -15,6 +15,10 @@
 //     64 x 4 tile and 32-plane chunks with the planes z-1, z, z+1 in registers, D as a fourth stream.
 // The flat and the marching form of the fine level compute every point with ONE set of inline functions (p7_*: the same fma
 // order, the same reciprocal of c0 + D - mu), so their sweeps give the same bits; MGCMT_3D_POINT_MARCH=0 selects the flat form.
+// A fine level with per-point bonds as well (K3Op::point == 3: the planes D, Bx, By, Bz; mgcmt_plan_create3d_bonds) is a third
+// branch of the flat kernels' point (bonds3_point.h), a four-plane source of k3p_coarsen and six more entries per row of
+// k3p_band_add; its marching kernels are kernels_3d_bonds.hip's, to which the launchers below offer every pass first.
+#include "bonds3_point.h"
 #include "fused_kernel.h"
 #include "kernels_3d_common.h"
 #include "mgcmt_internal.h"
@@ -67,6 +71,15 @@ __device__ __forceinline__ PEval eval3p(const K3Op& op, W&& w, long z, long y, l
                  yp ? w(z, y + 1, x) : 0.0, xm ? w(z, y, x - 1) : 0.0, xp ? w(z, y, x + 1) : 0.0);
     return r;
   }
+  if (op.point == 3 && op.seven) {  // constant 7-point part + D + bonds (bonds3_point.h): a bond towards outside is a predicated zero
+    const double* __restrict__ g = op.pg + idx;
+    const long pl = op.pplane;
+    const b7::Coef c = b7::coef(op, zm ? g[3 * pl - n2] : 0.0, g[3 * pl], ym ? g[2 * pl - n] : 0.0, g[2 * pl], xm ? g[pl - 1] : 0.0, g[pl]);
+    r.dg = b7::dg(op, g[0], mu);
+    r.av = b7::av(c, r.dg, w(z, y, x), zm ? w(z - 1, y, x) : 0.0, zp ? w(z + 1, y, x) : 0.0, ym ? w(z, y - 1, x) : 0.0,
+                  yp ? w(z, y + 1, x) : 0.0, xm ? w(z, y, x - 1) : 0.0, xp ? w(z, y, x + 1) : 0.0);
+    return r;
+  }
   // the 27 neighbours once, zeros outside the grid
   double wn[3][3][3];
 #pragma unroll
@@ -106,6 +119,17 @@ __device__ __forceinline__ PEval eval3p(const K3Op& op, W&& w, long z, long y, l
   if (op.point == 1) {  // a diagonal on top of general terms
     acc += g[0] * wn[1][1][1];
     diag += g[0];
+  } else if (op.point == 3) {  // a diagonal and bonds on top of general terms: the six neighbour products and the centre
+    const long pl = op.pplane;
+    double pa = g[0] * wn[1][1][1];
+    pa += (zm ? g[3 * pl - n2] : 0.0) * wn[0][1][1];
+    pa += g[3 * pl] * wn[2][1][1];
+    pa += (ym ? g[2 * pl - n] : 0.0) * wn[1][0][1];
+    pa += g[2 * pl] * wn[1][2][1];
+    pa += (xm ? g[pl - 1] : 0.0) * wn[1][1][0];
+    pa += g[pl] * wn[1][1][2];
+    acc += pa;
+    diag += g[0];
   } else {
     const long pl = op.pplane;
 #pragma unroll
@@ -131,6 +155,7 @@ __device__ __forceinline__ PEval eval3p(const K3Op& op, W&& w, long z, long y, l
 
 __device__ __forceinline__ double relax3p(const K3Op& op, const PEval& e, double omega, double f, double vc) {
   if (op.point == 1 && op.seven) return p7_relax(omega, f, e.av, e.dg, vc);
+  if (op.point == 3 && op.seven) return b7::relax(omega, f, e.av, e.dg, vc);
   return vc + omega * (f - e.av) / e.dg;
 }
 
@@ -248,6 +273,18 @@ __global__ void k3p_band_add(K3Op op, KBand b) {
     ab[r * b.width + b.kl] += op.pg[r];
     return;
   }
+  if (op.point == 3) {  // D and the six bonds (a plan whose fine level is also its coarsest)
+    const long pl = op.pplane;
+    double* row = ab + r * b.width + b.kl;
+    row[0] += op.pg[r];
+    if (x > 0) row[-1] += op.pg[pl + r - 1];
+    if (x + 1 < n) row[1] += op.pg[pl + r];
+    if (y > 0) row[-n] += op.pg[2 * pl + r - n];
+    if (y + 1 < n) row[n] += op.pg[2 * pl + r];
+    if (z > 0) row[-n2] += op.pg[3 * pl + r - n2];
+    if (z + 1 < n) row[n2] += op.pg[3 * pl + r];
+    return;
+  }
   for (int a = -1; a <= 1; ++a)
     for (int bb = -1; bb <= 1; ++bb)
       for (int c = -1; c <= 1; ++c) {
@@ -269,7 +306,8 @@ __device__ __forceinline__ void prolong_weights(long ip, long I, long cn, double
   }
 }
 
-// coarse = R G P for the per-point part G of a level of fn^3 points (fp == 27: 27 planes; fp == 1: a diagonal), one thread
+// coarse = R G P for the per-point part G of a level of fn^3 points (fp == 27: 27 planes; fp == 1: a diagonal; fp == 4: the
+// planes D, Bx, By, Bz of a level with bonds — the centre from D, the six axis neighbours from the bond the two points share), one thread
 // per coarse point (Z, Y, X) and all 27 of its coefficients.  R1 puts (1/4, 1/2, 1/4) on fine 2I .. 2I + 2; the last coarse
 // plane / row / column has no fine point 2I + 2 (the one-sided end of the reference's transfers), which the range checks
 // are.  Fixed summation order: the result does not depend on the launch geometry.  Every weight is a power of two, so only
@@ -301,15 +339,25 @@ __global__ void __launch_bounds__(kFlatThreads) k3p_coarsen(long fn, const doubl
           prolong_weights(zp, Z, cn, wz);
           for (int b = 0; b < 3; ++b) {
             const long yp = y + b - 1;
-            if (yp < 0 || yp >= fn || (fp == 1 && b != 1)) continue;
+            if (yp < 0 || yp >= fn || (fp == 1 && b != 1) || (fp == 4 && a != 1 && b != 1)) continue;
             double wy[3];
             prolong_weights(yp, Y, cn, wy);
             for (int c = 0; c < 3; ++c) {
               const long xp = x + c - 1;
-              if (xp < 0 || xp >= fn || (fp == 1 && c != 1)) continue;
+              if (xp < 0 || xp >= fn || (fp == 1 && c != 1) || (fp == 4 && (a != 1 || b != 1) && c != 1)) continue;
               double wx[3];
               prolong_weights(xp, X, cn, wx);
-              const double gv = r * (fp == 1 ? fine[fi] : fine[(9 * a + 3 * b + c) * fplane + fi]);
+              double gf;
+              if (fp == 1)
+                gf = fine[fi];
+              else if (fp == 4)  // the bond lies with the lower of the two points
+                gf = a != 1   ? fine[3 * fplane + (a == 0 ? fi - fn * fn : fi)]
+                     : b != 1 ? fine[2 * fplane + (b == 0 ? fi - fn : fi)]
+                     : c != 1 ? fine[fplane + (c == 0 ? fi - 1 : fi)]
+                              : fine[fi];
+              else
+                gf = fine[(9 * a + 3 * b + c) * fplane + fi];
+              const double gv = r * gf;
 #pragma unroll
               for (int A = 0; A < 3; ++A) {
                 if (wz[A] == 0.0) continue;
@@ -451,11 +499,14 @@ dim3 march_grid(const K3Op& op, int k) {
 
 bool point3_marching(const K3Op& op) { return op.point == 1 && op.seven && op.pmarch && op.n >= kTileX && op.n % kTileX == 0; }
 
+// (a level with bonds, op.point == 3: the launchers below offer every pass to kernels_3d_bonds.hip first)
+
 void launch3p_apply(hipStream_t s, const K3Op& op, KVec src, KVec dst, const double* shifts, int k) {
   hipLaunchKernelGGL(k3p_apply, flat_grid(op.n * op.n * op.n, k), dim3(kFlatThreads), 0, s, op, src, dst, shifts);
 }
 
 void launch3p_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k) {
+  if (op.point == 3 && launch3b_wjacobi(s, op, vin, f, vout, shifts, omega, k)) return;
   if (point3_marching(op)) {
     hipLaunchKernelGGL(k3pm_sweep<0>, march_grid(op, k), dim3(kTileX, kTileY), 0, s, op, vin, f, vout, shifts, omega, 0, (int)(op.n / kChunkZ));
     return;
@@ -466,8 +517,9 @@ void launch3p_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout
 void launch3p_mc_sweep(hipStream_t s, const K3Op& op, KVec v, KVec f, const double* shifts, double omega, int k) {
   // the order of launch3_mc_sweep: odd coordinate sum first
   static const int order[8][3] = {{0, 0, 1}, {0, 1, 0}, {1, 0, 0}, {1, 1, 1}, {0, 0, 0}, {0, 1, 1}, {1, 0, 1}, {1, 1, 0}};
-  if (op.point == 1 && op.seven) {  // a diagonal does not couple points: two parity stages, as on the constant 7-point level
+  if ((op.point == 1 || op.point == 3) && op.seven) {  // a 7-point operator with any coefficients does not couple points of one parity: two stages
     for (int par = 1; par >= 0; --par) {
+      if (op.point == 3 && launch3b_parity(s, op, v, f, shifts, omega, par, k)) continue;
       if (point3_marching(op))
         hipLaunchKernelGGL(k3pm_sweep<1>, march_grid(op, k), dim3(kTileX, kTileY), 0, s, op, v, f, v, shifts, omega, par, (int)(op.n / kChunkZ));
       else
@@ -482,6 +534,7 @@ void launch3p_mc_sweep(hipStream_t s, const K3Op& op, KVec v, KVec f, const doub
 
 void launch3p_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k) {
   const long nc = op.n / 2;
+  if (op.point == 3 && launch3b_residual_restrict(s, op, v, f, fc, vc, shifts, k)) return;
   if (point3_marching(op)) {
     const int nch = (int)(op.n / kChunkZ);
     hipLaunchKernelGGL(k3pm_residual_restrict, dim3((unsigned)((nc + kTileX - 1) / kTileX), (unsigned)((nc + kTileY - 1) / kTileY), (unsigned)(nch * k)),
@@ -492,6 +545,7 @@ void launch3p_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, K
 }
 
 void launch3p_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k) {
+  if (op.point == 3 && launch3b_prolong_jacobi(s, op, e, vin, f, vout, shifts, omega, k)) return;
   if (point3_marching(op)) {
     hipLaunchKernelGGL(k3pm_prolong_jacobi, march_grid(op, k), dim3(kTileX, kTileY), 0, s, op, e, vin, f, vout, shifts, omega, (int)(op.n / kChunkZ));
     return;

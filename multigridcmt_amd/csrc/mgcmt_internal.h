@@ -77,7 +77,11 @@ struct K3Op {
   // (the Galerkin levels R D P): the coefficient of v(z + a - 1, y + b - 1, x + c - 1) in row idx is
   // pg[(9 a + 3 b + c) * pplane + idx], zero towards points outside the grid.  The flags above describe the Kronecker part
   // alone.  pmarch: a constant 7-point level with a diagonal takes the marching kernels where its size allows
-  // (MGCMT_3D_POINT_MARCH, read at plan creation).
+  // (MGCMT_3D_POINT_MARCH, read at plan creation).  3: a diagonal and bonds (mgcmt_plan_create3d_bonds; the fine level,
+  // kernels_3d_bonds.hip): four planes of g^3 numbers, pplane apart, no halo — D = pg[idx], Bx = pg[pplane + idx] added to the
+  // two entries between (z, y, x) and (z, y, x + 1), By = pg[2 pplane + idx] towards (z, y + 1, x), Bz = pg[3 pplane + idx]
+  // towards (z + 1, y, x); Bx(x = n - 1) = By(y = n - 1) = Bz(z = n - 1) = 0, a bond read at x - 1 < 0 etc. is a predicated
+  // zero.  pmarch is then the set of passes (kBonds3*) that march where the level's size allows.
   int point, pmarch;
   const double* pg;
   long pplane;
@@ -307,8 +311,19 @@ void launch3_band_assemble(hipStream_t s, const K3Op& op, const double* shifts, 
 // the same for a level with a per-point part (op.point; kernels_3d_point.hip) — the launchers above hand over —: flat
 // kernels for the 27-plane Galerkin levels, flat and marching ones for the constant 7-point fine level with a diagonal; the
 // per-point entries added into the assembled band matrix of the coarsest level; and the Galerkin product of the per-point
-// part: coarse <- R G P for the 27 planes (fine_planes = 27) or the diagonal (fine_planes = 1) of a level of fn^3 points
+// part: coarse <- R G P for the 27 planes (fine_planes = 27), the diagonal (fine_planes = 1) or the planes D, Bx, By, Bz
+// (fine_planes = 4) of a level of fn^3 points
 bool point3_marching(const K3Op& op);
+// a level with per-point bonds (op.point == 3): kernels_3d_point.hip's flat kernels run it, and its launchers offer every pass
+// to the marching kernels of kernels_3d_bonds.hip first.  bonds3_marching: the passes (kBonds3* bits of op.pmarch) that march
+// on this level — a constant 7-point Kronecker part, n a multiple of 64 — or 0; a launcher returns false, nothing launched,
+// where its pass stays flat.  launch3b_parity: one parity class of the red-black sweep, in place.
+constexpr int kBonds3Jacobi = 1, kBonds3Parity = 2, kBonds3Residual = 4, kBonds3Prolong = 8;
+int bonds3_marching(const K3Op& op);
+bool launch3b_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
+bool launch3b_parity(hipStream_t s, const K3Op& op, KVec v, KVec f, const double* shifts, double omega, int par, int k);
+bool launch3b_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k);
+bool launch3b_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
 void launch3p_apply(hipStream_t s, const K3Op& op, KVec src, KVec dst, const double* shifts, int k);
 void launch3p_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
 void launch3p_mc_sweep(hipStream_t s, const K3Op& op, KVec v, KVec f, const double* shifts, double omega, int k);

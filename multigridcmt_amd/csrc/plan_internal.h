@@ -87,7 +87,7 @@ struct mgcmt_plan {
   double* d_rqhistory = nullptr;  // Rayleigh quotients recorded by mgcmt_rq_line_step (MGCMT_RQ_HISTORY numbers)
   std::vector<double> h_shifts;
   bool has_mass = false;
-  bool has_point = false;  // A carries a per-point part (mgcmt_plan_create_pot / mgcmt_plan_create3d_pot): KOp::point / K3Op::point on every level
+  bool has_point = false;  // A carries a per-point part (mgcmt_plan_create_pot / _bonds / mgcmt_plan_create3d_pot / _bonds): KOp::point / K3Op::point on every level
   bool use_fused = true;
   bool use_tail = true;   // levels of at most 32 x 32 points as one launch (kernels_tail.hip)
   bool use_tail_dense = true;  // ... and that launch as ONE dense product with the tail's matrix (formed once per shift set)

@@ -53,6 +53,11 @@ class StructuredOperator:
     5-point operator with ANY coefficients, e.g. -div(w grad) + V with a position-dependent inverse effective mass w
     (``variable_mass_operator``, ``recognise_five_point``).  E[:, g-1] and S[g-1, :] point outside the grid and must be zero.
     An operator with bonds always has a ``point_diagonal`` (zeros if none was given).
+
+    3-D: a triple (Bx, By, Bz) of (g, g, g) arrays, index [z, y, x] — Bx[z, y, x] is added to the two entries between
+    (z, y, x) and (z, y, x + 1), By towards (z, y + 1, x), Bz towards (z + 1, y, x): a symmetric 7-point operator with any
+    coefficients (``variable_mass_operator(..., dimension="3d")``, ``recognise_seven_point``).  Bx[:, :, g-1], By[:, g-1, :]
+    and Bz[g-1, :, :] point outside the grid and must be zero.
     """
 
     def __init__(self, dimension, g, terms, point_diagonal=None, point_bonds=None):
@@ -60,9 +65,24 @@ class StructuredOperator:
         self.g = int(g)
         self.point_diagonal = None
         self.point_bonds = None
-        if point_bonds is not None:
+        if point_bonds is not None and dimension == "3d":
+            if len(point_bonds) != 3:
+                raise ValueError("point_bonds of a 3-D operator is a triple (Bx, By, Bz) of g x g x g arrays")
+            bonds = []
+            for name, b in zip(("Bx", "By", "Bz"), point_bonds):
+                b = np.array(b, dtype=np.float64, order="C")
+                if b.size != self.g ** 3:
+                    raise ValueError("point_bonds %s must hold g^3 = %d^3 values, not %r" % (name, self.g, b.shape))
+                bonds.append(b.reshape(self.g, self.g, self.g))
+            if bonds[0][:, :, -1].any() or bonds[1][:, -1, :].any() or bonds[2][-1, :, :].any():
+                raise ValueError("point_bonds: Bx[:, :, g-1], By[:, g-1, :] and Bz[g-1, :, :] are bonds towards points outside the grid "
+                                 "and must be zero")
+            self.point_bonds = tuple(bonds)
+            if point_diagonal is None:
+                point_diagonal = np.zeros((self.g, self.g, self.g))
+        elif point_bonds is not None:
             if dimension != "2d":
-                raise ValueError("point_bonds is a property of 2-D operators")
+                raise ValueError("point_bonds is a property of 2-D and 3-D operators")
             if len(point_bonds) != 2:
                 raise ValueError("point_bonds is a pair (E, S) of g x g arrays")
             bonds = []
@@ -109,7 +129,8 @@ class StructuredOperator:
             return StructuredOperator("1d", self.g, [(None, y * c) for _, y in self.terms])
         if self.dimension == "3d":
             return StructuredOperator("3d", self.g, [(x, y, z * c) for x, y, z in self.terms],
-                                      point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c)
+                                      point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c,
+                                      point_bonds=None if self.point_bonds is None else tuple(b * c for b in self.point_bonds))
         return StructuredOperator("2d", self.g, [(x, y * c) for x, y in self.terms],
                                   point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c,
                                   point_bonds=None if self.point_bonds is None else tuple(b * c for b in self.point_bonds))
@@ -138,7 +159,7 @@ class StructuredOperator:
         if self.dimension == "3d":
             i = tri_identity(self.g)
             terms = [tuple(a.copy() for a in t) for t in self.terms] + [(i, i.copy(), i * (-float(mu)))]
-            return StructuredOperator("3d", self.g, terms, point_diagonal=self.point_diagonal)
+            return StructuredOperator("3d", self.g, terms, point_diagonal=self.point_diagonal, point_bonds=self.point_bonds)
         terms = [(None if x is None else x.copy(), y.copy()) for x, y in self.terms]
         if self.dimension == "1d":
             terms[0][1][1] -= mu
@@ -166,6 +187,8 @@ class StructuredOperator:
                     for x, y, z in self.terms).tocsr()
             if self.point_diagonal is not None:
                 A = (A + sp.diags(self.point_diagonal.reshape(-1), 0, format="csr")).tocsr()
+            if self.point_bonds is not None:
+                A = (A + _bonds3_to_sparse(*self.point_bonds)).tocsr()
             return A
         A = sum(sp.kron(tri_to_sparse(x), tri_to_sparse(y), format="csr") for x, y in self.terms).tocsr()
         if self.point_diagonal is not None:
@@ -206,7 +229,8 @@ class StructuredOperator:
                 h.update(b"point_diagonal")
                 h.update(self.point_diagonal.tobytes())
             if self.point_bonds is not None:
-                for name, b in zip((b"point_bonds_east", b"point_bonds_south"), self.point_bonds):
+                names = (b"point_bonds_east", b"point_bonds_south") if self.dimension == "2d" else (b"point_bonds_x", b"point_bonds_y", b"point_bonds_z")
+                for name, b in zip(names, self.point_bonds):
                     h.update(name)
                     h.update(b.tobytes())
             self._fingerprint = h.hexdigest()
@@ -220,6 +244,17 @@ def _bonds_to_sparse(E, S):
     e = E.reshape(-1)[:n - 1]                  # (E[:, g-1] = 0: nothing wraps into the next row)
     s = S.reshape(-1)[:n - g]
     return sp.diags([s, e, e, s], [-g, -1, 1, g], shape=(n, n), format="csr")
+
+
+def _bonds3_to_sparse(Bx, By, Bz):
+    """The symmetric matrix with Bx[z, y, x] between (z, y, x) and (z, y, x + 1), By towards (z, y + 1, x) and Bz towards
+    (z + 1, y, x) (zero diagonal)."""
+    g = Bx.shape[0]
+    n = g ** 3
+    bx = Bx.reshape(-1)[:n - 1]                # (the outward bonds are zero: nothing wraps into the next row or plane)
+    by = By.reshape(-1)[:n - g]
+    bz = Bz.reshape(-1)[:n - g * g]
+    return sp.diags([bz, by, bx, bx, by, bz], [-g * g, -g, -1, 1, g, g * g], shape=(n, n), format="csr")
 
 
 def laplacian_operator(n, dimension="1d"):
@@ -332,7 +367,7 @@ def _mean_bond(a, b, mean):
     raise ValueError("variable_mass_operator: mean must be 'harmonic' or 'arithmetic', not %r" % (mean,))
 
 
-def variable_mass_operator(g, inv_mass, V=None, scale=-1.0 / np.pi ** 2, mean="harmonic"):
+def variable_mass_operator(g, inv_mass, V=None, scale=-1.0 / np.pi ** 2, mean="harmonic", dimension="2d"):
     """H = scale * div(w grad) + diag(V) on the g x g grid of ``laplacian(g, "2d")`` with a position-dependent inverse
     effective mass w = inv_mass (a (g, g) array, positive): the BenDaniel-Duke form of the kinetic term across the
     interfaces of a heterostructure.  Matrix-free.  With t = scale * L[0, 1] the neighbour entry of the uniform operator, the
@@ -342,8 +377,15 @@ def variable_mass_operator(g, inv_mass, V=None, scale=-1.0 / np.pi ** 2, mean="h
 
     The Kronecker terms carry w_ref * scale * Laplacian with w_ref = median(w); ``point_bonds`` and ``point_diagonal`` carry
     the deviations, so a uniform region stores zeros and level 0 keeps a constant 5-point Kronecker part.  A uniform w
-    returns what ``potential_operator`` / ``laplacian_operator`` (scaled) would return: no bonds."""
+    returns what ``potential_operator`` / ``laplacian_operator`` (scaled) would return: no bonds.
+
+    dimension="3d": the same on the g^3 grid of ``laplacian(g, "3d")`` — inv_mass and V are (g, g, g) arrays (or g^3 values),
+    index [z, y, x]; six bonds per point, three Kronecker terms, ``point_bonds`` = (Bx, By, Bz)."""
     g = int(g)
+    if dimension == "3d":
+        return _variable_mass_operator_3d(g, inv_mass, V, scale, mean)
+    if dimension != "2d":
+        raise ValueError("variable_mass_operator: dimension must be '2d' or '3d'")
     w = np.ascontiguousarray(inv_mass, dtype=np.float64)
     if w.size != g * g:
         raise ValueError("variable_mass_operator: inv_mass must hold g x g = %d x %d values, not %r" % (g, g, w.shape))
@@ -379,6 +421,46 @@ def variable_mass_operator(g, inv_mass, V=None, scale=-1.0 / np.pi ** 2, mean="h
     if V is not None:
         D = D + V
     return StructuredOperator("2d", g, [(tri_identity(g), Lr), (Lr.copy(), tri_identity(g))], point_diagonal=D, point_bonds=(E, S))
+
+
+def _variable_mass_operator_3d(g, inv_mass, V, scale, mean):
+    w = np.ascontiguousarray(inv_mass, dtype=np.float64)
+    if w.size != g ** 3:
+        raise ValueError("variable_mass_operator: inv_mass must hold g^3 = %d^3 values, not %r" % (g, w.shape))
+    w = w.reshape(g, g, g)
+    if not (w > 0).all():
+        raise ValueError("variable_mass_operator: the inverse mass must be positive everywhere")
+    _mean_bond(1.0, 1.0, mean)
+    if V is not None:
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        if V.size != g ** 3:
+            raise ValueError("variable_mass_operator: V must hold g^3 = %d^3 values, not %r" % (g, V.shape))
+        V = V.reshape(g, g, g)
+    w_ref = float(np.median(w))
+    L = tri_laplacian(g) * float(scale)
+    i = tri_identity(g)
+    Lr = L * w_ref
+    terms = [(i, i.copy(), Lr), (i.copy(), Lr.copy(), i.copy()), (Lr.copy(), i.copy(), i.copy())]
+    if (w == w_ref).all():
+        return StructuredOperator("3d", g, terms) if V is None else StructuredOperator("3d", g, terms, point_diagonal=V)
+    t = float(L[2, 0])
+    # bond values (multiples of t) towards x+ / y+ / z+ and x- / y- / z-; ghosts take the point's own w
+    bxp, byp, bzp = w.copy(), w.copy(), w.copy()
+    bxp[:, :, :-1] = _mean_bond(w[:, :, :-1], w[:, :, 1:], mean)
+    byp[:, :-1, :] = _mean_bond(w[:, :-1, :], w[:, 1:, :], mean)
+    bzp[:-1, :, :] = _mean_bond(w[:-1, :, :], w[1:, :, :], mean)
+    bxm, bym, bzm = w.copy(), w.copy(), w.copy()
+    bxm[:, :, 1:] = bxp[:, :, :-1]
+    bym[:, 1:, :] = byp[:, :-1, :]
+    bzm[1:, :, :] = bzp[:-1, :, :]
+    Bx, By, Bz = np.zeros((g, g, g)), np.zeros((g, g, g)), np.zeros((g, g, g))
+    Bx[:, :, :-1] = t * bxp[:, :, :-1] - t * w_ref
+    By[:, :-1, :] = t * byp[:, :-1, :] - t * w_ref
+    Bz[:-1, :, :] = t * bzp[:-1, :, :] - t * w_ref
+    D = -t * (bxp + bxm + byp + bym + bzp + bzm) - 3.0 * float(Lr[1, 0])
+    if V is not None:
+        D = D + V
+    return StructuredOperator("3d", g, terms, point_diagonal=D, point_bonds=(Bx, By, Bz))
 
 
 class UnrecognisedOperator(ValueError):
@@ -529,6 +611,71 @@ def recognise_five_point(A):
     E[:, :-1] = e[:, :-1] - ce
     S[:-1, :] = s[:-1, :] - cs
     op = StructuredOperator("2d", g, [(tri_identity(g), Y), (X, tri_identity(g))], point_diagonal=d0 - base, point_bonds=(E, S))
+    if len(_CACHE) > 64:
+        _CACHE.clear()
+    _CACHE[key] = (A, op)
+    return op
+
+
+def recognise_seven_point(A):
+    """StructuredOperator for ANY symmetric 7-point matrix on a g^3 grid (a 3-D Hamiltonian with a position-dependent effective
+    mass assembled as a sparse matrix).  What ``recognise(A, "3d")`` or ``recognise_potential(A, "3d")`` accepts is returned
+    as they return it; otherwise the median off-diagonal per direction and the median diagonal go into three Toeplitz
+    Kronecker terms — so that a uniform region leaves zeros — and the rest into the operator's ``point_bonds`` and
+    ``point_diagonal``.  Unsymmetric matrices, entries off the seven bands and entries across row or plane ends raise
+    UnrecognisedOperator."""
+    try:
+        return recognise_potential(A, "3d")
+    except UnrecognisedOperator:
+        if isinstance(A, StructuredOperator):
+            raise
+    if not sp.issparse(A):
+        A = sp.csr_matrix(np.asarray(A, dtype=np.float64))
+    key = ("seven_point",) + _cache_key(A)
+    hit = _CACHE.get(key)
+    if hit is not None and hit[0] is A:
+        return hit[1]
+    n = A.shape[0]
+    if A.shape[0] != A.shape[1] or np.iscomplexobj(A):
+        raise UnrecognisedOperator("recognise_seven_point: a real square matrix on a g^3 grid is needed")
+    g = int(round(n ** (1.0 / 3.0)))
+    while g ** 3 > n:
+        g -= 1
+    while (g + 1) ** 3 <= n:
+        g += 1
+    if g ** 3 != n or g < 2:
+        raise UnrecognisedOperator("3-D operator size %d is not a cube number" % n)
+    M = sp.csr_matrix(A, dtype=np.float64, copy=True)
+    M.eliminate_zeros()
+
+    def band(off):
+        out = np.zeros(n)
+        d = M.diagonal(off)
+        if off >= 0:
+            out[:n - off] = d
+        else:
+            out[-off:] = d
+        return out.reshape(g, g, g)                       # [z, y, x] of the row
+
+    d0 = M.diagonal(0).reshape(g, g, g)
+    xp, xm, yp, ym, zp, zm = (band(off) for off in (1, -1, g, -g, g * g, -g * g))
+    if sum(np.count_nonzero(b) for b in (xp, xm, yp, ym, zp, zm)) + np.count_nonzero(d0) != M.nnz:
+        raise UnrecognisedOperator("3-D operator is not a 7-point matrix: it has entries off the stencil")
+    if xp[:, :, -1].any() or xm[:, :, 0].any() or yp[:, -1, :].any() or ym[:, 0, :].any():
+        raise UnrecognisedOperator("3-D operator is not a 7-point matrix: it has entries across the row or plane ends")
+    if not (np.array_equal(xp[:, :, :-1], xm[:, :, 1:]) and np.array_equal(yp[:, :-1, :], ym[:, 1:, :])
+            and np.array_equal(zp[:-1, :, :], zm[1:, :, :])):
+        raise UnrecognisedOperator("3-D 7-point operator is not symmetric: per-point bonds describe symmetric matrices only")
+    base = float(np.median(d0))
+    cx, cy, cz = float(np.median(xp[:, :, :-1])), float(np.median(yp[:, :-1, :])), float(np.median(zp[:-1, :, :]))
+    Xt, Yt, Zt = _toeplitz_tri(cx, base - 2.0 * (base / 3.0), cx, g), _toeplitz_tri(cy, base / 3.0, cy, g), _toeplitz_tri(cz, base / 3.0, cz, g)
+    Bx, By, Bz = np.zeros((g, g, g)), np.zeros((g, g, g)), np.zeros((g, g, g))
+    Bx[:, :, :-1] = xp[:, :, :-1] - cx
+    By[:, :-1, :] = yp[:, :-1, :] - cy
+    Bz[:-1, :, :] = zp[:-1, :, :] - cz
+    i = tri_identity(g)
+    op = StructuredOperator("3d", g, [(i, i.copy(), Xt), (i.copy(), Yt, i.copy()), (Zt, i.copy(), i.copy())], point_diagonal=d0 - base,
+                            point_bonds=(Bx, By, Bz))
     if len(_CACHE) > 64:
         _CACHE.clear()
     _CACHE[key] = (A, op)

@@ -89,11 +89,17 @@ class Plan:
         if pd is not None:
             # an arbitrary potential V(x, y, z) on the diagonal: the per-point hierarchy R D P (27 planes per level) is built at creation
             if mass is not None:
-                raise ValueError("a 3-D operator with a point diagonal takes no mass operator: the Rayleigh-quotient routines (rqmin, "
+                raise ValueError("a 3-D operator with a point diagonal%s takes no mass operator: the Rayleigh-quotient routines (rqmin, "
                                  "vcycle_rqmg, ...) do not run on it; vcycle / vcycle_matrix, the smoothers wjacobi and gseidel_rb, "
-                                 "apply and drivers.block_eigensolve do")
+                                 "apply and drivers.block_eigensolve do" % (" and point bonds" if getattr(op, "point_bonds", None) is not None else ""))
             pd = _f64(pd)
-            check(_lib.lib().mgcmt_plan_create3d_pot(ctypes.byref(desc), as_dp(pd), ctypes.byref(self._h)))
+            bonds = getattr(op, "point_bonds", None)
+            if bonds is not None:
+                # per-point bonds as well (operators.variable_mass_operator(..., dimension="3d")): level 0 keeps D, Bx, By, Bz
+                bx, by, bz = (_f64(b) for b in bonds)
+                check(_lib.lib().mgcmt_plan_create3d_bonds(ctypes.byref(desc), as_dp(pd), as_dp(bx), as_dp(by), as_dp(bz), ctypes.byref(self._h)))
+            else:
+                check(_lib.lib().mgcmt_plan_create3d_pot(ctypes.byref(desc), as_dp(pd), ctypes.byref(self._h)))
         elif mass is None:
             check(_lib.lib().mgcmt_plan_create3d(ctypes.byref(desc), ctypes.byref(self._h)))
         else:
@@ -140,11 +146,12 @@ class Plan:
         """Host copy of the per-point part of `level` of a plan whose operator has a point diagonal: level 0 the diagonal,
         array [rows, cols]; below it the 9-point stencil R D P, array [3, 3, rows, cols] — entry [a, b, i, j] is the
         coefficient of point (i + a - 1, j + b - 1) in row (i, j).  Level 0 of an operator with ``point_bonds``: the three
-        planes D, E, S, array [3, rows, cols].  3-D: [g, g, g] on level 0 and the 27-point stencil
+        planes D, E, S, array [3, rows, cols].  3-D: [g, g, g] on level 0 ([4, g, g, g] = D, Bx, By, Bz with bonds) and the 27-point stencil
         [3, 3, 3, g_l, g_l, g_l] below — entry [a, b, c, z, y, x] is the coefficient of point (z + a - 1, y + b - 1, x + c - 1)."""
         if self.dim == 3:
             gl = self.g >> level
-            out = np.zeros((gl, gl, gl) if level == 0 else (3, 3, 3, gl, gl, gl))
+            bonds = getattr(self.op, "point_bonds", None) is not None
+            out = np.zeros(((4, gl, gl, gl) if bonds else (gl, gl, gl)) if level == 0 else (3, 3, 3, gl, gl, gl))
             check(_lib.lib().mgcmt_plan_get_point_stencil(self._h, level, as_dp(out), out.size))
             return out
         r, c, _ = self.shapes[level]

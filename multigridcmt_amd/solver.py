@@ -16,7 +16,7 @@ import scipy.sparse as sp
 from . import _lib
 from ._lib import GS_LEX, GS_MC, OP_A, OP_M, SLOT_F, SLOT_T, SLOT_V, SLOT_W, SOR_LEX, WJACOBI
 from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, planes_to_csr, recognise, recognise_five_point, recognise_potential,
-                        tag_structured)
+                        recognise_seven_point, tag_structured)
 from .plan import get_plan
 from .processor import MGCMTProcessor
 from .stencil_maker import MGCMTStencilMaker
@@ -62,7 +62,8 @@ def _recognise_entry(A, dimension):
     """``recognise`` for the 2-D and 3-D entry points: a 5-point (7-point) matrix with an arbitrary diagonal (a Hamiltonian
     with any potential), which ``recognise`` refuses, is mapped by ``recognise_potential`` to an operator with a point
     diagonal; in 2-D a symmetric 5-point matrix whose off-diagonals vary too (a position-dependent effective mass) is mapped
-    last by ``recognise_five_point`` to an operator with point bonds; what that refuses too raises ``recognise``'s error."""
+    last by ``recognise_five_point`` to an operator with point bonds, in 3-D a symmetric 7-point matrix by
+    ``recognise_seven_point``; what that refuses too raises ``recognise``'s error."""
     try:
         return recognise(A, dimension)
     except UnrecognisedOperator as err:
@@ -71,10 +72,9 @@ def _recognise_entry(A, dimension):
         try:
             return recognise_potential(A, dimension)
         except UnrecognisedOperator:
-            if dimension != "2d":
-                raise err
+            pass
         try:
-            return recognise_five_point(A)
+            return recognise_five_point(A) if dimension == "2d" else recognise_seven_point(A)
         except UnrecognisedOperator:
             raise err
 
@@ -247,7 +247,10 @@ class MGCMTSolver:
                     M = M - float(shift) * sp.identity(n, format="csr")
                 return M.tocsr()
             pd = plan.point_stencil(0) if getattr(plan.op, "point_diagonal", None) is not None else None
-            op = StructuredOperator("3d", gl, terms, point_diagonal=pd)
+            if pd is not None and getattr(plan.op, "point_bonds", None) is not None:
+                op = StructuredOperator("3d", gl, terms, point_diagonal=pd[0], point_bonds=(pd[1], pd[2], pd[3]))      # D, Bx, By, Bz
+            else:
+                op = StructuredOperator("3d", gl, terms, point_diagonal=pd)
             if shift:
                 op = op.shifted(float(shift))
             return tag_structured(op.tocsr(), op)

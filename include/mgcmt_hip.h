@@ -175,6 +175,26 @@ int mgcmt_plan_create_pot(const mgcmt_plan_desc* desc, const double* point_diag,
  * none does.  Both forms give the same bits.  The fused row-streaming passes do not take such a level (mgcmt_fused_max_sweeps: 0).
  * mgcmt_plan_get_point_stencil(level 0) returns the three planes D, E, S, rows x cols numbers each. */
 int mgcmt_plan_create_bonds(const mgcmt_plan_desc* desc, const double* point_diag, const double* east, const double* south, mgcmt_plan** out);
+/* A 2-D plan whose operator carries a per-point 9-point stencil on top of its Kronecker terms: any symmetric 9-point matrix,
+ *     A = sum_m X_m (x) Y_m + G  - shift * I,
+ * stencil = nine planes of g x g numbers on the host, plane 3 a + b, index [i * g + j] = the coefficient of
+ * v(i + a - 1, j + b - 1) in row (i, j) (the centre plane is a point diagonal): H = -div(W grad) + V with a position-dependent
+ * symmetric 2 x 2 inverse-mass tensor W, whose mixed derivative puts entries on the four corner neighbours.  A non-zero
+ * coefficient towards a point outside the grid, and a stencil that is not symmetric — plane 3 a + b at (i, j) must equal plane
+ * 3 (2 - a) + (2 - b) at (i + a - 1, j + b - 1) —, give MGCMT_ERR_INVALID.  desc and the refusals are mgcmt_plan_create_pot's
+ * (dim = 2, no mass operator, no row strip; the entries listed there return MGCMT_ERR_UNSUPPORTED on such a plan too).
+ * Level 0 (MGCMT_OPK_NINE_POINT) has the layout of the Galerkin levels of every plan with a per-point part — nine planes, 72 B
+ * per point — and the levels below are formed from it as they are formed from one another.  The fused row-streaming passes
+ * (mgcmt_fused_max_sweeps: 0), the tail, the two-level passes and the lexicographic pipelines do not take such a plan.
+ * Where level 0 has at least 128 columns it runs the tile kernels of csrc/kernels_nine_tile.hip (a whole four-colour sweep, two
+ * weighted-Jacobi sweeps, residual + restriction: one launch each, staged through LDS), otherwise one thread per point
+ * (csrc/kernels_pointwise.hip); both forms give the same bits per sweep.  The environment variable MGCMT_NINE_TILE, read at
+ * creation: 0 = flat everywhere; 2 = additionally every nine-plane Galerkin level of at least 128 columns of ANY plan with a
+ * per-point part takes the tile kernels (for measurements; not the default).
+ * mgcmt_plan_get_point_stencil(level 0) returns the nine planes. */
+int mgcmt_plan_create_nine(const mgcmt_plan_desc* desc, const double* stencil, mgcmt_plan** out);
+/* *tiled = 1 when `level` runs the tile kernels of csrc/kernels_nine_tile.hip (decided at creation, see above), else 0 */
+int mgcmt_plan_level_tiled(const mgcmt_plan* plan, int level, int* tiled);
 /* host copy of the per-point part of `level` of such a plan: level 0 rows x cols numbers (point_diag); a level below nine
  * planes of rows x cols, plane 3 a + b = the coefficient of v(i + a - 1, j + b - 1) in row (i, j), zero towards points
  * outside the grid.  The level's matrix is the one assembled from mgcmt_plan_get_factors plus these. */

@@ -87,6 +87,8 @@ _SIGNATURES = {
     "mgcmt_plan_create3d_mass": (c_int, [POINTER(Plan3dDesc), c_int32, _dp, _dp, _dp, POINTER(c_void_p)]),
     "mgcmt_plan_create_pot": (c_int, [POINTER(PlanDesc), _dp, POINTER(c_void_p)]),
     "mgcmt_plan_create_bonds": (c_int, [POINTER(PlanDesc), _dp, _dp, _dp, POINTER(c_void_p)]),
+    "mgcmt_plan_create_nine": (c_int, [POINTER(PlanDesc), _dp, POINTER(c_void_p)]),
+    "mgcmt_plan_level_tiled": (c_int, [c_void_p, c_int, POINTER(c_int)]),
     "mgcmt_plan_create3d_pot": (c_int, [POINTER(Plan3dDesc), _dp, POINTER(c_void_p)]),
     "mgcmt_plan_create3d_bonds": (c_int, [POINTER(Plan3dDesc), _dp, _dp, _dp, _dp, POINTER(c_void_p)]),
     "mgcmt_plan3d_level_path": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int)]),

@@ -145,6 +145,13 @@ int mgcmt::smooth_impl(mgcmt_plan* p, int l, int kind, int nu, double omega, int
     case MGCMT_WJACOBI: {
       MG_TRY(ensure_slot(p, l, MGCMT_SLOT_T));
       for (int it = 0; it < nu; ++it) {
+        // a level whose kernels take two sweeps in one launch (the tile form of a nine-plane level): pairs, then the odd one
+        if (it + 1 < nu && op.point &&
+            launch_point_wjacobi_pair(s, g, op, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, omega, k)) {
+          std::swap(L.base[MGCMT_SLOT_V], L.base[MGCMT_SLOT_T]);
+          ++it;
+          continue;
+        }
         launch_wjacobi(s, g, op, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, omega, k);
         std::swap(L.base[MGCMT_SLOT_V], L.base[MGCMT_SLOT_T]);
       }
@@ -152,7 +159,14 @@ int mgcmt::smooth_impl(mgcmt_plan* p, int l, int kind, int nu, double omega, int
     }
     case MGCMT_GS_MC: {
       static const int order[4][2] = {{0, 1}, {1, 0}, {0, 0}, {1, 1}};
+      if (op.point == 2 && nine_tiled(g, op)) MG_TRY(ensure_slot(p, l, MGCMT_SLOT_T));  // (the tile form is out of place)
       for (int it = 0; it < nu; ++it) {
+        // a level whose kernels take the whole four-colour sweep in one launch, out of place (the tile form of a nine-plane level)
+        if (op.point == 2 &&
+            launch_point_mc_sweep(s, g, op, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, omega, k)) {
+          std::swap(L.base[MGCMT_SLOT_V], L.base[MGCMT_SLOT_T]);
+          continue;
+        }
         // a level with bonds on the marching kernels: the colours (0,1), (1,0) are one parity stage, (0,0), (1,1) the other
         if (launch_bonds_parity(s, g, op, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->d_shifts, omega, 1, k)) {
           launch_bonds_parity(s, g, op, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->d_shifts, omega, 0, k);
@@ -186,10 +200,10 @@ int mgcmt::smooth_impl(mgcmt_plan* p, int l, int kind, int nu, double omega, int
 
 namespace {
 
-// level l and the one below halve exactly, as the one-pass residual + restriction of a level with bonds assumes
+// level l and the one below halve exactly, as the one-pass residual + restriction of a level with bonds or nine planes assumes
 bool bonds_restrict_ok(const mgcmt_plan* p, int l) {
   const Level &F = p->levels[l], &C = p->levels[l + 1];
-  return p->dim == 2 && F.dA.k.point == 3 && C.nr * 2 == F.nr && C.gc * 2 == F.gc;
+  return p->dim == 2 && F.dA.k.point >= 2 && C.nr * 2 == F.nr && C.gc * 2 == F.gc;
 }
 
 int residual_restrict_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {
@@ -205,7 +219,7 @@ int residual_restrict_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {
     return post_launch();
   }
   // a level with bonds on the marching kernels: one pass, F[l+1] and V[l+1] = 0 written, no fine residual stored
-  if (bonds_restrict_ok(p, l) && launch_bonds_residual_restrict(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F),
+  if (bonds_restrict_ok(p, l) && launch_point_residual_restrict(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F),
                                                                 p->kvec(l + 1, MGCMT_SLOT_F), p->kvec(l + 1, MGCMT_SLOT_V), p->d_shifts, k))
     return post_launch();
   launch_residual(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, k);
@@ -317,7 +331,7 @@ int down_leg(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, bool z
   }
   MG_TRY(smooth_impl(p, l, kind, nu, omega, k, s));
   // (V[l+1] is cleared by the level below, which starts from "zero, uncleared")
-  if (bonds_restrict_ok(p, l) && launch_bonds_residual_restrict(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F),
+  if (bonds_restrict_ok(p, l) && launch_point_residual_restrict(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F),
                                                                 p->kvec(l + 1, MGCMT_SLOT_F), KVec{nullptr, 0}, p->d_shifts, k))
     return post_launch();
   launch_residual(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, k);

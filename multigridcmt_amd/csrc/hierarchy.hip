@@ -289,6 +289,7 @@ struct PlanSpec {
   const double* point_east = nullptr;  // 2-D, mgcmt_plan_create_bonds: g x g numbers each, added to the entries between (i, j) and
   const double* point_south = nullptr;  // (i, j + 1) / (i + 1, j); both or neither
   const double* point_bonds3[3] = {nullptr, nullptr, nullptr};  // 3-D, mgcmt_plan_create3d_bonds: Bx, By, Bz, g^3 numbers each; all or none
+  const double* point_nine = nullptr;  // 2-D, mgcmt_plan_create_nine: nine planes of g x g numbers (instead of point_diag)
 };
 
 // The per-point part of A on every level (kernels_pointwise.hip): the diagonal D on level 0 in the level's padded row
@@ -296,7 +297,16 @@ struct PlanSpec {
 // The Kronecker part's operators (upload_op) are in place; this adds the pointers to them.
 // With bonds (east, south: mgcmt_plan_create_bonds) level 0 holds three such planes — D, E, S, each with its zero halo
 // rows — and KOp::point = 3; their Galerkin product is the same nine planes, so the levels below are what they always were.
-int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east, const double* south) {
+// With a 9-point stencil (nine: mgcmt_plan_create_nine) level 0 is a nine-plane level itself — KOp::point = 2, the layout of
+// the levels below, whose planes k_pw_coarsen forms from it as it forms level 2 from level 1.
+int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east, const double* south, const double* nine) {
+  // which nine-plane levels take the tile kernels (KOp::pmarch; kernels_nine_tile.hip).  Unset or "1": level 0 of a plan with a
+  // 9-point stencil, every pass (each measured faster than its flat form at 4096^2; nine_tiled adds the size rule);
+  // "0": none (A/B tests); "2": the Galerkin levels of every plan with a per-point part as well (measurements; not the default:
+  // existing plans run the launches they always ran).
+  const char* nt = getenv("MGCMT_NINE_TILE");
+  const int tile_mode = !nt || !nt[0] ? 1 : nt[0] == '0' ? 0 : nt[0] == '2' ? 2 : 1;
+  const int tile_all = kNineColour | kNineJacobi | kNineResidual;
   // which passes of the fine level of a plan with bonds march (KOp::pmarch; kernels_bonds.hip).  Unset: those that measured
   // faster than their flat form at 8192^2 — the parity stages and residual + restriction (bit 0); the weighted-Jacobi sweep
   // and the applied operator measured level with it and stay flat.  "1": every pass (bit 1 as well); "0": none (A/B tests).
@@ -306,6 +316,18 @@ int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east
     Level& L = p->levels[l];
     KOp& k = L.dA.k;
     double* q = nullptr;
+    if (l == 0 && nine) {
+      const size_t plane = (size_t)L.nr * L.gc;
+      MG_HIP(hipMalloc((void**)&q, 9 * plane * sizeof(double)));
+      L.dA.owned.push_back(q);
+      MG_HIP(hipMemcpy(q, nine, 9 * plane * sizeof(double), hipMemcpyHostToDevice));
+      k.point = 2;
+      k.pmarch = tile_mode >= 1 ? tile_all : 0;
+      k.pg = q;
+      k.pld = L.gc;
+      k.pplane = (long)plane;
+      continue;
+    }
     if (l == 0 && east) {
       const size_t padded = (size_t)(L.nr + 2 * L.halo) * L.gc, rows = (size_t)L.nr * L.gc, first = (size_t)L.halo * L.gc;
       MG_HIP(hipMalloc((void**)&q, 3 * padded * sizeof(double)));
@@ -340,6 +362,7 @@ int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east
     launch_point_coarsen(nullptr, F.nr, F.gc, kf.pg, kf.point == 1 ? 1 : kf.point == 3 ? 3 : 9, kf.pld, kf.pplane, q, L.gc, L.nr * L.gc);
     MG_TRY(post_launch());
     k.point = 2;
+    k.pmarch = tile_mode == 2 ? tile_all : 0;
     k.pg = q;
     k.pld = L.gc;
     k.pplane = L.nr * L.gc;
@@ -493,8 +516,9 @@ int build_plan(const PlanSpec& d, mgcmt_plan** out) {
       return rc;
     }
   }
-  if (d.point_diag) {
-    const int rc = d.dim == 3 ? build_point_part3(p, d.point_diag, d.point_bonds3) : build_point_part(p, d.point_diag, d.point_east, d.point_south);
+  if (d.point_diag || d.point_nine) {
+    const int rc = d.dim == 3 ? build_point_part3(p, d.point_diag, d.point_bonds3)
+                              : build_point_part(p, d.point_diag, d.point_east, d.point_south, d.point_nine);
     if (rc != MGCMT_OK) {
       mgcmt_plan_destroy(p);
       return rc;
@@ -553,6 +577,43 @@ int mgcmt_plan_create_bonds(const mgcmt_plan_desc* d, const double* point_diag, 
   spec.point_east = east;
   spec.point_south = south;
   return build_plan(spec, out);
+}
+
+int mgcmt_plan_create_nine(const mgcmt_plan_desc* d, const double* stencil, mgcmt_plan** out) {
+  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!stencil) return fail(MGCMT_ERR_INVALID, "null point stencil");
+  if (d->dim != 2) return fail(MGCMT_ERR_INVALID, "a point stencil needs a 2-D plan (dim = 2)");
+  if (d->m_nterms != 0) return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal (a point stencil) takes no mass operator (the Rayleigh-quotient entries do not run on it)");
+  if (!((d->row_begin == 0 && d->row_end == 0) || (d->row_begin == 0 && d->row_end == d->g)))
+    return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal (a point stencil) is a whole grid (no row strips)");
+  const int64_t g = d->g, plane = g * g;
+  for (int a = 0; a < 3 && g >= 1; ++a)
+    for (int b = 0; b < 3; ++b) {
+      const double* G = stencil + (3 * a + b) * plane;
+      const double* T = stencil + (3 * (2 - a) + (2 - b)) * plane;  // the plane of the opposite offset
+      for (int64_t i = 0; i < g; ++i) {
+        const int64_t ip = i + a - 1;
+        for (int64_t j = 0; j < g; ++j) {
+          const int64_t jp = j + b - 1;
+          if (ip < 0 || ip >= g || jp < 0 || jp >= g) {
+            if (G[i * g + j] != 0.0) return fail(MGCMT_ERR_INVALID, "point stencil: a coefficient towards a point outside the grid must be zero");
+          } else if (G[i * g + j] != T[ip * g + jp]) {
+            return fail(MGCMT_ERR_INVALID, "point stencil is not symmetric: the coefficient of (i', j') in row (i, j) must equal that of (i, j) in row (i', j')");
+          }
+        }
+      }
+    }
+  PlanSpec spec{2, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->xfac, d->yfac, nullptr}, {nullptr, nullptr, nullptr}, 0, 0, 0};
+  spec.point_nine = stencil;
+  return build_plan(spec, out);
+}
+
+int mgcmt_plan_level_tiled(const mgcmt_plan* p, int l, int* tiled) {
+  MG_TRY(check_level(p, l));
+  if (!tiled) return fail(MGCMT_ERR_INVALID, "null argument");
+  *tiled = p->dim == 2 && nine_tiled(p->kgrid(l), p->levels[l].dA.k) ? 1 : 0;
+  return MGCMT_OK;
 }
 
 int mgcmt_plan_get_point_stencil(const mgcmt_plan* p, int l, double* out, int64_t capacity) {

@@ -15,6 +15,7 @@
 #include "bonds_point.h"
 #include "fused_kernel.h"
 #include "mgcmt_internal.h"
+#include "nine_point.h"
 
 namespace mgcmt {
 
@@ -57,42 +58,55 @@ __device__ __forceinline__ PointOp eval_five_bonds(const KOp& op, const double* 
   return r;
 }
 
-// Any other level: the Kronecker terms and the per-point part (nine planes of G, or D, or D with the bonds E, S)
-// evaluated from ONE set of neighbour registers, rows north to south.
-__device__ __forceinline__ PointOp eval_general(const KOp& op, const double* __restrict__ v, long nc, long i, long j, double mu) {
-  const double* c = v + i * nc + j;
+// The values at the eight neighbours of (i, j): rows -1 / nr are the halo rows, columns outside the grid enter as zeros.
+__device__ __forceinline__ nine::Nb neighbours(const double* __restrict__ c, long nc, long j) {
   const bool hw = j > 0, he = j + 1 < nc;
-  const double n = c[-nc], s = c[nc];
-  const double w = hw ? c[-1] : 0.0, e = he ? c[1] : 0.0;
-  const double nw = hw ? c[-nc - 1] : 0.0, ne = he ? c[-nc + 1] : 0.0;
-  const double sw = hw ? c[nc - 1] : 0.0, se = he ? c[nc + 1] : 0.0;
+  nine::Nb v;
+  v.n = c[-nc];
+  v.s = c[nc];
+  v.w = hw ? c[-1] : 0.0;
+  v.e = he ? c[1] : 0.0;
+  v.nw = hw ? c[-nc - 1] : 0.0;
+  v.ne = he ? c[-nc + 1] : 0.0;
+  v.sw = hw ? c[nc - 1] : 0.0;
+  v.se = he ? c[nc + 1] : 0.0;
+  return v;
+}
+
+// Fine level of a plan with a per-point 9-point stencil (mgcmt_plan_create_nine; point == 2): constant 5-point Kronecker part
+// plus the nine planes.  The expressions are nine_point.h's, which the tile kernels (kernels_nine_tile.hip) share: the same
+// bits in either form.
+__device__ __forceinline__ PointOp eval_five_nine(const KOp& op, const double* __restrict__ v, long nc, long i, long j, double mu) {
+  const nine::Nb nb = neighbours(v + i * nc + j, nc, j);
+  double g[9];
+  nine::load9(g, op.pg + i * op.pld + j, op.pplane);
+  const nine::Pt p = nine::five(op.cn, op.cw, op.c0 - mu, nb, g);
+  PointOp r;
+  r.off = p.off;
+  r.dg = p.dg;
+  r.inv = p.inv;
+  return r;
+}
+
+// Any other level: the Kronecker terms and the per-point part (nine planes of G, or D, or D with the bonds E, S)
+// evaluated from ONE set of neighbour registers, rows north to south (nine_point.h: the tile kernels evaluate a nine-plane
+// level with the same functions).
+__device__ __forceinline__ PointOp eval_general(const KOp& op, const double* __restrict__ v, long nc, long i, long j, double mu) {
+  const nine::Nb nb = neighbours(v + i * nc + j, nc, j);
   double off = 0.0, diag = 0.0;
-  for (int m = 0; m < op.nterms; ++m) {
-    const double* X = op.X[m] + i;
-    const double* Y = op.Y[m] + j;
-    const double xl = X[0], xd = X[op.ldx], xu = X[2 * op.ldx];
-    const double yl = Y[0], yd = Y[op.ldy], yu = Y[2 * op.ldy];
-    const double rn = yl * nw + yd * n + yu * ne;
-    const double rc = yl * w + yu * e;
-    const double rs = yl * sw + yd * s + yu * se;
-    off += xl * rn + xd * rc + xu * rs;
-    diag += xd * yd;
-  }
+  nine::kron_terms(op, i, j, nb, off, diag);
   const double* __restrict__ g = op.pg + i * op.pld + j;
   if (op.point == 1) {
     diag += g[0];
   } else if (op.point == 3) {
     const double* __restrict__ ge = g + op.pplane;
     const double* __restrict__ gs = g + 2 * op.pplane;
-    off += bonds::neighbour_sum(0.0, 0.0, hw ? ge[-1] : 0.0, ge[0], gs[-op.pld], gs[0], w, e, n, s);
+    off += bonds::neighbour_sum(0.0, 0.0, j > 0 ? ge[-1] : 0.0, ge[0], gs[-op.pld], gs[0], nb.w, nb.e, nb.n, nb.s);
     diag += g[0];
   } else {
-    const long pl = op.pplane;
-    const double rn = g[0] * nw + g[pl] * n + g[2 * pl] * ne;
-    const double rc = g[3 * pl] * w + g[5 * pl] * e;
-    const double rs = g[6 * pl] * sw + g[7 * pl] * s + g[8 * pl] * se;
-    off += rn + rc + rs;
-    diag += g[4 * pl];
+    double g9[9];
+    nine::load9(g9, g, op.pplane);
+    nine::plane_terms(g9, nb, off, diag);
   }
   PointOp r;
   r.off = off;
@@ -103,6 +117,7 @@ __device__ __forceinline__ PointOp eval_general(const KOp& op, const double* __r
 
 __device__ __forceinline__ PointOp eval_point_pw(const KOp& op, const double* __restrict__ v, long nc, long i, long j, double mu) {
   if (op.point == 3 && op.five_point) return eval_five_bonds(op, v, nc, i, j, mu);
+  if (op.point == 2 && op.five_point) return eval_five_nine(op, v, nc, i, j, mu);
   return (op.point == 1 && op.five_point) ? eval_five_diag(op, v, nc, i, j, mu) : eval_general(op, v, nc, i, j, mu);
 }
 
@@ -251,6 +266,7 @@ void launch_point_apply(hipStream_t s, KGrid g, KOp op, KVec src, KVec dst, cons
 
 void launch_point_wjacobi(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k) {
   if (launch_bonds_wjacobi(s, g, op, vin, f, vout, shifts, omega, k)) return;
+  if (launch_nine_wjacobi(s, g, op, vin, f, vout, shifts, omega, 1, k)) return;  // the tile form of a nine-plane level
   const dim3 b(64, 4, 1);
   hipLaunchKernelGGL(k_pw_wjacobi, grid2d(g.nc, g.nr, k, b), b, 0, s, g, op, vin, f, vout, shifts, omega);
 }
@@ -265,6 +281,19 @@ void launch_point_mc_colour(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, cons
 void launch_point_residual(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, KVec r, const double* shifts, int k) {
   const dim3 b(64, 4, 1);
   hipLaunchKernelGGL(k_pw_residual, grid2d(g.nc, g.nr, k, b), b, 0, s, g, op, v, f, r, shifts);
+}
+
+bool launch_point_wjacobi_pair(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k) {
+  return launch_nine_wjacobi(s, g, op, vin, f, vout, shifts, omega, 2, k);
+}
+
+bool launch_point_mc_sweep(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k) {
+  return launch_nine_colour(s, g, op, vin, f, vout, shifts, omega, k);
+}
+
+bool launch_point_residual_restrict(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k) {
+  if (op.point == 3) return launch_bonds_residual_restrict(s, g, op, v, f, fc, vc, shifts, k);
+  return launch_nine_residual_restrict(s, g, op, v, f, fc, vc, shifts, k);
 }
 
 void launch_point_band_add(hipStream_t s, KGrid g, KOp op, const KBand& b, int k) {

@@ -55,7 +55,9 @@ struct KOp {
   // halo rows of every plane are zero, so S(-1, j) reads an exact zero; E(i, nc - 1) = S(nr - 1, j) = 0.  pmarch: which
   // passes of such a level take the marching kernels where its size allows — bit 0 the parity stages and residual +
   // restriction, bit 1 the Jacobi sweep and the applied operator (MGCMT_BONDS_MARCH, read at plan creation: hierarchy.hip).
-  // The flags above describe the Kronecker part alone.
+  // The flags above describe the Kronecker part alone.  Level 0 of mgcmt_plan_create_nine is a point == 2 level too (the
+  // caller's nine planes); on a point == 2 level pmarch is the set of passes (kNine* below) that take the tile kernels of
+  // kernels_nine_tile.hip where the level's size allows (MGCMT_NINE_TILE, read at plan creation: hierarchy.hip).
   int point, pmarch;
   const double* pg;
   long pld, pplane;
@@ -133,6 +135,21 @@ bool launch_bonds_apply(hipStream_t s, KGrid g, KOp op, KVec src, KVec dst, cons
 bool launch_bonds_wjacobi(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
 bool launch_bonds_parity(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, const double* shifts, double omega, int parity, int k);
 bool launch_bonds_residual_restrict(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k);
+// a nine-plane level (op.point == 2) on the tile kernels (kernels_nine_tile.hip): a workgroup stages v on its tile plus the
+// stages' rings in LDS, runs every stage there and stores the tile — out of place, vin -> vout, nothing between workgroups.
+// nine_tiled: the passes (kNine* bits of op.pmarch) that tile on this level — at least 128 columns, rows coarsened — or 0; a
+// launcher returns false, nothing launched, where its pass stays flat.  launch_nine_wjacobi: nsweep = 1 or 2 weighted-Jacobi
+// sweeps in one launch; launch_nine_colour: one whole four-colour sweep (0,1), (1,0), (0,0), (1,1);
+// launch_nine_residual_restrict: fc <- R (f - (A - mu) v) in one pass (even sizes; the fine residual is not stored), vc.p != null:
+// vc <- 0.  The launch_point_* forms are what the cycle calls: they pick the level's own kernels (bonds or nine planes).
+constexpr int kNineColour = 1, kNineJacobi = 2, kNineResidual = 4;
+int nine_tiled(const KGrid& g, const KOp& op);
+bool launch_nine_wjacobi(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int nsweep, int k);
+bool launch_nine_colour(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
+bool launch_nine_residual_restrict(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k);
+bool launch_point_wjacobi_pair(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
+bool launch_point_mc_sweep(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
+bool launch_point_residual_restrict(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k);
 // generalised lexicographic sweep (in place):
 //   v_k <- (alpha d_k v_k + beta f_k - wU sum_{j>k} a_kj v_j - wL sum_{j<k} a_kj v_j^new) / d_k
 void launch_lex_sweep(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, const double* shifts, double alpha, double beta,

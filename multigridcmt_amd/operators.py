@@ -58,13 +58,32 @@ class StructuredOperator:
     (z, y, x) and (z, y, x + 1), By towards (z, y + 1, x), Bz towards (z + 1, y, x): a symmetric 7-point operator with any
     coefficients (``variable_mass_operator(..., dimension="3d")``, ``recognise_seven_point``).  Bx[:, :, g-1], By[:, g-1, :]
     and Bz[g-1, :, :] point outside the grid and must be zero.
+
+    ``point_stencil`` (2-D only, instead of ``point_diagonal`` / ``point_bonds``, both of which it carries: its centre plane is
+    the diagonal): a (3, 3, g, g) array G — G[a, b][i, j] is the coefficient of v(i + a - 1, j + b - 1) in row (i, j), added to
+    the Kronecker terms: a symmetric 9-point operator with ANY coefficients, e.g. -div(W grad) + V with a position-dependent
+    2 x 2 inverse-mass tensor W (``tensor_mass_operator``, ``recognise_nine_point``).  Coefficients towards points outside the
+    grid must be zero and G[a, b][i, j] == G[2 - a, 2 - b][i + a - 1, j + b - 1] (``Plan.point_stencil`` returns this shape
+    for the levels below 0).
     """
 
-    def __init__(self, dimension, g, terms, point_diagonal=None, point_bonds=None):
+    def __init__(self, dimension, g, terms, point_diagonal=None, point_bonds=None, point_stencil=None):
         self.dimension = dimension
         self.g = int(g)
         self.point_diagonal = None
         self.point_bonds = None
+        self.point_stencil = None
+        if point_stencil is not None:
+            if dimension != "2d":
+                raise ValueError("point_stencil is a property of 2-D operators")
+            if point_diagonal is not None or point_bonds is not None:
+                raise ValueError("point_stencil carries the diagonal (its centre plane) and the bonds: give it instead of point_diagonal / point_bonds")
+            G = np.array(point_stencil, dtype=np.float64, order="C")
+            if G.size != 9 * self.g * self.g:
+                raise ValueError("point_stencil must hold 3 x 3 x g x g = 9 x %d x %d values, not %r" % (self.g, self.g, G.shape))
+            G = G.reshape(3, 3, self.g, self.g)
+            _check_point_stencil(G)
+            self.point_stencil = G
         if point_bonds is not None and dimension == "3d":
             if len(point_bonds) != 3:
                 raise ValueError("point_bonds of a 3-D operator is a triple (Bx, By, Bz) of g x g x g arrays")
@@ -133,7 +152,8 @@ class StructuredOperator:
                                       point_bonds=None if self.point_bonds is None else tuple(b * c for b in self.point_bonds))
         return StructuredOperator("2d", self.g, [(x, y * c) for x, y in self.terms],
                                   point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c,
-                                  point_bonds=None if self.point_bonds is None else tuple(b * c for b in self.point_bonds))
+                                  point_bonds=None if self.point_bonds is None else tuple(b * c for b in self.point_bonds),
+                                  point_stencil=None if self.point_stencil is None else self.point_stencil * c)
 
     def __mul__(self, other):
         if np.isscalar(other):
@@ -165,7 +185,8 @@ class StructuredOperator:
             terms[0][1][1] -= mu
         else:
             terms.append((tri_identity(self.g), tri_identity(self.g) * (-float(mu))))
-        return StructuredOperator(self.dimension, self.g, terms, point_diagonal=self.point_diagonal, point_bonds=self.point_bonds)
+        return StructuredOperator(self.dimension, self.g, terms, point_diagonal=self.point_diagonal, point_bonds=self.point_bonds,
+                                  point_stencil=self.point_stencil)
 
     # -- views ----------------------------------------------------------------------------------
     def diagonal(self):
@@ -175,6 +196,8 @@ class StructuredOperator:
             d = sum(np.kron(x[1], np.kron(y[1], z[1])) for x, y, z in self.terms)
             return d if self.point_diagonal is None else d + self.point_diagonal.reshape(-1)
         d = sum(np.outer(x[1], y[1]) for x, y in self.terms)
+        if self.point_stencil is not None:
+            d = d + self.point_stencil[1, 1]
         return (d if self.point_diagonal is None else d + self.point_diagonal).reshape(-1)
 
     def tocsr(self):
@@ -195,6 +218,8 @@ class StructuredOperator:
             A = (A + sp.diags(self.point_diagonal.reshape(-1), 0, format="csr")).tocsr()
         if self.point_bonds is not None:
             A = (A + _bonds_to_sparse(*self.point_bonds)).tocsr()
+        if self.point_stencil is not None:
+            A = (A + planes_to_csr(self.point_stencil)).tocsr()
         return A
 
     def tocsc(self):
@@ -233,8 +258,28 @@ class StructuredOperator:
                 for name, b in zip(names, self.point_bonds):
                     h.update(name)
                     h.update(b.tobytes())
+            if self.point_stencil is not None:
+                h.update(b"point_stencil")
+                h.update(self.point_stencil.tobytes())
             self._fingerprint = h.hexdigest()
         return self._fingerprint
+
+
+def _check_point_stencil(G):
+    """ValueError unless the (3, 3, g, g) stencil is zero towards points outside the grid and symmetric as a matrix."""
+    g = G.shape[-1]
+    for a in range(3):
+        for b in range(3):
+            # rows i (columns j) whose neighbour i + a - 1 (j + b - 1) lies inside the grid
+            i0, i1 = max(0, 1 - a), g - max(0, a - 1)
+            j0, j1 = max(0, 1 - b), g - max(0, b - 1)
+            inside = np.zeros((g, g), dtype=bool)
+            inside[i0:i1, j0:j1] = True
+            if G[a, b][~inside].any():
+                raise ValueError("point_stencil: a coefficient towards a point outside the grid is not zero (plane [%d, %d])" % (a, b))
+            if not np.array_equal(G[a, b][i0:i1, j0:j1], G[2 - a, 2 - b][i0 + a - 1:i1 + a - 1, j0 + b - 1:j1 + b - 1]):
+                raise ValueError("point_stencil is not symmetric: G[a, b][i, j] must equal G[2 - a, 2 - b][i + a - 1, j + b - 1] "
+                                 "(plane [%d, %d])" % (a, b))
 
 
 def _bonds_to_sparse(E, S):
@@ -463,6 +508,77 @@ def _variable_mass_operator_3d(g, inv_mass, V, scale, mean):
     return StructuredOperator("3d", g, terms, point_diagonal=D, point_bonds=(Bx, By, Bz))
 
 
+def tensor_mass_operator(g, wxx, wyy, wxy, V=None, scale=-1.0 / np.pi ** 2, mean="harmonic"):
+    """H = scale * div(W grad) + diag(V) on the g x g grid of ``laplacian(g, "2d")`` with a position-dependent symmetric 2 x 2
+    inverse-mass tensor W = [[wxx, wxy], [wxy, wyy]] ((g, g) arrays indexed [i, j]; positive definite everywhere): anisotropic
+    valleys rotated against the grid, strain, a principal axis that turns across an interface.  wxx acts along j (the east / west
+    bonds), wyy along i (north / south), wxy is the mixed coefficient in index directions (i, j).  Matrix-free.
+
+    With t = scale * L[0, 1] the neighbour entry of the uniform operator: the east entry between (i, j) and (i, j + 1) is
+    t * m(wxx[i, j], wxx[i, j + 1]), the south entry between (i, j) and (i + 1, j) is t * m(wyy[i, j], wyy[i + 1, j]) — m the
+    harmonic (default) or arithmetic mean —, the diagonal is -t * (the point's four bond values) + V, a bond towards a ghost
+    point taking the point's own wxx / wyy, and the corner entry between (i, j) and (i + a, j + b), a, b = -1 or +1, is
+    a * b * t * (wxy[i + a, j] + wxy[i, j + b]) / 4: the mixed derivative as the product of two central differences, made
+    symmetric.  W = I, V = 0 is scale * laplacian(g, "2d") exactly.
+
+    The Kronecker terms carry median(wxx) and median(wyy) times the scaled 1-D Laplacians; ``point_stencil`` carries the
+    deviations, so a uniform region stores zeros and level 0 keeps a constant 5-point Kronecker part.  wxy = 0 everywhere is a
+    diagonal tensor: the operator comes back with ``point_bonds`` (and wxx = wyy as well gives exactly
+    ``variable_mass_operator``'s)."""
+    g = int(g)
+    arrs = []
+    for name, a in (("wxx", wxx), ("wyy", wyy), ("wxy", wxy)):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size != g * g:
+            raise ValueError("tensor_mass_operator: %s must hold g x g = %d x %d values, not %r" % (name, g, g, a.shape))
+        arrs.append(a.reshape(g, g))
+    wxx, wyy, wxy = arrs
+    if not ((wxx > 0).all() and (wyy > 0).all() and (wxx * wyy > wxy * wxy).all()):
+        raise ValueError("tensor_mass_operator: the inverse-mass tensor must be positive definite everywhere (wxx, wyy > 0 and wxx wyy > wxy^2)")
+    if mean not in ("harmonic", "arithmetic"):
+        raise ValueError("tensor_mass_operator: mean must be 'harmonic' or 'arithmetic', not %r" % (mean,))
+    if V is not None:
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        if V.size != g * g:
+            raise ValueError("tensor_mass_operator: V must hold g x g = %d x %d values, not %r" % (g, g, V.shape))
+        V = V.reshape(g, g)
+    if not wxy.any() and np.array_equal(wxx, wyy):
+        return variable_mass_operator(g, wxx, V=V, scale=scale, mean=mean)
+    L = tri_laplacian(g) * float(scale)
+    t = float(L[2, 0])
+    rx, ry = float(np.median(wxx)), float(np.median(wyy))
+    Lx, Ly = L * rx, L * ry                       # along j (column factor) / along i (row factor)
+    # bond values (multiples of t) towards east / west / south / north; ghosts take the point's own value
+    be, bs = wxx.copy(), wyy.copy()
+    be[:, :-1] = _mean_bond(wxx[:, :-1], wxx[:, 1:], mean)
+    bs[:-1, :] = _mean_bond(wyy[:-1, :], wyy[1:, :], mean)
+    bw, bn = wxx.copy(), wyy.copy()
+    bw[:, 1:] = be[:, :-1]
+    bn[1:, :] = bs[:-1, :]
+    E, S = np.zeros((g, g)), np.zeros((g, g))
+    E[:, :-1] = t * be[:, :-1] - t * rx
+    S[:-1, :] = t * bs[:-1, :] - t * ry
+    D = -t * (be + bw + bs + bn) - float(Lx[1, 0]) - float(Ly[1, 0])
+    if V is not None:
+        D = D + V
+    terms = [(tri_identity(g), Lx), (Ly, tri_identity(g))]
+    if not wxy.any():
+        return StructuredOperator("2d", g, terms, point_diagonal=D, point_bonds=(E, S))
+    G = np.zeros((3, 3, g, g))
+    G[1, 1] = D
+    G[1, 2] = E
+    G[1, 0][:, 1:] = E[:, :-1]
+    G[2, 1] = S
+    G[0, 1][1:, :] = S[:-1, :]
+    # corners: a * b * t * (wxy[i + a, j] + wxy[i, j + b]) / 4 between (i, j) and (i + a, j + b)
+    q = 0.25 * t
+    G[2, 2][:-1, :-1] = q * (wxy[1:, :-1] + wxy[:-1, 1:])
+    G[0, 0][1:, 1:] = q * (wxy[:-1, 1:] + wxy[1:, :-1])
+    G[2, 0][:-1, 1:] = -q * (wxy[1:, 1:] + wxy[:-1, :-1])
+    G[0, 2][1:, :-1] = -q * (wxy[:-1, :-1] + wxy[1:, 1:])
+    return StructuredOperator("2d", g, terms, point_stencil=G)
+
+
 class UnrecognisedOperator(ValueError):
     pass
 
@@ -611,6 +727,68 @@ def recognise_five_point(A):
     E[:, :-1] = e[:, :-1] - ce
     S[:-1, :] = s[:-1, :] - cs
     op = StructuredOperator("2d", g, [(tri_identity(g), Y), (X, tri_identity(g))], point_diagonal=d0 - base, point_bonds=(E, S))
+    if len(_CACHE) > 64:
+        _CACHE.clear()
+    _CACHE[key] = (A, op)
+    return op
+
+
+def recognise_nine_point(A):
+    """StructuredOperator for ANY real symmetric 9-point matrix on a g x g grid (a Hamiltonian with a position-dependent
+    inverse-mass tensor assembled as a sparse matrix).  What ``recognise``, ``recognise_potential`` or ``recognise_five_point``
+    accepts is returned as they return it; otherwise the median east / south off-diagonal and the median diagonal go into two
+    Toeplitz Kronecker terms, as ``recognise_five_point`` takes them — so that a uniform region leaves zeros — and the rest into
+    the operator's ``point_stencil``.  Unsymmetric matrices, entries outside the 3 x 3 neighbourhood and entries across a row end
+    raise UnrecognisedOperator."""
+    try:
+        return recognise_five_point(A)
+    except UnrecognisedOperator:
+        if isinstance(A, StructuredOperator):
+            raise
+    if not sp.issparse(A):
+        A = sp.csr_matrix(np.asarray(A, dtype=np.float64))
+    key = ("nine_point",) + _cache_key(A)
+    hit = _CACHE.get(key)
+    if hit is not None and hit[0] is A:
+        return hit[1]
+    n = A.shape[0]
+    g = int(round(math.sqrt(n)))
+    if A.shape[0] != A.shape[1] or g * g != n or g < 3 or np.iscomplexobj(A):
+        raise UnrecognisedOperator("recognise_nine_point: a real square matrix on a g x g grid is needed")
+    M = sp.csr_matrix(A, dtype=np.float64, copy=True)
+    M.eliminate_zeros()
+    G = np.zeros((3, 3, g, g))
+    counted = 0
+    for a in range(3):
+        for b in range(3):
+            off = (a - 1) * g + (b - 1)
+            band = np.zeros(n)
+            d = M.diagonal(off)
+            if off >= 0:
+                band[:n - off] = d
+            else:
+                band[-off:] = d
+            counted += np.count_nonzero(band)
+            G[a, b] = band.reshape(g, g)                  # [i, j] of the row
+    if counted != M.nnz:
+        raise UnrecognisedOperator("2-D operator is not a 9-point matrix: it has entries outside the 3 x 3 neighbourhood")
+    if G[:, 0, :, 0].any() or G[:, 2, :, -1].any():
+        raise UnrecognisedOperator("2-D operator is not a 9-point matrix: it has entries across the row ends")
+    try:
+        _check_point_stencil(G)
+    except ValueError:
+        raise UnrecognisedOperator("2-D 9-point operator is not symmetric: a per-point stencil describes symmetric matrices only")
+    base = float(np.median(G[1, 1]))
+    ce, cs = float(np.median(G[1, 2][:, :-1])), float(np.median(G[2, 1][:-1, :]))
+    Y, X = np.zeros((3, g)), np.zeros((3, g))
+    Y[0, 1:], Y[1], Y[2, :-1] = ce, 0.5 * base, ce
+    X[0, 1:], X[1], X[2, :-1] = cs, base - 0.5 * base, cs
+    G[1, 1] -= base
+    G[1, 2][:, :-1] -= ce
+    G[1, 0][:, 1:] -= ce
+    G[2, 1][:-1, :] -= cs
+    G[0, 1][1:, :] -= cs
+    op = StructuredOperator("2d", g, [(tri_identity(g), Y), (X, tri_identity(g))], point_stencil=G)
     if len(_CACHE) > 64:
         _CACHE.clear()
     _CACHE[key] = (A, op)

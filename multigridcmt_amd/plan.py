@@ -44,8 +44,20 @@ class Plan:
             keep += [mx, my]
         desc.nvec, desc.device = self.nvec, device
         desc.row_begin, desc.row_end, desc.strip_levels = row_begin, row_end, strip_levels
+        ps = getattr(op, "point_stencil", None)
         pd = getattr(op, "point_diagonal", None)
-        if pd is not None:
+        if ps is not None:
+            # a per-point 9-point stencil (operators.tensor_mass_operator): level 0 is a nine-plane level like the Galerkin
+            # levels below it; such plans are whole 2-D grids without a mass operator
+            if mass is not None:
+                raise ValueError("an operator with a point stencil takes no mass operator: the Rayleigh-quotient routines (rqmin, "
+                                 "vcycle_rqmg, ...) do not run on it; vcycle / vcycle_matrix / fmg, the smoothers wjacobi and "
+                                 "gseidel_rb, apply and drivers.block_eigensolve do")
+            if row_begin or row_end or strip_levels:
+                raise ValueError("an operator with a point stencil is not sharded")
+            ps = _f64(ps)
+            check(_lib.lib().mgcmt_plan_create_nine(ctypes.byref(desc), as_dp(ps), ctypes.byref(self._h)))
+        elif pd is not None:
             # an arbitrary potential on the diagonal (operators.potential_operator): the per-point hierarchy R D P is built
             # at creation; such plans are whole 2-D grids without a mass operator
             if mass is not None:
@@ -146,7 +158,7 @@ class Plan:
         """Host copy of the per-point part of `level` of a plan whose operator has a point diagonal: level 0 the diagonal,
         array [rows, cols]; below it the 9-point stencil R D P, array [3, 3, rows, cols] — entry [a, b, i, j] is the
         coefficient of point (i + a - 1, j + b - 1) in row (i, j).  Level 0 of an operator with ``point_bonds``: the three
-        planes D, E, S, array [3, rows, cols].  3-D: [g, g, g] on level 0 ([4, g, g, g] = D, Bx, By, Bz with bonds) and the 27-point stencil
+        planes D, E, S, array [3, rows, cols]; of an operator with ``point_stencil``: [3, 3, rows, cols] like the levels below.  3-D: [g, g, g] on level 0 ([4, g, g, g] = D, Bx, By, Bz with bonds) and the 27-point stencil
         [3, 3, 3, g_l, g_l, g_l] below — entry [a, b, c, z, y, x] is the coefficient of point (z + a - 1, y + b - 1, x + c - 1)."""
         if self.dim == 3:
             gl = self.g >> level
@@ -156,7 +168,8 @@ class Plan:
             return out
         r, c, _ = self.shapes[level]
         bonds = getattr(self.op, "point_bonds", None) is not None
-        out = np.zeros(((3, r, c) if bonds else (r, c)) if level == 0 else (3, 3, r, c))
+        nine = getattr(self.op, "point_stencil", None) is not None      # level 0 is a nine-plane level too
+        out = np.zeros(((3, r, c) if bonds else (r, c)) if level == 0 and not nine else (3, 3, r, c))
         check(_lib.lib().mgcmt_plan_get_point_stencil(self._h, level, as_dp(out), out.size))
         return out
 
@@ -165,6 +178,13 @@ class Plan:
         kind, marching = c_int(0), c_int(0)
         check(_lib.lib().mgcmt_plan3d_level_path(self._h, level, ctypes.byref(kind), ctypes.byref(marching)))
         return kind.value, bool(marching.value)
+
+    def level_tiled(self, level):
+        """Whether `level` runs the tile kernels of a nine-plane level (mgcmt_plan_level_tiled; decided at creation from the
+        level's kind and size and the environment variable MGCMT_NINE_TILE)."""
+        t = c_int(0)
+        check(_lib.lib().mgcmt_plan_level_tiled(self._h, level, ctypes.byref(t)))
+        return bool(t.value)
 
     def level_halo(self, level):
         """(halo rows kept around every vector of `level`, how many of them a sharded cycle exchanges and reads)"""

@@ -15,8 +15,8 @@ import scipy.sparse as sp
 
 from . import _lib
 from ._lib import GS_LEX, GS_MC, OP_A, OP_M, SLOT_F, SLOT_T, SLOT_V, SLOT_W, SOR_LEX, WJACOBI
-from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, planes_to_csr, recognise, recognise_five_point, recognise_potential,
-                        recognise_seven_point, tag_structured)
+from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, planes_to_csr, recognise, recognise_five_point,
+                        recognise_nine_point, recognise_potential, recognise_seven_point, tag_structured)
 from .plan import get_plan
 from .processor import MGCMTProcessor
 from .stencil_maker import MGCMTStencilMaker
@@ -62,8 +62,9 @@ def _recognise_entry(A, dimension):
     """``recognise`` for the 2-D and 3-D entry points: a 5-point (7-point) matrix with an arbitrary diagonal (a Hamiltonian
     with any potential), which ``recognise`` refuses, is mapped by ``recognise_potential`` to an operator with a point
     diagonal; in 2-D a symmetric 5-point matrix whose off-diagonals vary too (a position-dependent effective mass) is mapped
-    last by ``recognise_five_point`` to an operator with point bonds, in 3-D a symmetric 7-point matrix by
-    ``recognise_seven_point``; what that refuses too raises ``recognise``'s error."""
+    by ``recognise_five_point`` to an operator with point bonds and a symmetric 9-point matrix (an inverse-mass tensor) last by
+    ``recognise_nine_point`` to one with a point stencil; in 3-D a symmetric 7-point matrix by ``recognise_seven_point``; what
+    that refuses too raises ``recognise``'s error."""
     try:
         return recognise(A, dimension)
     except UnrecognisedOperator as err:
@@ -74,15 +75,20 @@ def _recognise_entry(A, dimension):
         except UnrecognisedOperator:
             pass
         try:
-            return recognise_five_point(A) if dimension == "2d" else recognise_seven_point(A)
+            return recognise_nine_point(A) if dimension == "2d" else recognise_seven_point(A)     # (tries recognise_five_point first)
         except UnrecognisedOperator:
             raise err
+
+
+def _has_point(op):
+    """The operator carries a per-point part: a point diagonal (with or without bonds) or a point stencil."""
+    return getattr(op, "point_diagonal", None) is not None or getattr(op, "point_stencil", None) is not None
 
 
 def _check_point_smoother(op, kind):
     """An operator with a point diagonal has weighted Jacobi and multicolour Gauss-Seidel; a lexicographic smoother raises
     instead of being replaced by another one."""
-    if getattr(op, "point_diagonal", None) is not None and kind in (GS_LEX, SOR_LEX):
+    if _has_point(op) and kind in (GS_LEX, SOR_LEX):
         raise ValueError("gseidel / sor (lexicographic) are not available for an operator with a point diagonal (an arbitrary "
                          "potential V(x, y) or V(x, y, z)); the supported smoothers are wjacobi, gseidel_rb (multicolour) and "
                          "foreign smoother callables")
@@ -257,7 +263,12 @@ class MGCMTSolver:
         xf = plan.factors(level, 0) if plan.dim == 2 else None
         yf = plan.factors(level, 1)
         terms = [((xf[m].copy() if xf is not None else None), yf[m].copy()) for m in range(yf.shape[0])]
-        if getattr(plan.op, "point_diagonal", None) is not None:
+        if getattr(plan.op, "point_stencil", None) is not None and level == 0:
+            op = StructuredOperator("2d", plan.g, terms, point_stencil=plan.point_stencil(0))      # the factors plus the nine planes
+            if shift:
+                op = op.shifted(float(shift))
+            return tag_structured(op.tocsr(), op)
+        if _has_point(plan.op):
             # the Kronecker part's level plus the per-point part the library formed: the diagonal on level 0, the 9-point
             # stencil R D P below (a foreign smoother sees the true R A P - mu I)
             gl = plan.g >> level
@@ -439,7 +450,7 @@ class MGCMTSolver:
         if g < 4:
             raise ValueError("twogrid needs a fine grid of at least 4 points per direction")
         op = _recognise_entry(A, dimension)
-        if getattr(op, "point_diagonal", None) is not None:
+        if _has_point(op):
             raise ValueError("twogrid is not available for an operator with a point diagonal; vcycle (with lowest_level = g / 2: "
                              "the same two-grid cycle), vcycle_matrix and fmg are, with the smoothers wjacobi and gseidel_rb")
         plan = get_plan(op, g // 2, nvec=1)

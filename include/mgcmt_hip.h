@@ -222,10 +222,10 @@ int mgcmt_plan_create3d_pot(const mgcmt_plan3d_desc* desc, const double* point_d
  * AlGaAs barrier), the Kronecker terms carrying a reference mass and the bonds the deviations.  bx at x = g - 1, by at
  * y = g - 1 and bz at z = g - 1 point outside the grid and must be zero (MGCMT_ERR_INVALID otherwise).  desc, what runs and
  * the refusals are mgcmt_plan_create3d_pot's.  The Galerkin levels are the same 27 planes per level as for a point diagonal.
- * Level 0 keeps four planes D, Bx, By, Bz (32 B per point, about 4 GiB at 512^3) and runs kernels of its own: where its
- * Kronecker part is a constant 7-point operator and g is a multiple of 64, marching kernels with the four planes as streams
- * (csrc/kernels_3d_bonds.hip), otherwise — and with MGCMT_3D_POINT_MARCH=0 — one thread per point
- * (csrc/kernels_3d_point.hip); both forms give the same bits per sweep.  mgcmt_apply runs flat.
+ * Level 0 keeps four planes D, Bx, By, Bz (32 B per point, about 4 GiB at 512^3) and runs the point-diagonal level's kernels
+ * with the bonds as three more streams (csrc/kernels_3d_point.hip): where its Kronecker part is a constant 7-point operator and
+ * g is a multiple of 64 the marching kernels k3pm_*<BONDS = true>, otherwise — and with MGCMT_3D_POINT_MARCH=0 — the flat
+ * ones, one thread per point; both forms give the same bits per sweep.  mgcmt_apply runs flat.
  * mgcmt_plan_get_point_stencil(level 0) returns the four planes D, Bx, By, Bz, g^3 numbers each. */
 int mgcmt_plan_create3d_bonds(const mgcmt_plan3d_desc* desc, const double* point_diag, const double* bx, const double* by, const double* bz,
                               mgcmt_plan** out);

@@ -1,4 +1,4 @@
-// One point of (A - mu I) for a 5-point operator with per-point bond coefficients (KOp::point == 3,
+// One point of (A - mu I) for a 5-point operator with per-point bond coefficients (KOp::point == kPointBonds,
 // mgcmt_plan_create_bonds): the constant 5-point Kronecker part (c0, cn, cw) plus a diagonal D and the bonds E (towards
 // the east neighbour) and S (towards the south neighbour) — H = -div(w grad) + V with a position-dependent inverse mass w.
 //   east  coefficient  cw + E(i, j)        west   cw + E(i, j - 1)

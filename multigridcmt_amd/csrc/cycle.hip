@@ -159,10 +159,10 @@ int mgcmt::smooth_impl(mgcmt_plan* p, int l, int kind, int nu, double omega, int
     }
     case MGCMT_GS_MC: {
       static const int order[4][2] = {{0, 1}, {1, 0}, {0, 0}, {1, 1}};
-      if (op.point == 2 && nine_tiled(g, op)) MG_TRY(ensure_slot(p, l, MGCMT_SLOT_T));  // (the tile form is out of place)
+      if (op.point == kPointPlanes && nine_tiled(g, op)) MG_TRY(ensure_slot(p, l, MGCMT_SLOT_T));  // (the tile form is out of place)
       for (int it = 0; it < nu; ++it) {
         // a level whose kernels take the whole four-colour sweep in one launch, out of place (the tile form of a nine-plane level)
-        if (op.point == 2 &&
+        if (op.point == kPointPlanes &&
             launch_point_mc_sweep(s, g, op, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, omega, k)) {
           std::swap(L.base[MGCMT_SLOT_V], L.base[MGCMT_SLOT_T]);
           continue;
@@ -203,7 +203,7 @@ namespace {
 // level l and the one below halve exactly, as the one-pass residual + restriction of a level with bonds or nine planes assumes
 bool bonds_restrict_ok(const mgcmt_plan* p, int l) {
   const Level &F = p->levels[l], &C = p->levels[l + 1];
-  return p->dim == 2 && F.dA.k.point >= 2 && C.nr * 2 == F.nr && C.gc * 2 == F.gc;
+  return p->dim == 2 && (F.dA.k.point == kPointPlanes || F.dA.k.point == kPointBonds) && C.nr * 2 == F.nr && C.gc * 2 == F.gc;
 }
 
 int residual_restrict_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {

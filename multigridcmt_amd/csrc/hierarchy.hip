@@ -296,8 +296,8 @@ struct PlanSpec {
 // layout (zero halo rows), below it the nine planes of R D P, R (R D P) P, ... formed on the device, one launch per level.
 // The Kronecker part's operators (upload_op) are in place; this adds the pointers to them.
 // With bonds (east, south: mgcmt_plan_create_bonds) level 0 holds three such planes — D, E, S, each with its zero halo
-// rows — and KOp::point = 3; their Galerkin product is the same nine planes, so the levels below are what they always were.
-// With a 9-point stencil (nine: mgcmt_plan_create_nine) level 0 is a nine-plane level itself — KOp::point = 2, the layout of
+// rows — and KOp::point = kPointBonds; their Galerkin product is the same nine planes, so the levels below are what they always were.
+// With a 9-point stencil (nine: mgcmt_plan_create_nine) level 0 is a nine-plane level itself — KOp::point = kPointPlanes, the layout of
 // the levels below, whose planes k_pw_coarsen forms from it as it forms level 2 from level 1.
 int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east, const double* south, const double* nine) {
   // which nine-plane levels take the tile kernels (KOp::pmarch; kernels_nine_tile.hip).  Unset or "1": level 0 of a plan with a
@@ -321,7 +321,7 @@ int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east
       MG_HIP(hipMalloc((void**)&q, 9 * plane * sizeof(double)));
       L.dA.owned.push_back(q);
       MG_HIP(hipMemcpy(q, nine, 9 * plane * sizeof(double), hipMemcpyHostToDevice));
-      k.point = 2;
+      k.point = kPointPlanes;
       k.pmarch = tile_mode >= 1 ? tile_all : 0;
       k.pg = q;
       k.pld = L.gc;
@@ -336,7 +336,7 @@ int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east
       MG_HIP(hipMemcpy(q + first, point_diag, rows * sizeof(double), hipMemcpyHostToDevice));
       MG_HIP(hipMemcpy(q + padded + first, east, rows * sizeof(double), hipMemcpyHostToDevice));
       MG_HIP(hipMemcpy(q + 2 * padded + first, south, rows * sizeof(double), hipMemcpyHostToDevice));
-      k.point = 3;
+      k.point = kPointBonds;
       k.pmarch = march;
       k.pg = q + first;
       k.pld = L.gc;
@@ -349,7 +349,7 @@ int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east
       L.dA.owned.push_back(q);
       MG_HIP(hipMemset(q, 0, padded * sizeof(double)));
       MG_HIP(hipMemcpy(q + (size_t)L.halo * L.gc, point_diag, (size_t)L.nr * L.gc * sizeof(double), hipMemcpyHostToDevice));
-      k.point = 1;
+      k.point = kPointDiag;
       k.pg = q + (size_t)L.halo * L.gc;
       k.pld = L.gc;
       k.pplane = 0;
@@ -359,9 +359,9 @@ int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east
     const KOp& kf = F.dA.k;
     MG_HIP(hipMalloc((void**)&q, (size_t)9 * L.nr * L.gc * sizeof(double)));
     L.dA.owned.push_back(q);
-    launch_point_coarsen(nullptr, F.nr, F.gc, kf.pg, kf.point == 1 ? 1 : kf.point == 3 ? 3 : 9, kf.pld, kf.pplane, q, L.gc, L.nr * L.gc);
+    launch_point_coarsen(nullptr, F.nr, F.gc, kf.pg, kf.point == kPointDiag ? 1 : kf.point == kPointBonds ? 3 : 9, kf.pld, kf.pplane, q, L.gc, L.nr * L.gc);
     MG_TRY(post_launch());
-    k.point = 2;
+    k.point = kPointPlanes;
     k.pmarch = tile_mode == 2 ? tile_all : 0;
     k.pg = q;
     k.pld = L.gc;
@@ -374,13 +374,12 @@ int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east
 
 // The same on a 3-D plan (kernels_3d_point.hip): D as g^3 numbers at the index of the right-hand side (no halo planes: the
 // kernels predicate all three directions), below it the 27 planes of R D P, R (R D P) P, ...
-// With bonds (mgcmt_plan_create3d_bonds) level 0 holds four such planes — D, Bx, By, Bz — and K3Op::point = 3; their Galerkin
-// product is the same 27 planes, so the levels below are what they always were.
+// With bonds (mgcmt_plan_create3d_bonds) level 0 holds four such planes — D, Bx, By, Bz — and K3Op::point = kPointBonds; their
+// Galerkin product is the same 27 planes, so the levels below are what they always were.
 int build_point_part3(mgcmt_plan* p, const double* point_diag, const double* const* bonds) {
   const char* e = getenv("MGCMT_3D_POINT_MARCH");  // "0": the fine level on the flat kernels (A/B tests)
-  const int march = !(e && e[0] == '0');
-  // the passes of a fine level with bonds that march (kernels_3d_bonds.hip): those that measured faster than their flat form at 256^3
-  const int march_bonds = march ? (kBonds3Jacobi | kBonds3Parity | kBonds3Residual | kBonds3Prolong) : 0;
+  // the passes of the fine level that march (K3Op::pmarch; point3_marching adds the size rule)
+  const int march = e && e[0] == '0' ? 0 : (kMarch3Jacobi | kMarch3Parity | kMarch3Residual | kMarch3Prolong);
   for (size_t l = 0; l < p->levels.size(); ++l) {
     Level& L = p->levels[l];
     K3Op& k = L.dA.k3;
@@ -389,25 +388,24 @@ int build_point_part3(mgcmt_plan* p, const double* point_diag, const double* con
     MG_HIP(hipMalloc((void**)&q, (l == 0 ? (bonds[0] ? 4 : 1) : 27) * N * sizeof(double)));
     L.dA.owned.push_back(q);
     k.pg = q;
-    k.pmarch = march;
+    k.pmarch = l == 0 ? march : 0;
     if (l == 0 && bonds[0]) {
       MG_HIP(hipMemcpy(q, point_diag, N * sizeof(double), hipMemcpyHostToDevice));
       for (int a = 0; a < 3; ++a) MG_HIP(hipMemcpy(q + (a + 1) * N, bonds[a], N * sizeof(double), hipMemcpyHostToDevice));
-      k.point = 3;
-      k.pmarch = march_bonds;
+      k.point = kPointBonds;
       k.pplane = (long)N;
       continue;
     }
     if (l == 0) {
       MG_HIP(hipMemcpy(q, point_diag, N * sizeof(double), hipMemcpyHostToDevice));
-      k.point = 1;
+      k.point = kPointDiag;
       k.pplane = 0;
       continue;
     }
     const K3Op& kf = p->levels[l - 1].dA.k3;
-    launch3p_coarsen(nullptr, kf.n, kf.pg, kf.point == 1 ? 1 : kf.point == 3 ? 4 : 27, kf.pplane, q, (long)N);
+    launch3p_coarsen(nullptr, kf.n, kf.pg, kf.point == kPointDiag ? 1 : kf.point == kPointBonds ? 4 : 27, kf.pplane, q, (long)N);
     MG_TRY(post_launch());
-    k.point = 2;
+    k.point = kPointPlanes;
     k.pplane = (long)N;
   }
   MG_HIP(hipDeviceSynchronize());
@@ -622,15 +620,15 @@ int mgcmt_plan_get_point_stencil(const mgcmt_plan* p, int l, double* out, int64_
   const Level& L = p->levels[l];
   if (p->dim == 3) {
     const K3Op& k3 = L.dA.k3;
-    const int64_t N = L.nr * L.gc, need3 = k3.point == 1 ? N : k3.point == 3 ? 4 * N : 27 * N;  // (D, Bx, By, Bz lie one behind the other)
+    const int64_t N = L.nr * L.gc, need3 = k3.point == kPointDiag ? N : k3.point == kPointBonds ? 4 * N : 27 * N;  // (D, Bx, By, Bz lie one behind the other)
     if (!out || capacity < need3) return fail(MGCMT_ERR_INVALID, "point stencil buffer too small");
     MG_HIP(hipMemcpy(out, k3.pg, (size_t)need3 * sizeof(double), hipMemcpyDeviceToHost));
     return MGCMT_OK;
   }
   const KOp& k = L.dA.k;
-  const int64_t plane = L.nr * L.gc, need = k.point == 1 ? plane : k.point == 3 ? 3 * plane : 9 * plane;
+  const int64_t plane = L.nr * L.gc, need = k.point == kPointDiag ? plane : k.point == kPointBonds ? 3 * plane : 9 * plane;
   if (!out || capacity < need) return fail(MGCMT_ERR_INVALID, "point stencil buffer too small");
-  if (k.point == 3) {  // D, E, S: the interior rows of each padded plane
+  if (k.point == kPointBonds) {  // D, E, S: the interior rows of each padded plane
     for (int a = 0; a < 3; ++a) MG_HIP(hipMemcpy(out + a * plane, k.pg + a * k.pplane, (size_t)plane * sizeof(double), hipMemcpyDeviceToHost));
     return MGCMT_OK;
   }
@@ -687,8 +685,26 @@ int mgcmt_plan3d_level_path(const mgcmt_plan* p, int l, int* kind, int* marching
   MG_TRY(check_level(p, l));
   if (p->dim != 3) return fail(MGCMT_ERR_INVALID, "mgcmt_plan3d_level_path needs a 3-D plan");
   const K3Op& k = p->levels[l].dA.k3;
-  if (kind) *kind = k.point == 2 ? 3 : k.point == 3 ? (k.seven ? 5 : 6) : k.seven ? (k.point == 1 ? 2 : 1) : (k.point == 1 ? 4 : 0);
-  if (marching) *marching = k.point == 3 ? (bonds3_marching(k) ? 1 : 0) : k.point ? (point3_marching(k) ? 1 : 0) : (k.seven && k.n >= 64 && k.n % 64 == 0 ? 1 : 0);
+  int path = 0, march = 0;  // (kinds: include/mgcmt_hip.h)
+  switch (k.point) {
+    case kPointNone:
+      path = k.seven ? 1 : 0;
+      march = k.seven && k.n >= 64 && k.n % 64 == 0;  // the constant level's own kernels (kernels_3d.hip)
+      break;
+    case kPointDiag:
+      path = k.seven ? 2 : 4;
+      march = point3_marching(k) != 0;
+      break;
+    case kPointPlanes:
+      path = 3;
+      break;
+    case kPointBonds:
+      path = k.seven ? 5 : 6;
+      march = point3_marching(k) != 0;
+      break;
+  }
+  if (kind) *kind = path;
+  if (marching) *marching = march;
   return MGCMT_OK;
 }
 
@@ -775,7 +791,7 @@ int mgcmt_level_operator_kind(const mgcmt_plan* p, int l, int* kind) {
   if (!kind) return fail(MGCMT_ERR_INVALID, "null output");
   const KOp& k = p->levels[l].dA.k;
   if (k.point) {
-    *kind = k.point == 1 ? MGCMT_OPK_POINT_DIAG : k.point == 3 ? MGCMT_OPK_POINT_BONDS : MGCMT_OPK_NINE_POINT;
+    *kind = k.point == kPointDiag ? MGCMT_OPK_POINT_DIAG : k.point == kPointBonds ? MGCMT_OPK_POINT_BONDS : MGCMT_OPK_NINE_POINT;
     return MGCMT_OK;
   }
   *kind = k.five_point ? MGCMT_OPK_FIVE_POINT : k.five_diag ? MGCMT_OPK_FIVE_DIAG : k.nine_const ? MGCMT_OPK_NINE_CONST : k.nine_var ? MGCMT_OPK_NINE_VAR : MGCMT_OPK_GENERAL;

@@ -1,27 +1,29 @@
-// 3-D operators with a per-point part, fp64, gfx950: H = -c Laplacian + V(x, y, z) with an arbitrary potential V.
+// 3-D operators with a per-point part, fp64, gfx950: H = -c Laplacian + V(x, y, z) with an arbitrary potential V, or
+// H = -div(w grad) + V with a position-dependent inverse effective mass w.
 //
-// As in 2-D (kernels_pointwise.hip) the Kronecker part keeps its factors and their Galerkin hierarchy and the rest of V is
-// data per point: a diagonal D on the fine level (one vector, 8 B per point, read at the index of the right-hand side) and,
-// under R = R1 (x) R1 (x) R1, P = P1 (x) P1 (x) P1, a 27-point stencil with variable coefficients on every level below —
-// 27 planes per level (K3Op::pg; a thread reads its own point's coefficients, coalesced): 216 B per coarse point, 27/7 of a
-// fine vector summed over all coarse levels (about 4 GiB at 512^3).
+// As in 2-D (kernels_pointwise.hip) the Kronecker part keeps its factors and their Galerkin hierarchy and the rest is data per
+// point.  On the fine level that is a diagonal D (K3Op::point == kPointDiag, mgcmt_plan_create3d_pot: one vector, 8 B per point,
+// read at the index of the right-hand side) or the four planes D, Bx, By, Bz, pplane apart (kPointBonds,
+// mgcmt_plan_create3d_bonds: Bx / By / Bz are added to the two entries between a point and its neighbour at x + 1 / y + 1 / z + 1).
+// Under R = R1 (x) R1 (x) R1, P = P1 (x) P1 (x) P1 either becomes a 27-point stencil with variable coefficients on every level
+// below — 27 planes per level (kPointPlanes; K3Op::pg; a thread reads its own point's coefficients, coalesced): 216 B per coarse
+// point, 27/7 of a fine vector summed over all coarse levels (about 4 GiB at 512^3).
 //
 // This file holds
-//   - the Galerkin product of the per-point part (k3p_coarsen, one thread per coarse point and all 27 of its coefficients);
+//   - the Galerkin product of the per-point part (k3p_coarsen, one thread per coarse point and all 27 of its coefficients;
+//     the diagonal, the four planes of a level with bonds or 27 planes as its source);
 //   - flat kernels, one thread per point, for any such level: apply, weighted Jacobi, one colour stage, residual + full
 //     weighting, prolongation + correction + first Jacobi sweep, the per-point entries of the coarsest level's band matrix.
 //     They evaluate the Kronecker part with eval3's expressions (kernels_3d.hip) and the planes from the same neighbour registers;
-//   - marching kernels for the fine level — constant 7-point Kronecker part plus D, 7/8 of all points —: kernels_3d.hip's
-//     64 x 4 tile and 32-plane chunks with the planes z-1, z, z+1 in registers, D as a fourth stream.
-// The flat and the marching form of the fine level compute every point with ONE set of inline functions (p7_*: the same fma
-// order, the same reciprocal of c0 + D - mu), so their sweeps give the same bits; MGCMT_3D_POINT_MARCH=0 selects the flat form.
-// A fine level with per-point bonds as well (K3Op::point == 3: the planes D, Bx, By, Bz; mgcmt_plan_create3d_bonds) is a third
-// branch of the flat kernels' point (bonds3_point.h), a four-plane source of k3p_coarsen and six more entries per row of
-// k3p_band_add; its marching kernels are kernels_3d_bonds.hip's, to which the launchers below offer every pass first.
-#include "bonds3_point.h"
-#include "fused_kernel.h"
+//   - marching kernels for the fine level — constant 7-point Kronecker part plus D, or plus D and bonds; 7/8 of all points —:
+//     kernels_3d.hip's 64 x 4 tile and 32-plane chunks with the planes z-1, z, z+1 of the thread's column in registers, no LDS,
+//     no halo planes (all three directions are predicated), templated on whether the level has bonds.
+// The flat and the marching form of the fine level compute every point with ONE set of inline functions (seven_point.h: the
+// same fma order, the same reciprocal of c0 + D - mu), so their sweeps give the same bits.  Which passes march is
+// point3_marching (K3Op::pmarch, hierarchy.hip); MGCMT_3D_POINT_MARCH=0 selects the flat form.
 #include "kernels_3d_common.h"
 #include "mgcmt_internal.h"
+#include "seven_point.h"
 
 namespace mgcmt {
 
@@ -29,27 +31,9 @@ namespace {
 
 using namespace k3;
 
-// ---- the fine level's point: constant 7-point Kronecker part + D ------------------------------------------------
-// neighbours outside the grid are passed as zeros
-
-__device__ __forceinline__ double p7_dg(const K3Op& op, double d, double mu) { return (op.c0 - mu) + d; }
-
-// ((A - mu I) v) at the point
-__device__ __forceinline__ double p7_av(const K3Op& op, double dg, double vc, double vzm, double vzp, double vym, double vyp, double vxm,
-                                        double vxp) {
-  double acc = dg * vc;
-  acc = fma(op.czm, vzm, acc);
-  acc = fma(op.czp, vzp, acc);
-  acc = fma(op.cym, vym, acc);
-  acc = fma(op.cyp, vyp, acc);
-  acc = fma(op.cxm, vxm, acc);
-  acc = fma(op.cxp, vxp, acc);
-  return acc;
-}
-
-// v + omega (f - (A - mu I) v) / (c0 + D - mu)
-__device__ __forceinline__ double p7_relax(double omega, double f, double av, double dg, double vc) {
-  return fma(omega * (f - av), fused::fast_reciprocal(dg), vc);
+// the fine level's own form: a constant 7-point Kronecker part plus a per-point row (seven_point.h)
+__host__ __device__ __forceinline__ bool seven_point_row(const K3Op& op) {
+  return op.seven && (op.point == kPointDiag || op.point == kPointBonds);
 }
 
 // ---- any level with a per-point part, one point -------------------------------------------------------------------
@@ -65,18 +49,21 @@ __device__ __forceinline__ PEval eval3p(const K3Op& op, W&& w, long z, long y, l
   const long idx = z * n2 + y * n + x;
   const bool zm = z > 0, zp = z + 1 < n, ym = y > 0, yp = y + 1 < n, xm = x > 0, xp = x + 1 < n;
   PEval r;
-  if (op.point == 1 && op.seven) {
-    r.dg = p7_dg(op, op.pg[idx], mu);
-    r.av = p7_av(op, r.dg, w(z, y, x), zm ? w(z - 1, y, x) : 0.0, zp ? w(z + 1, y, x) : 0.0, ym ? w(z, y - 1, x) : 0.0,
-                 yp ? w(z, y + 1, x) : 0.0, xm ? w(z, y, x - 1) : 0.0, xp ? w(z, y, x + 1) : 0.0);
+  // the fine level's own forms, constant 7-point part + D and the same + bonds (seven_point.h): neighbours outside the grid are
+  // passed as zeros, a bond towards outside is a predicated zero.  (Two branches that differ in the coefficient source only: as
+  // one branch every red-black cycle measured 2 % slower at 256^3, see profiles/r11_fold_3d_point_bonds.md)
+  if (op.point == kPointDiag && op.seven) {
+    r.dg = p7::dg(op, op.pg[idx], mu);
+    r.av = p7::av(p7::coef(op), r.dg, w(z, y, x), zm ? w(z - 1, y, x) : 0.0, zp ? w(z + 1, y, x) : 0.0, ym ? w(z, y - 1, x) : 0.0,
+                  yp ? w(z, y + 1, x) : 0.0, xm ? w(z, y, x - 1) : 0.0, xp ? w(z, y, x + 1) : 0.0);
     return r;
   }
-  if (op.point == 3 && op.seven) {  // constant 7-point part + D + bonds (bonds3_point.h): a bond towards outside is a predicated zero
+  if (op.point == kPointBonds && op.seven) {
     const double* __restrict__ g = op.pg + idx;
     const long pl = op.pplane;
-    const b7::Coef c = b7::coef(op, zm ? g[3 * pl - n2] : 0.0, g[3 * pl], ym ? g[2 * pl - n] : 0.0, g[2 * pl], xm ? g[pl - 1] : 0.0, g[pl]);
-    r.dg = b7::dg(op, g[0], mu);
-    r.av = b7::av(c, r.dg, w(z, y, x), zm ? w(z - 1, y, x) : 0.0, zp ? w(z + 1, y, x) : 0.0, ym ? w(z, y - 1, x) : 0.0,
+    const p7::Coef c = p7::coef(op, zm ? g[3 * pl - n2] : 0.0, g[3 * pl], ym ? g[2 * pl - n] : 0.0, g[2 * pl], xm ? g[pl - 1] : 0.0, g[pl]);
+    r.dg = p7::dg(op, g[0], mu);
+    r.av = p7::av(c, r.dg, w(z, y, x), zm ? w(z - 1, y, x) : 0.0, zp ? w(z + 1, y, x) : 0.0, ym ? w(z, y - 1, x) : 0.0,
                   yp ? w(z, y + 1, x) : 0.0, xm ? w(z, y, x - 1) : 0.0, xp ? w(z, y, x + 1) : 0.0);
     return r;
   }
@@ -116,10 +103,10 @@ __device__ __forceinline__ PEval eval3p(const K3Op& op, W&& w, long z, long y, l
     }
   }
   const double* __restrict__ g = op.pg + idx;
-  if (op.point == 1) {  // a diagonal on top of general terms
+  if (op.point == kPointDiag) {  // a diagonal on top of general terms
     acc += g[0] * wn[1][1][1];
     diag += g[0];
-  } else if (op.point == 3) {  // a diagonal and bonds on top of general terms: the six neighbour products and the centre
+  } else if (op.point == kPointBonds) {  // a diagonal and bonds on top of general terms: the six neighbour products and the centre
     const long pl = op.pplane;
     double pa = g[0] * wn[1][1][1];
     pa += (zm ? g[3 * pl - n2] : 0.0) * wn[0][1][1];
@@ -154,8 +141,7 @@ __device__ __forceinline__ PEval eval3p(const K3Op& op, W&& w, long z, long y, l
 }
 
 __device__ __forceinline__ double relax3p(const K3Op& op, const PEval& e, double omega, double f, double vc) {
-  if (op.point == 1 && op.seven) return p7_relax(omega, f, e.av, e.dg, vc);
-  if (op.point == 3 && op.seven) return b7::relax(omega, f, e.av, e.dg, vc);
+  if (seven_point_row(op)) return p7::relax(omega, f, e.av, e.dg, vc);
   return vc + omega * (f - e.av) / e.dg;
 }
 
@@ -269,11 +255,11 @@ __global__ void k3p_band_add(K3Op op, KBand b) {
   double* ab = b.ab + q * b.ab_stride;
   const long n = op.n, n2 = n * n;
   const long z = r / n2, y = (r / n) % n, x = r % n;
-  if (op.point == 1) {
+  if (op.point == kPointDiag) {
     ab[r * b.width + b.kl] += op.pg[r];
     return;
   }
-  if (op.point == 3) {  // D and the six bonds (a plan whose fine level is also its coarsest)
+  if (op.point == kPointBonds) {  // D and the six bonds (a plan whose fine level is also its coarsest)
     const long pl = op.pplane;
     double* row = ab + r * b.width + b.kl;
     row[0] += op.pg[r];
@@ -379,11 +365,15 @@ __global__ void __launch_bounds__(kFlatThreads) k3p_coarsen(long fn, const doubl
   for (int j = 0; j < 27; ++j) coarse[j * cplane + I] = out[j];
 }
 
-// ---- marching kernels: constant 7-point part + D, n a multiple of 64 ---------------------------------------------------
-// k3m_sweep's geometry (kernels_3d.hip) with D as a fourth stream, read once per updated point at the address of f.
+// ---- marching kernels: constant 7-point part + per-point row, n a multiple of 64 ---------------------------------------
+// k3m_sweep's geometry (kernels_3d.hip) with D as a fourth stream, read once per updated point at the address of f.  BONDS:
+// Bx, By, Bz are three more streams read there; Bx(x-1) and By(y-1) are one more 8-byte load each from the same or the
+// neighbouring row's cache line; Bz(z-1) is carried from the previous plane step where every plane is updated (the Jacobi and
+// the prolongation pass: a predicated load of its own at a chunk's first plane) and a load of its own in a parity stage, which
+// updates every other point.  A bond towards a point outside the grid is a predicated zero.
 // stage 0: weighted Jacobi vin -> vout; stage 1: the parity class (x + y + z) % 2 == par of the red-black sweep, in place
-// (exact on a 7-point operator with any diagonal: same-parity points do not couple)
-template <int STAGE>
+// (exact on a 7-point operator with any coefficients: same-parity points do not couple)
+template <bool BONDS, int STAGE>
 __global__ void __launch_bounds__(kTileX* kTileY) k3pm_sweep(K3Op op, KVec vin, KVec f, KVec vout, const double* __restrict__ shifts,
                                                            double omega, int par, int nchunks) {
   const long n = op.n, n2 = n * n;
@@ -394,20 +384,35 @@ __global__ void __launch_bounds__(kTileX* kTileY) k3pm_sweep(K3Op op, KVec vin, 
   const double* v = vin.p + q * vin.stride;
   const double* fq = f.p + q * f.stride;
   const double* __restrict__ dq = op.pg;
+  const double* __restrict__ bxq = op.pg + op.pplane;  // (the three bond streams: read only where BONDS)
+  const double* __restrict__ byq = op.pg + 2 * op.pplane;
+  const double* __restrict__ bzq = op.pg + 3 * op.pplane;
   double* out = vout.p + q * vout.stride;
   const double mu = shifts[q];
   const bool xm = x > 0, xp = x + 1 < n, ym = y > 0, yp = y + 1 < n;
   const long col = y * n + x;
   double vm = z0 > 0 ? v[(z0 - 1) * n2 + col] : 0.0;
   double vc = v[z0 * n2 + col];
+  double bzm = 0.0;  // Bz(z-1) of the column
+  if constexpr (BONDS && STAGE == 0) bzm = z0 > 0 ? bzq[(z0 - 1) * n2 + col] : 0.0;
   for (int t = 0; t < kChunkZ; ++t) {
     const long z = z0 + t;
-    const double vp = z + 1 < n ? v[(z + 1) * n2 + col] : 0.0;
+    const long i = z * n2 + col;
+    const double vp = z + 1 < n ? v[i + n2] : 0.0;
     if (STAGE == 0 || (((x + y + z) & 1) == par)) {
-      const double* c = v + z * n2 + col;
-      const double dg = p7_dg(op, dq[z * n2 + col], mu);
-      const double av = p7_av(op, dg, vc, vm, vp, ym ? c[-n] : 0.0, yp ? c[n] : 0.0, xm ? c[-1] : 0.0, xp ? c[1] : 0.0);
-      out[z * n2 + col] = p7_relax(omega, fq[z * n2 + col], av, dg, vc);
+      const double* c = v + i;
+      p7::Coef cf;
+      if constexpr (BONDS) {
+        const double bzp = bzq[i];
+        if (STAGE != 0) bzm = z > 0 ? bzq[i - n2] : 0.0;
+        cf = p7::coef(op, bzm, bzp, ym ? byq[i - n] : 0.0, byq[i], xm ? bxq[i - 1] : 0.0, bxq[i]);
+        if (STAGE == 0) bzm = bzp;
+      } else {
+        cf = p7::coef(op);
+      }
+      const double dg = p7::dg(op, dq[i], mu);
+      const double av = p7::av(cf, dg, vc, vm, vp, ym ? c[-n] : 0.0, yp ? c[n] : 0.0, xm ? c[-1] : 0.0, xp ? c[1] : 0.0);
+      out[i] = p7::relax(omega, fq[i], av, dg, vc);
     }
     vm = vc;
     vc = vp;
@@ -416,7 +421,9 @@ __global__ void __launch_bounds__(kTileX* kTileY) k3pm_sweep(K3Op op, KVec vin, 
 
 // residual + restriction, marching: a thread owns one coarse x-y column (X, Y) of a chunk of coarse planes and keeps the
 // x-y weighted residual of the fine plane 2Z + 2 (shared with the next coarse plane) in a register.  k3m_residual_restrict's
-// structure: v's planes are NOT held in registers here — every plane's nine residuals are re-formed from (cached) loads
+// structure: v's planes are NOT held in registers here — every plane's nine residuals are re-formed from (cached) loads, the
+// bonds among them
+template <bool BONDS>
 __global__ void __launch_bounds__(kTileX* kTileY) k3pm_residual_restrict(K3Op op, KVec v, KVec f, KVec fc, KVec vc,
                                                                        const double* __restrict__ shifts, int nchunks) {
   const long n = op.n, n2 = n * n, nc = n / 2, nc2 = nc * nc;
@@ -428,6 +435,7 @@ __global__ void __launch_bounds__(kTileX* kTileY) k3pm_residual_restrict(K3Op op
   const double* vq = v.p + q * v.stride;
   const double* fq = f.p + q * f.stride;
   const double* __restrict__ dq = op.pg;
+  const long pl = op.pplane;
   const double mu = shifts[q];
   // x-y full weighting of the residual on fine plane z
   auto plane = [&](long z) {
@@ -441,9 +449,15 @@ __global__ void __launch_bounds__(kTileX* kTileY) k3pm_residual_restrict(K3Op op
         if (x >= n) continue;
         const long i = z * n2 + y * n + x;
         const double* p = vq + i;
-        const double dg = p7_dg(op, dq[i], mu);
-        const double av = p7_av(op, dg, p[0], z > 0 ? p[-n2] : 0.0, z + 1 < n ? p[n2] : 0.0, y > 0 ? p[-n] : 0.0, y + 1 < n ? p[n] : 0.0,
-                                x > 0 ? p[-1] : 0.0, x + 1 < n ? p[1] : 0.0);
+        const double* g = dq + i;
+        p7::Coef cf;
+        if constexpr (BONDS)
+          cf = p7::coef(op, z > 0 ? g[3 * pl - n2] : 0.0, g[3 * pl], y > 0 ? g[2 * pl - n] : 0.0, g[2 * pl], x > 0 ? g[pl - 1] : 0.0, g[pl]);
+        else
+          cf = p7::coef(op);
+        const double dg = p7::dg(op, g[0], mu);
+        const double av = p7::av(cf, dg, p[0], z > 0 ? p[-n2] : 0.0, z + 1 < n ? p[n2] : 0.0, y > 0 ? p[-n] : 0.0, y + 1 < n ? p[n] : 0.0,
+                                 x > 0 ? p[-1] : 0.0, x + 1 < n ? p[1] : 0.0);
         pb += (c == 1 ? 0.5 : 0.25) * (fq[i] - av);
       }
       pa += (b == 1 ? 0.5 : 0.25) * pb;
@@ -463,6 +477,7 @@ __global__ void __launch_bounds__(kTileX* kTileY) k3pm_residual_restrict(K3Op op
 
 // prolongation + correction + one weighted-Jacobi sweep, marching: w = v + P e of the planes z-1, z, z+1 of the thread's
 // column in registers
+template <bool BONDS>
 __global__ void __launch_bounds__(kTileX* kTileY) k3pm_prolong_jacobi(K3Op op, KVec e, KVec vin, KVec f, KVec vout,
                                                                     const double* __restrict__ shifts, double omega, int nchunks) {
   const long n = op.n, n2 = n * n;
@@ -473,19 +488,33 @@ __global__ void __launch_bounds__(kTileX* kTileY) k3pm_prolong_jacobi(K3Op op, K
   const LoadProlonged w{vin.p + q * vin.stride, e.p + q * e.stride, n};
   const double* fq = f.p + q * f.stride;
   const double* __restrict__ dq = op.pg;
+  const double* __restrict__ bxq = op.pg + op.pplane;  // (the three bond streams: read only where BONDS)
+  const double* __restrict__ byq = op.pg + 2 * op.pplane;
+  const double* __restrict__ bzq = op.pg + 3 * op.pplane;
   double* out = vout.p + q * vout.stride;
   const double mu = shifts[q];
   const bool xm = x > 0, xp = x + 1 < n, ym = y > 0, yp = y + 1 < n;
   const long col = y * n + x;
   double wm = z0 > 0 ? w(z0 - 1, y, x) : 0.0;
   double wc = w(z0, y, x);
+  double bzm = 0.0;  // Bz(z-1) of the column
+  if constexpr (BONDS) bzm = z0 > 0 ? bzq[(z0 - 1) * n2 + col] : 0.0;
   for (int t = 0; t < kChunkZ; ++t) {
     const long z = z0 + t;
+    const long i = z * n2 + col;
     const double wp = z + 1 < n ? w(z + 1, y, x) : 0.0;
-    const double dg = p7_dg(op, dq[z * n2 + col], mu);
-    const double av = p7_av(op, dg, wc, wm, wp, ym ? w(z, y - 1, x) : 0.0, yp ? w(z, y + 1, x) : 0.0, xm ? w(z, y, x - 1) : 0.0,
-                            xp ? w(z, y, x + 1) : 0.0);
-    out[z * n2 + col] = p7_relax(omega, fq[z * n2 + col], av, dg, wc);
+    p7::Coef cf;
+    if constexpr (BONDS) {
+      const double bzp = bzq[i];
+      cf = p7::coef(op, bzm, bzp, ym ? byq[i - n] : 0.0, byq[i], xm ? bxq[i - 1] : 0.0, bxq[i]);
+      bzm = bzp;
+    } else {
+      cf = p7::coef(op);
+    }
+    const double dg = p7::dg(op, dq[i], mu);
+    const double av = p7::av(cf, dg, wc, wm, wp, ym ? w(z, y - 1, x) : 0.0, yp ? w(z, y + 1, x) : 0.0, xm ? w(z, y, x - 1) : 0.0,
+                             xp ? w(z, y, x + 1) : 0.0);
+    out[i] = p7::relax(omega, fq[i], av, dg, wc);
     wm = wc;
     wc = wp;
   }
@@ -497,18 +526,16 @@ dim3 march_grid(const K3Op& op, int k) {
 
 }  // namespace
 
-bool point3_marching(const K3Op& op) { return op.point == 1 && op.seven && op.pmarch && op.n >= kTileX && op.n % kTileX == 0; }
-
-// (a level with bonds, op.point == 3: the launchers below offer every pass to kernels_3d_bonds.hip first)
+int point3_marching(const K3Op& op) { return seven_point_row(op) && op.n >= kTileX && op.n % kTileX == 0 ? op.pmarch : 0; }
 
 void launch3p_apply(hipStream_t s, const K3Op& op, KVec src, KVec dst, const double* shifts, int k) {
   hipLaunchKernelGGL(k3p_apply, flat_grid(op.n * op.n * op.n, k), dim3(kFlatThreads), 0, s, op, src, dst, shifts);
 }
 
 void launch3p_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k) {
-  if (op.point == 3 && launch3b_wjacobi(s, op, vin, f, vout, shifts, omega, k)) return;
-  if (point3_marching(op)) {
-    hipLaunchKernelGGL(k3pm_sweep<0>, march_grid(op, k), dim3(kTileX, kTileY), 0, s, op, vin, f, vout, shifts, omega, 0, (int)(op.n / kChunkZ));
+  if (point3_marching(op) & kMarch3Jacobi) {
+    const auto kern = op.point == kPointBonds ? k3pm_sweep<true, 0> : k3pm_sweep<false, 0>;
+    hipLaunchKernelGGL(kern, march_grid(op, k), dim3(kTileX, kTileY), 0, s, op, vin, f, vout, shifts, omega, 0, (int)(op.n / kChunkZ));
     return;
   }
   hipLaunchKernelGGL(k3p_wjacobi, flat_grid(op.n * op.n * op.n, k), dim3(kFlatThreads), 0, s, op, vin, f, vout, shifts, omega);
@@ -517,11 +544,11 @@ void launch3p_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout
 void launch3p_mc_sweep(hipStream_t s, const K3Op& op, KVec v, KVec f, const double* shifts, double omega, int k) {
   // the order of launch3_mc_sweep: odd coordinate sum first
   static const int order[8][3] = {{0, 0, 1}, {0, 1, 0}, {1, 0, 0}, {1, 1, 1}, {0, 0, 0}, {0, 1, 1}, {1, 0, 1}, {1, 1, 0}};
-  if ((op.point == 1 || op.point == 3) && op.seven) {  // a 7-point operator with any coefficients does not couple points of one parity: two stages
+  if (seven_point_row(op)) {  // a 7-point operator with any coefficients does not couple points of one parity: two stages
+    const auto kern = op.point == kPointBonds ? k3pm_sweep<true, 1> : k3pm_sweep<false, 1>;
     for (int par = 1; par >= 0; --par) {
-      if (op.point == 3 && launch3b_parity(s, op, v, f, shifts, omega, par, k)) continue;
-      if (point3_marching(op))
-        hipLaunchKernelGGL(k3pm_sweep<1>, march_grid(op, k), dim3(kTileX, kTileY), 0, s, op, v, f, v, shifts, omega, par, (int)(op.n / kChunkZ));
+      if (point3_marching(op) & kMarch3Parity)
+        hipLaunchKernelGGL(kern, march_grid(op, k), dim3(kTileX, kTileY), 0, s, op, v, f, v, shifts, omega, par, (int)(op.n / kChunkZ));
       else
         hipLaunchKernelGGL(k3p_colour, flat_grid(op.n * op.n * op.n, k), dim3(kFlatThreads), 0, s, op, v, f, shifts, omega, -1, par, 0);
     }
@@ -534,10 +561,10 @@ void launch3p_mc_sweep(hipStream_t s, const K3Op& op, KVec v, KVec f, const doub
 
 void launch3p_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k) {
   const long nc = op.n / 2;
-  if (op.point == 3 && launch3b_residual_restrict(s, op, v, f, fc, vc, shifts, k)) return;
-  if (point3_marching(op)) {
+  if (point3_marching(op) & kMarch3Residual) {
     const int nch = (int)(op.n / kChunkZ);
-    hipLaunchKernelGGL(k3pm_residual_restrict, dim3((unsigned)((nc + kTileX - 1) / kTileX), (unsigned)((nc + kTileY - 1) / kTileY), (unsigned)(nch * k)),
+    const auto kern = op.point == kPointBonds ? k3pm_residual_restrict<true> : k3pm_residual_restrict<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((nc + kTileX - 1) / kTileX), (unsigned)((nc + kTileY - 1) / kTileY), (unsigned)(nch * k)),
                        dim3(kTileX, kTileY), 0, s, op, v, f, fc, vc, shifts, nch);
     return;
   }
@@ -545,9 +572,9 @@ void launch3p_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, K
 }
 
 void launch3p_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k) {
-  if (op.point == 3 && launch3b_prolong_jacobi(s, op, e, vin, f, vout, shifts, omega, k)) return;
-  if (point3_marching(op)) {
-    hipLaunchKernelGGL(k3pm_prolong_jacobi, march_grid(op, k), dim3(kTileX, kTileY), 0, s, op, e, vin, f, vout, shifts, omega, (int)(op.n / kChunkZ));
+  if (point3_marching(op) & kMarch3Prolong) {
+    const auto kern = op.point == kPointBonds ? k3pm_prolong_jacobi<true> : k3pm_prolong_jacobi<false>;
+    hipLaunchKernelGGL(kern, march_grid(op, k), dim3(kTileX, kTileY), 0, s, op, e, vin, f, vout, shifts, omega, (int)(op.n / kChunkZ));
     return;
   }
   hipLaunchKernelGGL(k3p_prolong_jacobi, flat_grid(op.n * op.n * op.n, k), dim3(kFlatThreads), 0, s, op, e, vin, f, vout, shifts, omega);

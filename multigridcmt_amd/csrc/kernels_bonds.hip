@@ -1,4 +1,4 @@
-// Marching kernels of the fine level of a plan with per-point bonds (KOp::point == 3, mgcmt_plan_create_bonds), fp64, gfx950:
+// Marching kernels of the fine level of a plan with per-point bonds (KOp::point == kPointBonds, mgcmt_plan_create_bonds), fp64, gfx950:
 // H = -div(w grad) + V, a symmetric 5-point operator whose off-diagonals vary from point to point.
 //
 // The mapping is k_apply_march's (kernels_stencil.hip): a thread owns two adjacent columns, so every access to v, f and
@@ -241,7 +241,7 @@ inline dim3 sweep_grid(const KGrid& g, dim3 b, int k) {
 }  // namespace
 
 bool bonds_marching(const KGrid& g, const KOp& op) {
-  return op.point == 3 && op.pmarch && op.five_point && g.coarsen_rows && g.nc >= kBondMinCols && (g.nc & 1) == 0 && g.nr >= 2 && (g.nr & 1) == 0 &&
+  return op.point == kPointBonds && op.pmarch && op.five_point && g.coarsen_rows && g.nc >= kBondMinCols && (g.nc & 1) == 0 && g.nr >= 2 && (g.nr & 1) == 0 &&
          (((uintptr_t)op.pg) & 15) == 0 && (op.pld & 1) == 0 && (op.pplane & 1) == 0;
 }
 

@@ -16,7 +16,7 @@ bool fused_supported(const KGrid& g, const KOp& op) {
   if (!g.coarsen_rows) return fused1d_supported(g, op);
   // a per-point part (mgcmt_plan_create_pot): the fine level — a constant 5-point operator plus a diagonal, Op5P — is
   // covered; the variable 9-point levels below run the one-launch-per-operation kernels of kernels_pointwise.hip
-  if (op.point && !(op.point == 1 && op.five_point)) return false;
+  if (op.point && !(op.point == kPointDiag && op.five_point)) return false;
   return g.coarsen_rows && g.nr >= 4 && g.nc >= kFusedMinCols && (g.nc & 1) == 0 && (g.nr & 1) == 0 && (op.five_point || op.five_diag || op.nine_const || op.nine_var || op.nterms == 2 || op.nterms == 3);
 }
 

@@ -1,4 +1,4 @@
-// Tile kernels of a nine-plane level (KOp::point == 2), fp64, gfx950: level 0 of mgcmt_plan_create_nine — H = -div(W grad) + V
+// Tile kernels of a nine-plane level (KOp::point == kPointPlanes), fp64, gfx950: level 0 of mgcmt_plan_create_nine — H = -div(W grad) + V
 // with a position-dependent 2 x 2 inverse-mass tensor W, a symmetric 9-point operator with per-point coefficients — and, with
 // MGCMT_NINE_TILE=2, the Galerkin levels of any plan with a per-point part.
 //
@@ -218,7 +218,7 @@ inline dim3 tile_grid(long nr, long nc, int tr, int tc, int k) { return dim3((un
 }  // namespace
 
 int nine_tiled(const KGrid& g, const KOp& op) {
-  if (op.point != 2 || !g.coarsen_rows || g.nc < kNineMinCols || g.nr < 2) return 0;
+  if (op.point != kPointPlanes || !g.coarsen_rows || g.nc < kNineMinCols || g.nr < 2) return 0;
   return op.pmarch & (kNineColour | kNineJacobi | kNineResidual);
 }
 

@@ -41,7 +41,7 @@ __device__ __forceinline__ PointOp eval_five_diag(const KOp& op, const double* _
   return r;
 }
 
-// Fine level of a plan with per-point bonds (point == 3): constant 5-point Kronecker part plus the planes D, E, S.  The
+// Fine level of a plan with per-point bonds (point == kPointBonds): constant 5-point Kronecker part plus the planes D, E, S.  The
 // expressions are bonds_point.h's, which the marching kernels (kernels_bonds.hip) share: the same bits in either form.
 // Row -1 of the plane S is a halo row of zeros; column -1 is predicated.
 __device__ __forceinline__ PointOp eval_five_bonds(const KOp& op, const double* __restrict__ v, long nc, long i, long j, double mu) {
@@ -73,7 +73,7 @@ __device__ __forceinline__ nine::Nb neighbours(const double* __restrict__ c, lon
   return v;
 }
 
-// Fine level of a plan with a per-point 9-point stencil (mgcmt_plan_create_nine; point == 2): constant 5-point Kronecker part
+// Fine level of a plan with a per-point 9-point stencil (mgcmt_plan_create_nine; point == kPointPlanes): constant 5-point Kronecker part
 // plus the nine planes.  The expressions are nine_point.h's, which the tile kernels (kernels_nine_tile.hip) share: the same
 // bits in either form.
 __device__ __forceinline__ PointOp eval_five_nine(const KOp& op, const double* __restrict__ v, long nc, long i, long j, double mu) {
@@ -96,9 +96,9 @@ __device__ __forceinline__ PointOp eval_general(const KOp& op, const double* __r
   double off = 0.0, diag = 0.0;
   nine::kron_terms(op, i, j, nb, off, diag);
   const double* __restrict__ g = op.pg + i * op.pld + j;
-  if (op.point == 1) {
+  if (op.point == kPointDiag) {
     diag += g[0];
-  } else if (op.point == 3) {
+  } else if (op.point == kPointBonds) {
     const double* __restrict__ ge = g + op.pplane;
     const double* __restrict__ gs = g + 2 * op.pplane;
     off += bonds::neighbour_sum(0.0, 0.0, j > 0 ? ge[-1] : 0.0, ge[0], gs[-op.pld], gs[0], nb.w, nb.e, nb.n, nb.s);
@@ -116,9 +116,9 @@ __device__ __forceinline__ PointOp eval_general(const KOp& op, const double* __r
 }
 
 __device__ __forceinline__ PointOp eval_point_pw(const KOp& op, const double* __restrict__ v, long nc, long i, long j, double mu) {
-  if (op.point == 3 && op.five_point) return eval_five_bonds(op, v, nc, i, j, mu);
-  if (op.point == 2 && op.five_point) return eval_five_nine(op, v, nc, i, j, mu);
-  return (op.point == 1 && op.five_point) ? eval_five_diag(op, v, nc, i, j, mu) : eval_general(op, v, nc, i, j, mu);
+  if (op.point == kPointBonds && op.five_point) return eval_five_bonds(op, v, nc, i, j, mu);
+  if (op.point == kPointPlanes && op.five_point) return eval_five_nine(op, v, nc, i, j, mu);
+  return (op.point == kPointDiag && op.five_point) ? eval_five_diag(op, v, nc, i, j, mu) : eval_general(op, v, nc, i, j, mu);
 }
 
 // dst = (A - mu I) src
@@ -177,11 +177,11 @@ __global__ void k_pw_band_add(KGrid g, KOp op, KBand b) {
   const long nc = g.nc;
   const long i = r / nc, j = r % nc;
   const double* gp = op.pg + i * op.pld + j;
-  if (op.point == 1) {
+  if (op.point == kPointDiag) {
     ab[r * b.width + b.kl] += gp[0];
     return;
   }
-  if (op.point == 3) {  // a single-level plan: the diagonal and the four bonds of the row
+  if (op.point == kPointBonds) {  // a single-level plan: the diagonal and the four bonds of the row
     const double* ge = gp + op.pplane;
     const double* gs = gp + 2 * op.pplane;
     ab[r * b.width + b.kl] += gp[0];
@@ -292,7 +292,7 @@ bool launch_point_mc_sweep(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVe
 }
 
 bool launch_point_residual_restrict(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k) {
-  if (op.point == 3) return launch_bonds_residual_restrict(s, g, op, v, f, fc, vc, shifts, k);
+  if (op.point == kPointBonds) return launch_bonds_residual_restrict(s, g, op, v, f, fc, vc, shifts, k);
   return launch_nine_residual_restrict(s, g, op, v, f, fc, vc, shifts, k);
 }
 

@@ -14,6 +14,9 @@ constexpr int kMaxTerms = MGCMT_MAX_TERMS;
 constexpr int kMaxVec = 32;  // upper bound on simultaneous vectors of one launch
 constexpr int kMaxStoreVec = MGCMT_MAX_STORE_VEC;  // ... and on the vectors a plan keeps per slot (only the block entries see those beyond kMaxVec)
 
+// KOp::point / K3Op::point: the kind of per-point part a level has on top of its Kronecker terms (the layouts: see the structs)
+constexpr int kPointNone = 0, kPointDiag = 1, kPointPlanes = 2, kPointBonds = 3;
+
 // Operator of one level as the kernels see it:  A = sum_m X_m (x) Y_m  (shift applied separately).
 // X[m] / Y[m] point at element 0 of the `lower` array; `diag` is at +ldx, `upper` at +2*ldx.
 // Row factors are stored with the level's halo count of entries before element 0 and after element nr-1 (the local
@@ -78,12 +81,12 @@ struct K3Op {
   // diagonal D(z, y, x) = pg[idx] (the fine level, g^3 numbers at the index of the right-hand side); 2: a 27-point stencil G
   // (the Galerkin levels R D P): the coefficient of v(z + a - 1, y + b - 1, x + c - 1) in row idx is
   // pg[(9 a + 3 b + c) * pplane + idx], zero towards points outside the grid.  The flags above describe the Kronecker part
-  // alone.  pmarch: a constant 7-point level with a diagonal takes the marching kernels where its size allows
-  // (MGCMT_3D_POINT_MARCH, read at plan creation).  3: a diagonal and bonds (mgcmt_plan_create3d_bonds; the fine level,
-  // kernels_3d_bonds.hip): four planes of g^3 numbers, pplane apart, no halo — D = pg[idx], Bx = pg[pplane + idx] added to the
-  // two entries between (z, y, x) and (z, y, x + 1), By = pg[2 pplane + idx] towards (z, y + 1, x), Bz = pg[3 pplane + idx]
-  // towards (z + 1, y, x); Bx(x = n - 1) = By(y = n - 1) = Bz(z = n - 1) = 0, a bond read at x - 1 < 0 etc. is a predicated
-  // zero.  pmarch is then the set of passes (kBonds3*) that march where the level's size allows.
+  // alone.  3: a diagonal and bonds (mgcmt_plan_create3d_bonds; the fine level): four planes of g^3 numbers, pplane apart, no
+  // halo — D = pg[idx], Bx = pg[pplane + idx] added to the two entries between (z, y, x) and (z, y, x + 1),
+  // By = pg[2 pplane + idx] towards (z, y + 1, x), Bz = pg[3 pplane + idx] towards (z + 1, y, x);
+  // Bx(x = n - 1) = By(y = n - 1) = Bz(z = n - 1) = 0, a bond read at x - 1 < 0 etc. is a predicated zero.
+  // pmarch: the set of passes (kMarch3*) of a fine level, 1 or 3, that take the marching kernels where the level's Kronecker
+  // part and size allow (point3_marching; MGCMT_3D_POINT_MARCH, read at plan creation: hierarchy.hip).
   int point, pmarch;
   const double* pg;
   long pplane;
@@ -125,7 +128,7 @@ struct KBand;
 void launch_point_band_add(hipStream_t s, KGrid g, KOp op, const KBand& b, int k);
 void launch_point_coarsen(hipStream_t s, long fnr, long fnc, const double* fine, int fine_planes, long fld, long fplane, double* coarse, long cld,
                           long cplane);
-// a level with per-point bonds (op.point == 3) as a row march (kernels_bonds.hip; bonds_marching: a constant 5-point
+// a level with per-point bonds (op.point == kPointBonds) as a row march (kernels_bonds.hip; bonds_marching: a constant 5-point
 // Kronecker part, at least 128 columns, even sizes, marching not switched off).  Every launcher returns false — nothing
 // launched — where the level or the vectors' alignment rule the march out; the flat kernels above take the level then.
 // parity: 1 = the colours (0,1), (1,0) of the multicolour order, 0 = (0,0), (1,1) — two launches are one sweep.
@@ -135,7 +138,7 @@ bool launch_bonds_apply(hipStream_t s, KGrid g, KOp op, KVec src, KVec dst, cons
 bool launch_bonds_wjacobi(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
 bool launch_bonds_parity(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, const double* shifts, double omega, int parity, int k);
 bool launch_bonds_residual_restrict(hipStream_t s, KGrid g, KOp op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k);
-// a nine-plane level (op.point == 2) on the tile kernels (kernels_nine_tile.hip): a workgroup stages v on its tile plus the
+// a nine-plane level (op.point == kPointPlanes) on the tile kernels (kernels_nine_tile.hip): a workgroup stages v on its tile plus the
 // stages' rings in LDS, runs every stage there and stores the tile — out of place, vin -> vout, nothing between workgroups.
 // nine_tiled: the passes (kNine* bits of op.pmarch) that tile on this level — at least 128 columns, rows coarsened — or 0; a
 // launcher returns false, nothing launched, where its pass stays flat.  launch_nine_wjacobi: nsweep = 1 or 2 weighted-Jacobi
@@ -326,21 +329,14 @@ void launch3_prolong(hipStream_t s, long n, KVec e, KVec dst, int accumulate, in
 void launch3_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
 void launch3_band_assemble(hipStream_t s, const K3Op& op, const double* shifts, KBand b, int k);
 // the same for a level with a per-point part (op.point; kernels_3d_point.hip) — the launchers above hand over —: flat
-// kernels for the 27-plane Galerkin levels, flat and marching ones for the constant 7-point fine level with a diagonal; the
+// kernels for the 27-plane Galerkin levels, flat and marching ones for the constant 7-point fine level with a diagonal or with bonds; the
 // per-point entries added into the assembled band matrix of the coarsest level; and the Galerkin product of the per-point
 // part: coarse <- R G P for the 27 planes (fine_planes = 27), the diagonal (fine_planes = 1) or the planes D, Bx, By, Bz
 // (fine_planes = 4) of a level of fn^3 points
-bool point3_marching(const K3Op& op);
-// a level with per-point bonds (op.point == 3): kernels_3d_point.hip's flat kernels run it, and its launchers offer every pass
-// to the marching kernels of kernels_3d_bonds.hip first.  bonds3_marching: the passes (kBonds3* bits of op.pmarch) that march
-// on this level — a constant 7-point Kronecker part, n a multiple of 64 — or 0; a launcher returns false, nothing launched,
-// where its pass stays flat.  launch3b_parity: one parity class of the red-black sweep, in place.
-constexpr int kBonds3Jacobi = 1, kBonds3Parity = 2, kBonds3Residual = 4, kBonds3Prolong = 8;
-int bonds3_marching(const K3Op& op);
-bool launch3b_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
-bool launch3b_parity(hipStream_t s, const K3Op& op, KVec v, KVec f, const double* shifts, double omega, int par, int k);
-bool launch3b_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k);
-bool launch3b_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
+// point3_marching: the passes (kMarch3* bits of op.pmarch) that march on this level — a constant 7-point Kronecker part with
+// a diagonal or with bonds, n a multiple of 64 — or 0; the other passes, and apply, run the flat kernels.
+constexpr int kMarch3Jacobi = 1, kMarch3Parity = 2, kMarch3Residual = 4, kMarch3Prolong = 8;
+int point3_marching(const K3Op& op);
 void launch3p_apply(hipStream_t s, const K3Op& op, KVec src, KVec dst, const double* shifts, int k);
 void launch3p_wjacobi(hipStream_t s, const K3Op& op, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
 void launch3p_mc_sweep(hipStream_t s, const K3Op& op, KVec v, KVec f, const double* shifts, double omega, int k);

@@ -1,4 +1,4 @@
-// One point of (A - mu I) for a 9-point operator with per-point coefficients (KOp::point == 2): the Kronecker part plus nine
+// One point of (A - mu I) for a 9-point operator with per-point coefficients (KOp::point == kPointPlanes): the Kronecker part plus nine
 // planes G, the coefficient of v(i + a - 1, j + b - 1) in row (i, j) being G[3 a + b](i, j) — the Galerkin levels of every plan
 // with a per-point part, and level 0 of mgcmt_plan_create_nine (H = -div(W grad) + V with a 2 x 2 inverse-mass tensor W).
 //

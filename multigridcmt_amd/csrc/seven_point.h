@@ -1,20 +1,24 @@
-// One point of a 3-D level with per-point bonds (K3Op::point == 3, mgcmt_plan_create3d_bonds): a constant 7-point Kronecker
-// part plus the planes D, Bx, By, Bz.  The flat kernels (kernels_3d_point.hip) and the marching kernels
-// (kernels_3d_bonds.hip) compute every point with THESE functions from the same values — the same sums, the same fma order
-// (p7_av's: z-, z+, y-, y+, x-, x+), the same reciprocal of c0 + D - mu — so their sweeps give the same bits.
-// A bond towards a point outside the grid is passed as zero, and so is that point's value.
+// One point of a 3-D fine level with a per-point part: a constant 7-point Kronecker part plus a diagonal D (K3Op::point ==
+// kPointDiag, mgcmt_plan_create3d_pot) or plus the planes D, Bx, By, Bz (kPointBonds, mgcmt_plan_create3d_bonds).  The flat and
+// the marching kernels of kernels_3d_point.hip compute every point of both kinds with THESE functions from the same values —
+// the same sums, the same fma order (z-, z+, y-, y+, x-, x+), the same reciprocal of c0 + D - mu — so their sweeps give the
+// same bits.  A neighbour outside the grid is passed as zero, and so is the bond towards it.
 #pragma once
 #include "fused_kernel.h"
 #include "mgcmt_internal.h"
 
 namespace mgcmt {
-namespace b7 {
+namespace p7 {
 
+// the six off-diagonal entries of the point's row
 struct Coef {
   double zm, zp, ym, yp, xm, xp;
 };
 
-// the six off-diagonal entries of the point's row: bzm = Bz(z-1, y, x), bzp = Bz(z, y, x), and so on
+// a diagonal alone: the operator's constants as they are (not constant + 0.0, which would turn a -0.0 into +0.0)
+__device__ __forceinline__ Coef coef(const K3Op& op) { return Coef{op.czm, op.czp, op.cym, op.cyp, op.cxm, op.cxp}; }
+
+// with bonds: bzm = Bz(z-1, y, x), bzp = Bz(z, y, x), and so on
 __device__ __forceinline__ Coef coef(const K3Op& op, double bzm, double bzp, double bym, double byp, double bxm, double bxp) {
   Coef c;
   c.zm = op.czm + bzm;
@@ -46,5 +50,5 @@ __device__ __forceinline__ double relax(double omega, double f, double avv, doub
   return fma(omega * (f - avv), fused::fast_reciprocal(dgv), vc);
 }
 
-}  // namespace b7
+}  // namespace p7
 }  // namespace mgcmt

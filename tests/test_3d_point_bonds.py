@@ -4,7 +4,7 @@ oracle (Ref3dSolver of tests/test_3d_cycle.py, which cycles any sparse matrix) a
 library on the GPU box and through the emulated kernels on CPU (``backend`` fixture).
 
 Level 0 of such a plan keeps four planes D, Bx, By, Bz.  With a constant 7-point Kronecker part it runs the marching kernels
-of csrc/kernels_3d_bonds.hip from 64^3 on (the flat ones of csrc/kernels_3d_point.hip below, or with MGCMT_3D_POINT_MARCH=0);
+k3pm_*<BONDS = true> of csrc/kernels_3d_point.hip from 64^3 on (that file's flat ones below, or with MGCMT_3D_POINT_MARCH=0);
 the levels below are the 27-plane levels of a point-diagonal plan (DESIGN par. 4.16)."""
 import ctypes
 

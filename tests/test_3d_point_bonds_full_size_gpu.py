@@ -1,5 +1,5 @@
 """GPU-only checks of the 3-D plans with per-point bonds (mgcmt_plan_create3d_bonds) at sizes where the marching kernels of
-csrc/kernels_3d_bonds.hip run on several x-tiles and z-chunks.  128^3 (two x-tiles, so Bx(x-1) crosses a tile edge; four
+csrc/kernels_3d_point.hip (k3pm_*<BONDS = true>) run on several x-tiles and z-chunks.  128^3 (two x-tiles, so Bx(x-1) crosses a tile edge; four
 chunks): constant bonds handed over explicitly against the Kronecker plan of the correspondingly scaled Laplacian, zero bonds
 plus a rough diagonal against the point-diagonal plan, and the marching kernels against the flat ones.  256^3: the convergence
 on the smooth dot against the NumPy oracle's on the same profile at 32^3."""

@@ -1,5 +1,5 @@
-"""Memory contract of the 3-D kernels of a plan with per-point bonds (csrc/kernels_3d_bonds.hip, the point == 3 branches of
-csrc/kernels_3d_point.hip) under the emulated runtime's guard mode: the checks and the case machinery of
+"""Memory contract of the 3-D kernels of a plan with per-point bonds (the k3pm_*<BONDS = true> marching kernels and the kPointBonds
+branches of csrc/kernels_3d_point.hip) under the emulated runtime's guard mode: the checks and the case machinery of
 tests/test_memory_contract.py, on plans of mgcmt_plan_create3d_bonds.
 
 16^3: the flat kernels of the fine level (constant 7-point + D + bonds) and of the 27-plane levels, entry by entry.  64^3: the

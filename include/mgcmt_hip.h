@@ -40,7 +40,8 @@
  *     twogrid, ritz_pair, rayleigh_residual, sharding, fused-pass and timing entries) return MGCMT_ERR_UNSUPPORTED on
  *     a 3-D plan.
  *     A 3-D operator may carry an arbitrary diagonal on top of its Kronecker terms (mgcmt_plan_create3d_pot), and per-point
- *     bonds as well: any symmetric 7-point matrix (mgcmt_plan_create3d_bonds).
+ *     bonds as well: any symmetric 7-point matrix (mgcmt_plan_create3d_bonds), or a per-point 27-point stencil: any symmetric
+ *     matrix on the 3 x 3 x 3 neighbourhood (mgcmt_plan_create3d_stencil).
  */
 #ifndef MGCMT_HIP_H
 #define MGCMT_HIP_H
@@ -229,11 +230,33 @@ int mgcmt_plan_create3d_pot(const mgcmt_plan3d_desc* desc, const double* point_d
  * mgcmt_plan_get_point_stencil(level 0) returns the four planes D, Bx, By, Bz, g^3 numbers each. */
 int mgcmt_plan_create3d_bonds(const mgcmt_plan3d_desc* desc, const double* point_diag, const double* bx, const double* by, const double* bz,
                               mgcmt_plan** out);
+/* A 3-D plan whose operator carries a per-point 27-point stencil on top of its Kronecker terms: any symmetric matrix on the
+ * 3 x 3 x 3 neighbourhood,
+ *     A = sum_m X_m (x) Y_m (x) Z_m + G(stencil)  - shift * I,
+ * stencil = 27 planes of g^3 numbers on the host, plane 9 a + 3 b + c, index [z * g^2 + y * g + x]: the coefficient of
+ * v(z + a - 1, y + b - 1, x + c - 1) in row (z, y, x) — H = -div(W grad) + V with a position-dependent symmetric 3 x 3
+ * inverse-mass tensor W(x, y, z) (a rotated L- or X-valley ellipsoid, strain, a principal axis that turns across an interface),
+ * the Kronecker terms carrying reference masses and the planes the deviations, the mixed derivatives on the twelve edge
+ * neighbours.  The centre plane (13) is the diagonal.  A non-zero coefficient towards a point outside the grid and a stencil
+ * that is not symmetric as a matrix (plane (a, b, c) at a point against plane (2 - a, 2 - b, 2 - c) at its neighbour) return
+ * MGCMT_ERR_INVALID.  desc, what runs and the other refusals are mgcmt_plan_create3d_pot's.  Level 0 is stored in the layout
+ * of the Galerkin levels below it (216 B per point: about 3.6 GiB at 256^3, 29 GiB at 512^3), which are formed from it as
+ * level 2 is formed from level 1.  A level 0 whose Kronecker part is a constant 7-point operator computes a point with
+ * csrc/stencil27_point.h's p27::seven (no factor loads).  Where g is a multiple of 64 the passes of level 0 that measured
+ * faster than their flat form take the kernels of csrc/kernels_3d_stencil.hip — one stage of the eight-colour sweep launched
+ * on its own points only (k3n_colour), residual + restriction with every fine residual formed once through LDS
+ * (k3n_residual_restrict) —, each giving the bits of its flat form.  The environment variable MGCMT_3D_STENCIL_TILE, read at
+ * creation: 0 = flat kernels everywhere, 1 = every such pass on level 0, 2 = those on the 27-plane Galerkin levels of that
+ * size of any 3-D plan with a per-point part as well (measurements).
+ * mgcmt_plan_get_point_stencil(level 0) returns the 27 planes. */
+int mgcmt_plan_create3d_stencil(const mgcmt_plan3d_desc* desc, const double* stencil, mgcmt_plan** out);
 /* Which kernels `level` of a 3-D plan runs on.  kind: 0 general Kronecker terms, 1 constant 7-point, 2 constant 7-point plus a
  * point diagonal, 3 Kronecker terms plus 27 planes, 4 general Kronecker terms plus a point diagonal (a fine level whose
  * factors are not Toeplitz: flat kernels), 5 constant 7-point plus a point diagonal and bonds, 6 general Kronecker terms
- * plus a point diagonal and bonds (flat kernels); marching: whether the level's smoothing and transfer passes take the
- * marching kernels (1) or the flat ones (0).  Either output may be NULL.  (mgcmt_level_operator_kind describes 1-D / 2-D plans.) */
+ * plus a point diagonal and bonds (flat kernels), 7 constant 7-point plus 27 planes (level 0 of mgcmt_plan_create3d_stencil);
+ * marching: whether the level's smoothing and transfer passes take the marching kernels (1) or the flat ones (0) — on a level
+ * of kind 3 or 7: whether any of its passes takes the kernels of csrc/kernels_3d_stencil.hip.  Either output may be NULL.
+ * (mgcmt_level_operator_kind describes 1-D / 2-D plans.) */
 int mgcmt_plan3d_level_path(const mgcmt_plan* plan, int level, int* kind, int* marching);
 int mgcmt_plan_get_point_stencil(const mgcmt_plan* plan, int level, double* out, int64_t capacity);
 int mgcmt_plan_num_levels(const mgcmt_plan* plan, int* levels);

@@ -4,7 +4,7 @@ Host side: the reference's three classes with unchanged signatures.  Device side
 kernels for gfx950 behind the C-ABI of include/mgcmt_hip.h (libmgcmt_hip.so, bound with ctypes).
 """
 from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator,
-                        potential_operator, potential_well_operator, recognise, recognise_five_point, recognise_nine_point,
+                        potential_operator, potential_well_operator, recognise, recognise_27_point, recognise_five_point, recognise_nine_point,
                         recognise_potential, recognise_seven_point, tensor_mass_operator, variable_mass_operator)
 from .plan import Plan, get_plan, release_plans
 from .processor import MGCMTProcessor
@@ -14,4 +14,4 @@ from .stencil_maker import MGCMTStencilMaker
 __all__ = ["MGCMTSolver", "MGCMTStencilMaker", "MGCMTProcessor", "StructuredOperator", "UnrecognisedOperator",
            "laplacian_operator", "identity_operator", "potential_well_operator", "potential_operator", "recognise",
            "recognise_potential", "variable_mass_operator", "recognise_five_point", "recognise_seven_point",
-           "tensor_mass_operator", "recognise_nine_point", "Plan", "get_plan", "release_plans"]
+           "tensor_mass_operator", "recognise_nine_point", "recognise_27_point", "Plan", "get_plan", "release_plans"]

@@ -75,6 +75,7 @@ OPK_POINT_BONDS = 7                            # ... level 0 of a plan with per-
 PATH3D_GENERAL, PATH3D_SEVEN, PATH3D_SEVEN_POINT, PATH3D_PLANES = 0, 1, 2, 3
 PATH3D_GENERAL_POINT = 4        # ... general terms + point diagonal (a fine level whose factors are not Toeplitz)
 PATH3D_SEVEN_BONDS, PATH3D_GENERAL_BONDS = 5, 6    # ... level 0 of a plan with per-point bonds (mgcmt_plan_create3d_bonds)
+PATH3D_SEVEN_PLANES = 7         # ... constant 7-point + 27 planes: level 0 of a plan with a point stencil (mgcmt_plan_create3d_stencil)
 HALO_RING = 0x100
 
 _SIGNATURES = {
@@ -91,6 +92,7 @@ _SIGNATURES = {
     "mgcmt_plan_level_tiled": (c_int, [c_void_p, c_int, POINTER(c_int)]),
     "mgcmt_plan_create3d_pot": (c_int, [POINTER(Plan3dDesc), _dp, POINTER(c_void_p)]),
     "mgcmt_plan_create3d_bonds": (c_int, [POINTER(Plan3dDesc), _dp, _dp, _dp, _dp, POINTER(c_void_p)]),
+    "mgcmt_plan_create3d_stencil": (c_int, [POINTER(Plan3dDesc), _dp, POINTER(c_void_p)]),
     "mgcmt_plan3d_level_path": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int)]),
     "mgcmt_plan_get_point_stencil": (c_int, [c_void_p, c_int, _dp, c_int64]),
     "mgcmt_plan_destroy": (c_int, [c_void_p]),

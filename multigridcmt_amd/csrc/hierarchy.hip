@@ -290,6 +290,7 @@ struct PlanSpec {
   const double* point_south = nullptr;  // (i, j + 1) / (i + 1, j); both or neither
   const double* point_bonds3[3] = {nullptr, nullptr, nullptr};  // 3-D, mgcmt_plan_create3d_bonds: Bx, By, Bz, g^3 numbers each; all or none
   const double* point_nine = nullptr;  // 2-D, mgcmt_plan_create_nine: nine planes of g x g numbers (instead of point_diag)
+  const double* point_stencil3 = nullptr;  // 3-D, mgcmt_plan_create3d_stencil: 27 planes of g^3 numbers (instead of point_diag)
 };
 
 // The per-point part of A on every level (kernels_pointwise.hip): the diagonal D on level 0 in the level's padded row
@@ -376,7 +377,16 @@ int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east
 // kernels predicate all three directions), below it the 27 planes of R D P, R (R D P) P, ...
 // With bonds (mgcmt_plan_create3d_bonds) level 0 holds four such planes — D, Bx, By, Bz — and K3Op::point = kPointBonds; their
 // Galerkin product is the same 27 planes, so the levels below are what they always were.
-int build_point_part3(mgcmt_plan* p, const double* point_diag, const double* const* bonds) {
+// With a 27-point stencil (stencil: mgcmt_plan_create3d_stencil) level 0 is a 27-plane level itself — K3Op::point = kPointPlanes,
+// the layout of the levels below, whose planes k3p_coarsen forms from it as it forms level 2 from level 1.
+int build_point_part3(mgcmt_plan* p, const double* point_diag, const double* const* bonds, const double* stencil) {
+  // which 27-plane levels take the kernels of kernels_3d_stencil.hip (K3Op::pmarch; stencil3_tiled adds the size rule).  Unset
+  // or "1": level 0 of a plan with a 27-point stencil, the passes in tile_default (those that measured no slower than 1.03 x
+  // their flat form at 256^3: DESIGN par. 4.18); "0": none (A/B tests); "2": every pass, on the Galerkin levels of every plan
+  // with a per-point part as well (measurements; not the default: existing plans run the launches they always ran).
+  const char* st = getenv("MGCMT_3D_STENCIL_TILE");
+  const int tile_mode = !st || !st[0] ? 1 : st[0] == '0' ? 0 : st[0] == '2' ? 2 : 1;
+  const int tile_all = kStencil3Colour | kStencil3Residual, tile_default = kStencil3Colour | kStencil3Residual;
   const char* e = getenv("MGCMT_3D_POINT_MARCH");  // "0": the fine level on the flat kernels (A/B tests)
   // the passes of the fine level that march (K3Op::pmarch; point3_marching adds the size rule)
   const int march = e && e[0] == '0' ? 0 : (kMarch3Jacobi | kMarch3Parity | kMarch3Residual | kMarch3Prolong);
@@ -385,10 +395,17 @@ int build_point_part3(mgcmt_plan* p, const double* point_diag, const double* con
     K3Op& k = L.dA.k3;
     const size_t N = (size_t)L.nr * L.gc;
     double* q = nullptr;
-    MG_HIP(hipMalloc((void**)&q, (l == 0 ? (bonds[0] ? 4 : 1) : 27) * N * sizeof(double)));
+    MG_HIP(hipMalloc((void**)&q, (l == 0 && !stencil ? (bonds[0] ? 4 : 1) : 27) * N * sizeof(double)));
     L.dA.owned.push_back(q);
     k.pg = q;
-    k.pmarch = l == 0 ? march : 0;
+    k.pmarch = l == 0 ? march : tile_mode == 2 ? tile_all : 0;
+    if (l == 0 && stencil) {
+      MG_HIP(hipMemcpy(q, stencil, 27 * N * sizeof(double), hipMemcpyHostToDevice));
+      k.point = kPointPlanes;
+      k.pplane = (long)N;
+      k.pmarch = tile_mode == 2 ? tile_all : tile_mode == 1 ? tile_default : 0;
+      continue;
+    }
     if (l == 0 && bonds[0]) {
       MG_HIP(hipMemcpy(q, point_diag, N * sizeof(double), hipMemcpyHostToDevice));
       for (int a = 0; a < 3; ++a) MG_HIP(hipMemcpy(q + (a + 1) * N, bonds[a], N * sizeof(double), hipMemcpyHostToDevice));
@@ -514,8 +531,8 @@ int build_plan(const PlanSpec& d, mgcmt_plan** out) {
       return rc;
     }
   }
-  if (d.point_diag || d.point_nine) {
-    const int rc = d.dim == 3 ? build_point_part3(p, d.point_diag, d.point_bonds3)
+  if (d.point_diag || d.point_nine || d.point_stencil3) {
+    const int rc = d.dim == 3 ? build_point_part3(p, d.point_diag, d.point_bonds3, d.point_stencil3)
                               : build_point_part(p, d.point_diag, d.point_east, d.point_south, d.point_nine);
     if (rc != MGCMT_OK) {
       mgcmt_plan_destroy(p);
@@ -681,6 +698,38 @@ int mgcmt_plan_create3d_bonds(const mgcmt_plan3d_desc* d, const double* point_di
   return build_plan(spec, out);
 }
 
+int mgcmt_plan_create3d_stencil(const mgcmt_plan3d_desc* d, const double* stencil, mgcmt_plan** out) {
+  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (!stencil) return fail(MGCMT_ERR_INVALID, "null point stencil");
+  if (d->lowest > 16) return fail(MGCMT_ERR_INVALID, "lowest must be at most 16 on a 3-D plan (the coarsest level is solved directly)");
+  const int64_t g = d->g, g2 = g * g, N = g2 * g;
+  for (int a = 0; a < 3 && g >= 1; ++a)
+    for (int b = 0; b < 3; ++b)
+      for (int c = 0; c < 3; ++c) {
+        const double* G = stencil + (9 * a + 3 * b + c) * N;
+        const double* T = stencil + (9 * (2 - a) + 3 * (2 - b) + (2 - c)) * N;  // the plane of the opposite offset
+        const int64_t off = (a - 1) * g2 + (b - 1) * g + (c - 1);
+        for (int64_t z = 0; z < g; ++z) {
+          const bool zin = z + a - 1 >= 0 && z + a - 1 < g;
+          for (int64_t y = 0; y < g; ++y) {
+            const bool yin = zin && y + b - 1 >= 0 && y + b - 1 < g;
+            const int64_t row = z * g2 + y * g;
+            for (int64_t x = 0; x < g; ++x) {
+              if (!yin || x + c - 1 < 0 || x + c - 1 >= g) {
+                if (G[row + x] != 0.0) return fail(MGCMT_ERR_INVALID, "point stencil: a coefficient towards a point outside the grid must be zero");
+              } else if (G[row + x] != T[row + x + off]) {
+                return fail(MGCMT_ERR_INVALID, "point stencil is not symmetric: the coefficient of p' in the row of p must equal that of p in the row of p'");
+              }
+            }
+          }
+        }
+      }
+  PlanSpec spec{3, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->zfac, d->yfac, d->xfac}, {nullptr, nullptr, nullptr}, 0, 0, 0};
+  spec.point_stencil3 = stencil;
+  return build_plan(spec, out);
+}
+
 int mgcmt_plan3d_level_path(const mgcmt_plan* p, int l, int* kind, int* marching) {
   MG_TRY(check_level(p, l));
   if (p->dim != 3) return fail(MGCMT_ERR_INVALID, "mgcmt_plan3d_level_path needs a 3-D plan");
@@ -696,7 +745,8 @@ int mgcmt_plan3d_level_path(const mgcmt_plan* p, int l, int* kind, int* marching
       march = point3_marching(k) != 0;
       break;
     case kPointPlanes:
-      path = 3;
+      path = k.seven ? 7 : 3;
+      march = stencil3_tiled(k) != 0;  // (kernels_3d_stencil.hip)
       break;
     case kPointBonds:
       path = k.seven ? 5 : 6;

@@ -21,9 +21,13 @@
 // The flat and the marching form of the fine level compute every point with ONE set of inline functions (seven_point.h: the
 // same fma order, the same reciprocal of c0 + D - mu), so their sweeps give the same bits.  Which passes march is
 // point3_marching (K3Op::pmarch, hierarchy.hip); MGCMT_3D_POINT_MARCH=0 selects the flat form.
+// A level of 27 planes — the Galerkin levels, and level 0 of mgcmt_plan_create3d_stencil, whose Kronecker part is a constant
+// 7-point operator — computes a point with stencil27_point.h's functions; its colour stages and its residual + restriction
+// have a second form in kernels_3d_stencil.hip (stencil3_tiled), which the launchers below try first.
 #include "kernels_3d_common.h"
 #include "mgcmt_internal.h"
 #include "seven_point.h"
+#include "stencil27_point.h"
 
 namespace mgcmt {
 
@@ -67,41 +71,19 @@ __device__ __forceinline__ PEval eval3p(const K3Op& op, W&& w, long z, long y, l
                   yp ? w(z, y + 1, x) : 0.0, xm ? w(z, y, x - 1) : 0.0, xp ? w(z, y, x + 1) : 0.0);
     return r;
   }
+  // 27 planes, on a constant 7-point part or on general terms (stencil27_point.h)
+  if (op.point == kPointPlanes) {
+    const p27::Eval e = p27::point(op, w, z, y, x, mu);
+    r.av = e.av;
+    r.dg = e.dg;
+    return r;
+  }
   // the 27 neighbours once, zeros outside the grid
   double wn[3][3][3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int b = 0; b < 3; ++b)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const bool in = (a != 0 || zm) && (a != 2 || zp) && (b != 0 || ym) && (b != 2 || yp) && (c != 0 || xm) && (c != 2 || xp);
-        wn[a][b][c] = in ? w(z + a - 1, y + b - 1, x + c - 1) : 0.0;
-      }
+  p27::neighbours(w, n, z, y, x, wn);
   // Kronecker part: a(dz, dy, dx) = sum_m X_m[dz](z) Y_m[dy](y) Z_m[dx](x), summed as eval3 does
   double acc = 0.0, diag = 0.0;
-  for (int m = 0; m < op.nterms; ++m) {
-    double fz[3], fy[3], fx[3];
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      fz[t] = op.X[m][t * n + z];
-      fy[t] = op.Y[m][t * n + y];
-      fx[t] = op.Z[m][t * n + x];
-    }
-    diag += fz[1] * fy[1] * fx[1];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      double pa = 0.0;
-#pragma unroll
-      for (int b = 0; b < 3; ++b) {
-        double pb = fx[0] * wn[a][b][0];
-        pb += fx[1] * wn[a][b][1];
-        pb += fx[2] * wn[a][b][2];
-        pa += fy[b] * pb;
-      }
-      acc += fz[a] * pa;
-    }
-  }
+  p27::kronecker(op, z, y, x, wn, acc, diag);
   const double* __restrict__ g = op.pg + idx;
   if (op.point == kPointDiag) {  // a diagonal on top of general terms
     acc += g[0] * wn[1][1][1];
@@ -117,22 +99,6 @@ __device__ __forceinline__ PEval eval3p(const K3Op& op, W&& w, long z, long y, l
     pa += g[pl] * wn[1][1][2];
     acc += pa;
     diag += g[0];
-  } else {
-    const long pl = op.pplane;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      double pa = 0.0;
-#pragma unroll
-      for (int b = 0; b < 3; ++b) {
-        const double* gp = g + (9 * a + 3 * b) * pl;
-        double pb = gp[0] * wn[a][b][0];
-        pb += gp[pl] * wn[a][b][1];
-        pb += gp[2 * pl] * wn[a][b][2];
-        pa += pb;
-      }
-      acc += pa;
-    }
-    diag += g[13 * pl];
   }
   // acc holds the unshifted sum, centre included
   r.dg = diag - mu;
@@ -142,6 +108,7 @@ __device__ __forceinline__ PEval eval3p(const K3Op& op, W&& w, long z, long y, l
 
 __device__ __forceinline__ double relax3p(const K3Op& op, const PEval& e, double omega, double f, double vc) {
   if (seven_point_row(op)) return p7::relax(omega, f, e.av, e.dg, vc);
+  if (op.point == kPointPlanes) return p27::relax(op, omega, f, p27::Eval{e.av, e.dg}, vc);
   return vc + omega * (f - e.av) / e.dg;
 }
 
@@ -554,9 +521,11 @@ void launch3p_mc_sweep(hipStream_t s, const K3Op& op, KVec v, KVec f, const doub
     }
     return;
   }
-  for (int c = 0; c < 8; ++c)
+  for (int c = 0; c < 8; ++c) {
+    if (launch3n_colour(s, op, v, f, shifts, omega, order[c][0], order[c][1], order[c][2], k)) continue;  // (a 27-plane level's own stage)
     hipLaunchKernelGGL(k3p_colour, flat_grid(op.n * op.n * op.n, k), dim3(kFlatThreads), 0, s, op, v, f, shifts, omega, order[c][0], order[c][1],
                        order[c][2]);
+  }
 }
 
 void launch3p_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k) {
@@ -568,6 +537,7 @@ void launch3p_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, K
                        dim3(kTileX, kTileY), 0, s, op, v, f, fc, vc, shifts, nch);
     return;
   }
+  if (launch3n_residual_restrict(s, op, v, f, fc, vc, shifts, k)) return;  // (a 27-plane level's own pass)
   hipLaunchKernelGGL(k3p_residual_restrict, flat_grid(nc * nc * nc, k), dim3(kFlatThreads), 0, s, op, v, f, fc, vc, shifts);
 }
 

@@ -86,7 +86,10 @@ struct K3Op {
   // By = pg[2 pplane + idx] towards (z, y + 1, x), Bz = pg[3 pplane + idx] towards (z + 1, y, x);
   // Bx(x = n - 1) = By(y = n - 1) = Bz(z = n - 1) = 0, a bond read at x - 1 < 0 etc. is a predicated zero.
   // pmarch: the set of passes (kMarch3*) of a fine level, 1 or 3, that take the marching kernels where the level's Kronecker
-  // part and size allow (point3_marching; MGCMT_3D_POINT_MARCH, read at plan creation: hierarchy.hip).
+  // part and size allow (point3_marching; MGCMT_3D_POINT_MARCH, read at plan creation: hierarchy.hip).  Level 0 of
+  // mgcmt_plan_create3d_stencil is a point == 2 level too (the caller's 27 planes); on a point == 2 level pmarch is the set of
+  // passes (kStencil3* below) that take the kernels of kernels_3d_stencil.hip where the level's size allows
+  // (stencil3_tiled; MGCMT_3D_STENCIL_TILE, read at plan creation: hierarchy.hip).
   int point, pmarch;
   const double* pg;
   long pplane;
@@ -344,6 +347,15 @@ void launch3p_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, K
 void launch3p_prolong_jacobi(hipStream_t s, const K3Op& op, KVec e, KVec vin, KVec f, KVec vout, const double* shifts, double omega, int k);
 void launch3p_band_add(hipStream_t s, const K3Op& op, const KBand& b, int k);
 void launch3p_coarsen(hipStream_t s, long fn, const double* fine, int fine_planes, long fplane, double* coarse, long cplane);
+// a 27-plane level (op.point == kPointPlanes) on the kernels of kernels_3d_stencil.hip.  stencil3_tiled: the passes (kStencil3*
+// bits of op.pmarch) that take them on this level — n a multiple of 64 — or 0; a launcher returns false, nothing launched, where
+// its pass stays flat.  launch3n_colour: one stage (cz, cy, cx) of the eight-colour sweep in place, launched on the n^3 / 8
+// points of its colour only; launch3n_residual_restrict: fc <- R (f - (A - mu) v), vc <- 0, a workgroup per tile of coarse
+// columns and chunk of coarse planes, every fine residual formed once (LDS).  Both give the bits of their flat form.
+constexpr int kStencil3Colour = 16, kStencil3Residual = 32;
+int stencil3_tiled(const K3Op& op);
+bool launch3n_colour(hipStream_t s, const K3Op& op, KVec v, KVec f, const double* shifts, double omega, int cz, int cy, int cx, int k);
+bool launch3n_residual_restrict(hipStream_t s, const K3Op& op, KVec v, KVec f, KVec fc, KVec vc, const double* shifts, int k);
 
 // Rayleigh-quotient passes on 3-D levels (kernels_rq3d.hip), the protocol of launch_rq_pass1 / launch_rq_pass2 /
 // launch_rq_scalars2 and the same state words: pass 1 ends with the step's scalars; pass 2 returns the number of partial

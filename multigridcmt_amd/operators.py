@@ -65,6 +65,11 @@ class StructuredOperator:
     2 x 2 inverse-mass tensor W (``tensor_mass_operator``, ``recognise_nine_point``).  Coefficients towards points outside the
     grid must be zero and G[a, b][i, j] == G[2 - a, 2 - b][i + a - 1, j + b - 1] (``Plan.point_stencil`` returns this shape
     for the levels below 0).
+
+    3-D: a (3, 3, 3, g, g, g) array G — G[a, b, c][z, y, x] is the coefficient of v(z + a - 1, y + b - 1, x + c - 1) in row
+    (z, y, x): a symmetric 27-point operator with any coefficients, e.g. -div(W grad) + V with a symmetric 3 x 3 inverse-mass
+    tensor W(x, y, z) (``tensor_mass_operator(..., dimension="3d")``, ``recognise_27_point``).  The same rules: zero towards points
+    outside the grid, G[a, b, c][z, y, x] == G[2 - a, 2 - b, 2 - c][z + a - 1, y + b - 1, x + c - 1].
     """
 
     def __init__(self, dimension, g, terms, point_diagonal=None, point_bonds=None, point_stencil=None):
@@ -74,14 +79,19 @@ class StructuredOperator:
         self.point_bonds = None
         self.point_stencil = None
         if point_stencil is not None:
-            if dimension != "2d":
-                raise ValueError("point_stencil is a property of 2-D operators")
+            if dimension not in ("2d", "3d"):
+                raise ValueError("point_stencil is a property of 2-D and 3-D operators")
             if point_diagonal is not None or point_bonds is not None:
                 raise ValueError("point_stencil carries the diagonal (its centre plane) and the bonds: give it instead of point_diagonal / point_bonds")
             G = np.array(point_stencil, dtype=np.float64, order="C")
-            if G.size != 9 * self.g * self.g:
-                raise ValueError("point_stencil must hold 3 x 3 x g x g = 9 x %d x %d values, not %r" % (self.g, self.g, G.shape))
-            G = G.reshape(3, 3, self.g, self.g)
+            if dimension == "3d":
+                if G.size != 27 * self.g ** 3:
+                    raise ValueError("point_stencil of a 3-D operator must hold 3 x 3 x 3 x g^3 = 27 x %d^3 values, not %r" % (self.g, G.shape))
+                G = G.reshape(3, 3, 3, self.g, self.g, self.g)
+            else:
+                if G.size != 9 * self.g * self.g:
+                    raise ValueError("point_stencil must hold 3 x 3 x g x g = 9 x %d x %d values, not %r" % (self.g, self.g, G.shape))
+                G = G.reshape(3, 3, self.g, self.g)
             _check_point_stencil(G)
             self.point_stencil = G
         if point_bonds is not None and dimension == "3d":
@@ -149,7 +159,8 @@ class StructuredOperator:
         if self.dimension == "3d":
             return StructuredOperator("3d", self.g, [(x, y, z * c) for x, y, z in self.terms],
                                       point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c,
-                                      point_bonds=None if self.point_bonds is None else tuple(b * c for b in self.point_bonds))
+                                      point_bonds=None if self.point_bonds is None else tuple(b * c for b in self.point_bonds),
+                                      point_stencil=None if self.point_stencil is None else self.point_stencil * c)
         return StructuredOperator("2d", self.g, [(x, y * c) for x, y in self.terms],
                                   point_diagonal=None if self.point_diagonal is None else self.point_diagonal * c,
                                   point_bonds=None if self.point_bonds is None else tuple(b * c for b in self.point_bonds),
@@ -179,7 +190,8 @@ class StructuredOperator:
         if self.dimension == "3d":
             i = tri_identity(self.g)
             terms = [tuple(a.copy() for a in t) for t in self.terms] + [(i, i.copy(), i * (-float(mu)))]
-            return StructuredOperator("3d", self.g, terms, point_diagonal=self.point_diagonal, point_bonds=self.point_bonds)
+            return StructuredOperator("3d", self.g, terms, point_diagonal=self.point_diagonal, point_bonds=self.point_bonds,
+                                      point_stencil=self.point_stencil)
         terms = [(None if x is None else x.copy(), y.copy()) for x, y in self.terms]
         if self.dimension == "1d":
             terms[0][1][1] -= mu
@@ -194,6 +206,8 @@ class StructuredOperator:
             return sum(y[1] for _, y in self.terms)
         if self.dimension == "3d":
             d = sum(np.kron(x[1], np.kron(y[1], z[1])) for x, y, z in self.terms)
+            if self.point_stencil is not None:
+                d = d + self.point_stencil[1, 1, 1].reshape(-1)
             return d if self.point_diagonal is None else d + self.point_diagonal.reshape(-1)
         d = sum(np.outer(x[1], y[1]) for x, y in self.terms)
         if self.point_stencil is not None:
@@ -212,6 +226,8 @@ class StructuredOperator:
                 A = (A + sp.diags(self.point_diagonal.reshape(-1), 0, format="csr")).tocsr()
             if self.point_bonds is not None:
                 A = (A + _bonds3_to_sparse(*self.point_bonds)).tocsr()
+            if self.point_stencil is not None:
+                A = (A + planes_to_csr(self.point_stencil)).tocsr()
             return A
         A = sum(sp.kron(tri_to_sparse(x), tri_to_sparse(y), format="csr") for x, y in self.terms).tocsr()
         if self.point_diagonal is not None:
@@ -266,20 +282,23 @@ class StructuredOperator:
 
 
 def _check_point_stencil(G):
-    """ValueError unless the (3, 3, g, g) stencil is zero towards points outside the grid and symmetric as a matrix."""
+    """ValueError unless the (3, 3, g, g) — 3-D: (3, 3, 3, g, g, g) — stencil is zero towards points outside the grid and
+    symmetric as a matrix."""
     g = G.shape[-1]
-    for a in range(3):
-        for b in range(3):
-            # rows i (columns j) whose neighbour i + a - 1 (j + b - 1) lies inside the grid
-            i0, i1 = max(0, 1 - a), g - max(0, a - 1)
-            j0, j1 = max(0, 1 - b), g - max(0, b - 1)
-            inside = np.zeros((g, g), dtype=bool)
-            inside[i0:i1, j0:j1] = True
-            if G[a, b][~inside].any():
-                raise ValueError("point_stencil: a coefficient towards a point outside the grid is not zero (plane [%d, %d])" % (a, b))
-            if not np.array_equal(G[a, b][i0:i1, j0:j1], G[2 - a, 2 - b][i0 + a - 1:i1 + a - 1, j0 + b - 1:j1 + b - 1]):
-                raise ValueError("point_stencil is not symmetric: G[a, b][i, j] must equal G[2 - a, 2 - b][i + a - 1, j + b - 1] "
-                                 "(plane [%d, %d])" % (a, b))
+    d = G.ndim // 2
+    for off in np.ndindex(*([3] * d)):
+        # per axis the rows whose neighbour at this offset lies inside the grid, and that neighbour
+        here = tuple(slice(max(0, 1 - o), g - max(0, o - 1)) for o in off)
+        there = tuple(slice(h.start + o - 1, h.stop + o - 1) for h, o in zip(here, off))
+        inside = np.zeros((g,) * d, dtype=bool)
+        inside[here] = True
+        if G[off][~inside].any():
+            raise ValueError("point_stencil: a coefficient towards a point outside the grid is not zero (plane %s)" % (list(off),))
+        opposite = tuple(2 - o for o in off)
+        if not np.array_equal(G[off][here], G[opposite][there]):
+            raise ValueError("point_stencil is not symmetric: the coefficient of a neighbour in the row of a point must equal the "
+                             "coefficient of the point in the row of that neighbour, G[a, b][i, j] == G[2 - a, 2 - b][i + a - 1, j + b - 1] "
+                             "(plane %s)" % (list(off),))
 
 
 def _bonds_to_sparse(E, S):
@@ -508,7 +527,7 @@ def _variable_mass_operator_3d(g, inv_mass, V, scale, mean):
     return StructuredOperator("3d", g, terms, point_diagonal=D, point_bonds=(Bx, By, Bz))
 
 
-def tensor_mass_operator(g, wxx, wyy, wxy, V=None, scale=-1.0 / np.pi ** 2, mean="harmonic"):
+def tensor_mass_operator(g, wxx, wyy, wxy, V=None, scale=-1.0 / np.pi ** 2, mean="harmonic", *, wzz=None, wxz=None, wyz=None, dimension="2d"):
     """H = scale * div(W grad) + diag(V) on the g x g grid of ``laplacian(g, "2d")`` with a position-dependent symmetric 2 x 2
     inverse-mass tensor W = [[wxx, wxy], [wxy, wyy]] ((g, g) arrays indexed [i, j]; positive definite everywhere): anisotropic
     valleys rotated against the grid, strain, a principal axis that turns across an interface.  wxx acts along j (the east / west
@@ -524,8 +543,24 @@ def tensor_mass_operator(g, wxx, wyy, wxy, V=None, scale=-1.0 / np.pi ** 2, mean
     The Kronecker terms carry median(wxx) and median(wyy) times the scaled 1-D Laplacians; ``point_stencil`` carries the
     deviations, so a uniform region stores zeros and level 0 keeps a constant 5-point Kronecker part.  wxy = 0 everywhere is a
     diagonal tensor: the operator comes back with ``point_bonds`` (and wxx = wyy as well gives exactly
-    ``variable_mass_operator``'s)."""
+    ``variable_mass_operator``'s).
+
+    dimension="3d": the same on the g^3 grid of ``laplacian(g, "3d")`` with the symmetric 3 x 3 tensor
+    W = [[wxx, wxy, wxz], [wxy, wyy, wyz], [wxz, wyz, wzz]] — all six components and V are (g, g, g) arrays (or g^3 values) indexed
+    [z, y, x]; wxx acts along x (the fastest index), wyy along y, wzz along z.  The bond between a point and its neighbour along
+    axis u is t * m(w_uu(p), w_uu(p + e_u)), the diagonal -t * (the six bond values, a ghost's bond taking the point's own w_uu)
+    + V, and for each pair of axes (u, v) of xy, xz, yz and a, b = -1 or +1 the entry between p and p + a e_u + b e_v is
+    a * b * t * (w_uv(p + a e_u) + w_uv(p + b e_v)) / 4 — the 2-D formula in every coordinate plane: a 19-point matrix, the eight
+    corner planes of ``point_stencil`` are zero.  Three Toeplitz Kronecker terms carry median(wzz), median(wyy), median(wxx) times
+    the scaled 1-D Laplacians.  All three mixed components zero returns the ``point_bonds`` operator, wxx = wyy = wzz as well exactly
+    ``variable_mass_operator(..., dimension="3d")``'s."""
     g = int(g)
+    if dimension == "3d":
+        return _tensor_mass_operator_3d(g, wxx, wyy, wzz, wxy, wxz, wyz, V, scale, mean)
+    if dimension != "2d":
+        raise ValueError("tensor_mass_operator: dimension must be '2d' or '3d'")
+    if wzz is not None or wxz is not None or wyz is not None:
+        raise ValueError("tensor_mass_operator: wzz, wxz and wyz are components of a 3-D tensor (dimension='3d')")
     arrs = []
     for name, a in (("wxx", wxx), ("wyy", wyy), ("wxy", wxy)):
         a = np.ascontiguousarray(a, dtype=np.float64)
@@ -577,6 +612,79 @@ def tensor_mass_operator(g, wxx, wyy, wxy, V=None, scale=-1.0 / np.pi ** 2, mean
     G[2, 0][:-1, 1:] = -q * (wxy[1:, 1:] + wxy[:-1, :-1])
     G[0, 2][1:, :-1] = -q * (wxy[:-1, :-1] + wxy[1:, 1:])
     return StructuredOperator("2d", g, terms, point_stencil=G)
+
+
+def _tensor_mass_operator_3d(g, wxx, wyy, wzz, wxy, wxz, wyz, V, scale, mean):
+    arrs = []
+    for name, a in (("wxx", wxx), ("wyy", wyy), ("wzz", wzz), ("wxy", wxy), ("wxz", wxz), ("wyz", wyz)):
+        if a is None:
+            raise ValueError("tensor_mass_operator: a 3-D tensor needs all six components, %s is missing" % name)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size != g ** 3:
+            raise ValueError("tensor_mass_operator: %s must hold g^3 = %d^3 values, not %r" % (name, g, a.shape))
+        arrs.append(a.reshape(g, g, g))
+    wxx, wyy, wzz, wxy, wxz, wyz = arrs
+    minor2 = wxx * wyy - wxy * wxy
+    det = wzz * minor2 - wxz * (wxz * wyy - wxy * wyz) + wyz * (wxz * wxy - wxx * wyz)
+    if not ((wxx > 0).all() and (minor2 > 0).all() and (det > 0).all()):
+        raise ValueError("tensor_mass_operator: the inverse-mass tensor must be positive definite everywhere (its leading minors "
+                         "wxx, wxx wyy - wxy^2 and det W must be positive)")
+    if mean not in ("harmonic", "arithmetic"):
+        raise ValueError("tensor_mass_operator: mean must be 'harmonic' or 'arithmetic', not %r" % (mean,))
+    if V is not None:
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        if V.size != g ** 3:
+            raise ValueError("tensor_mass_operator: V must hold g^3 = %d^3 values, not %r" % (g, V.shape))
+        V = V.reshape(g, g, g)
+    mixed = wxy.any() or wxz.any() or wyz.any()
+    if not mixed and np.array_equal(wxx, wyy) and np.array_equal(wxx, wzz):
+        return variable_mass_operator(g, wxx, V=V, scale=scale, mean=mean, dimension="3d")
+    L = tri_laplacian(g) * float(scale)
+    t = float(L[2, 0])
+    rx, ry, rz = float(np.median(wxx)), float(np.median(wyy)), float(np.median(wzz))
+    Lx, Ly, Lz = L * rx, L * ry, L * rz
+    i = tri_identity(g)
+    terms = [(i, i.copy(), Lx), (i.copy(), Ly, i.copy()), (Lz, i.copy(), i.copy())]
+    # bond values (multiples of t) towards x+ / y+ / z+ and x- / y- / z-; ghosts take the point's own value
+    bxp, byp, bzp = wxx.copy(), wyy.copy(), wzz.copy()
+    bxp[:, :, :-1] = _mean_bond(wxx[:, :, :-1], wxx[:, :, 1:], mean)
+    byp[:, :-1, :] = _mean_bond(wyy[:, :-1, :], wyy[:, 1:, :], mean)
+    bzp[:-1, :, :] = _mean_bond(wzz[:-1, :, :], wzz[1:, :, :], mean)
+    bxm, bym, bzm = wxx.copy(), wyy.copy(), wzz.copy()
+    bxm[:, :, 1:] = bxp[:, :, :-1]
+    bym[:, 1:, :] = byp[:, :-1, :]
+    bzm[1:, :, :] = bzp[:-1, :, :]
+    Bx, By, Bz = np.zeros((g, g, g)), np.zeros((g, g, g)), np.zeros((g, g, g))
+    Bx[:, :, :-1] = t * bxp[:, :, :-1] - t * rx
+    By[:, :-1, :] = t * byp[:, :-1, :] - t * ry
+    Bz[:-1, :, :] = t * bzp[:-1, :, :] - t * rz
+    D = -t * (bxp + bxm + byp + bym + bzp + bzm) - float(Lx[1, 0]) - float(Ly[1, 0]) - float(Lz[1, 0])
+    if V is not None:
+        D = D + V
+    if not mixed:
+        return StructuredOperator("3d", g, terms, point_diagonal=D, point_bonds=(Bx, By, Bz))
+    G = np.zeros((3, 3, 3, g, g, g))
+    G[1, 1, 1] = D
+    G[1, 1, 2] = Bx
+    G[1, 1, 0][:, :, 1:] = Bx[:, :, :-1]
+    G[1, 2, 1] = By
+    G[1, 0, 1][:, 1:, :] = By[:, :-1, :]
+    G[2, 1, 1] = Bz
+    G[0, 1, 1][1:, :, :] = Bz[:-1, :, :]
+    # edges: a * b * t * (w_uv(p + a e_u) + w_uv(p + b e_v)) / 4 between p and p + a e_u + b e_v; array axes: 0 = z, 1 = y, 2 = x
+    q = 0.25 * t
+    here = {1: slice(0, g - 1), -1: slice(1, g)}          # the rows whose neighbour one step along an axis lies inside
+    there = {1: slice(1, g), -1: slice(0, g - 1)}         # ... and that neighbour
+    for w, au, av in ((wxy, 2, 1), (wxz, 2, 0), (wyz, 1, 0)):
+        for a in (-1, 1):
+            for b in (-1, 1):
+                off, rows, pu, pv = [1, 1, 1], [slice(None)] * 3, [slice(None)] * 3, [slice(None)] * 3
+                off[au], off[av] = 1 + a, 1 + b
+                rows[au], rows[av] = here[a], here[b]
+                pu[au], pu[av] = there[a], here[b]          # p + a e_u
+                pv[au], pv[av] = here[a], there[b]          # p + b e_v
+                G[tuple(off)][tuple(rows)] = (a * b * q) * (w[tuple(pu)] + w[tuple(pv)])
+    return StructuredOperator("3d", g, terms, point_stencil=G)
 
 
 class UnrecognisedOperator(ValueError):
@@ -854,6 +962,74 @@ def recognise_seven_point(A):
     i = tri_identity(g)
     op = StructuredOperator("3d", g, [(i, i.copy(), Xt), (i.copy(), Yt, i.copy()), (Zt, i.copy(), i.copy())], point_diagonal=d0 - base,
                             point_bonds=(Bx, By, Bz))
+    if len(_CACHE) > 64:
+        _CACHE.clear()
+    _CACHE[key] = (A, op)
+    return op
+
+
+def recognise_27_point(A):
+    """StructuredOperator for ANY real symmetric sparse matrix on a g^3 grid whose entries lie within the 3 x 3 x 3 neighbourhood
+    (a 3-D Hamiltonian with a position-dependent inverse-mass tensor assembled as a sparse matrix).  What ``recognise(A, "3d")``,
+    ``recognise_potential(A, "3d")`` or ``recognise_seven_point`` accepts is returned as they return it; otherwise the median
+    off-diagonal per axis direction and the median diagonal go into three Toeplitz Kronecker terms, as ``recognise_seven_point``
+    takes them — so that a uniform region leaves zeros — and the rest into the operator's ``point_stencil``.  Unsymmetric
+    matrices, entries outside the neighbourhood and entries across row or plane ends raise UnrecognisedOperator."""
+    try:
+        return recognise_seven_point(A)
+    except UnrecognisedOperator:
+        if isinstance(A, StructuredOperator):
+            raise
+    if not sp.issparse(A):
+        A = sp.csr_matrix(np.asarray(A, dtype=np.float64))
+    key = ("27_point",) + _cache_key(A)
+    hit = _CACHE.get(key)
+    if hit is not None and hit[0] is A:
+        return hit[1]
+    n = A.shape[0]
+    if A.shape[0] != A.shape[1] or np.iscomplexobj(A):
+        raise UnrecognisedOperator("recognise_27_point: a real square matrix on a g^3 grid is needed")
+    g = int(round(n ** (1.0 / 3.0)))
+    while g ** 3 > n:
+        g -= 1
+    while (g + 1) ** 3 <= n:
+        g += 1
+    if g ** 3 != n or g < 3:          # (on 2^3 points the 27 offsets are not distinct matrix diagonals)
+        raise UnrecognisedOperator("3-D operator size %d is not a cube number of at least 3^3" % n)
+    M = sp.csr_matrix(A, dtype=np.float64, copy=True)
+    M.eliminate_zeros()
+    G = np.zeros((3, 3, 3, g, g, g))
+    counted = 0
+    for a, b, c in np.ndindex(3, 3, 3):
+        off = (a - 1) * g * g + (b - 1) * g + (c - 1)
+        band = np.zeros(n)
+        d = M.diagonal(off)
+        if off >= 0:
+            band[:n - off] = d
+        else:
+            band[-off:] = d
+        counted += np.count_nonzero(band)
+        G[a, b, c] = band.reshape(g, g, g)                # [z, y, x] of the row
+    if counted != M.nnz:
+        raise UnrecognisedOperator("3-D operator is not a 27-point matrix: it has entries outside the 3 x 3 x 3 neighbourhood")
+    if G[:, :, 0, :, :, 0].any() or G[:, :, 2, :, :, -1].any() or G[:, 0, :, :, 0, :].any() or G[:, 2, :, :, -1, :].any():
+        raise UnrecognisedOperator("3-D operator is not a 27-point matrix: it has entries across the row or plane ends")
+    try:
+        _check_point_stencil(G)
+    except ValueError:
+        raise UnrecognisedOperator("3-D 27-point operator is not symmetric: a per-point stencil describes symmetric matrices only")
+    base = float(np.median(G[1, 1, 1]))
+    cx, cy, cz = float(np.median(G[1, 1, 2][:, :, :-1])), float(np.median(G[1, 2, 1][:, :-1, :])), float(np.median(G[2, 1, 1][:-1, :, :]))
+    Xt, Yt, Zt = _toeplitz_tri(cx, base - 2.0 * (base / 3.0), cx, g), _toeplitz_tri(cy, base / 3.0, cy, g), _toeplitz_tri(cz, base / 3.0, cz, g)
+    G[1, 1, 1] -= base
+    G[1, 1, 2][:, :, :-1] -= cx
+    G[1, 1, 0][:, :, 1:] -= cx
+    G[1, 2, 1][:, :-1, :] -= cy
+    G[1, 0, 1][:, 1:, :] -= cy
+    G[2, 1, 1][:-1, :, :] -= cz
+    G[0, 1, 1][1:, :, :] -= cz
+    i = tri_identity(g)
+    op = StructuredOperator("3d", g, [(i, i.copy(), Xt), (i.copy(), Yt, i.copy()), (Zt, i.copy(), i.copy())], point_stencil=G)
     if len(_CACHE) > 64:
         _CACHE.clear()
     _CACHE[key] = (A, op)

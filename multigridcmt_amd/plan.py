@@ -88,6 +88,8 @@ class Plan:
             raise ValueError("the mass operator of a 3-D plan must be a 3-D operator on the same %d^3 grid" % op.g)
         if mass is not None and not 1 <= len(mass.terms) <= _lib.MAX_TERMS:
             raise ValueError("a 3-D mass operator has 1 .. %d Kronecker terms, not %d" % (_lib.MAX_TERMS, len(mass.terms)))
+        if (row_begin or row_end or strip_levels) and getattr(op, "point_stencil", None) is not None:
+            raise ValueError("an operator with a point stencil is not sharded")
         if row_begin or row_end or strip_levels:
             raise ValueError("3-D plans are not sharded")
         if self.lowest > 16:
@@ -98,7 +100,17 @@ class Plan:
         desc.zfac, desc.yfac, desc.xfac = as_dp(zfac), as_dp(yfac), as_dp(xfac)
         desc.device = self.device
         pd = getattr(op, "point_diagonal", None)
-        if pd is not None:
+        ps = getattr(op, "point_stencil", None)
+        if ps is not None:
+            # a per-point 27-point stencil (operators.tensor_mass_operator(..., dimension="3d")): level 0 is a 27-plane level like
+            # the Galerkin levels below it
+            if mass is not None:
+                raise ValueError("a 3-D operator with a point stencil (a point diagonal and more) takes no mass operator: the "
+                                 "Rayleigh-quotient routines (rqmin, vcycle_rqmg, ...) do not run on it; vcycle / vcycle_matrix, the "
+                                 "smoothers wjacobi and gseidel_rb, apply and drivers.block_eigensolve do")
+            ps = _f64(ps)
+            check(_lib.lib().mgcmt_plan_create3d_stencil(ctypes.byref(desc), as_dp(ps), ctypes.byref(self._h)))
+        elif pd is not None:
             # an arbitrary potential V(x, y, z) on the diagonal: the per-point hierarchy R D P (27 planes per level) is built at creation
             if mass is not None:
                 raise ValueError("a 3-D operator with a point diagonal%s takes no mass operator: the Rayleigh-quotient routines (rqmin, "
@@ -159,11 +171,13 @@ class Plan:
         array [rows, cols]; below it the 9-point stencil R D P, array [3, 3, rows, cols] — entry [a, b, i, j] is the
         coefficient of point (i + a - 1, j + b - 1) in row (i, j).  Level 0 of an operator with ``point_bonds``: the three
         planes D, E, S, array [3, rows, cols]; of an operator with ``point_stencil``: [3, 3, rows, cols] like the levels below.  3-D: [g, g, g] on level 0 ([4, g, g, g] = D, Bx, By, Bz with bonds) and the 27-point stencil
-        [3, 3, 3, g_l, g_l, g_l] below — entry [a, b, c, z, y, x] is the coefficient of point (z + a - 1, y + b - 1, x + c - 1)."""
+        [3, 3, 3, g_l, g_l, g_l] below — entry [a, b, c, z, y, x] is the coefficient of point (z + a - 1, y + b - 1, x + c - 1); level 0 of
+        a 3-D operator with ``point_stencil`` has that shape too."""
         if self.dim == 3:
             gl = self.g >> level
             bonds = getattr(self.op, "point_bonds", None) is not None
-            out = np.zeros(((4, gl, gl, gl) if bonds else (gl, gl, gl)) if level == 0 else (3, 3, 3, gl, gl, gl))
+            planes = getattr(self.op, "point_stencil", None) is not None      # level 0 is a 27-plane level too
+            out = np.zeros(((4, gl, gl, gl) if bonds else (gl, gl, gl)) if level == 0 and not planes else (3, 3, 3, gl, gl, gl))
             check(_lib.lib().mgcmt_plan_get_point_stencil(self._h, level, as_dp(out), out.size))
             return out
         r, c, _ = self.shapes[level]

@@ -15,8 +15,8 @@ import scipy.sparse as sp
 
 from . import _lib
 from ._lib import GS_LEX, GS_MC, OP_A, OP_M, SLOT_F, SLOT_T, SLOT_V, SLOT_W, SOR_LEX, WJACOBI
-from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, planes_to_csr, recognise, recognise_five_point,
-                        recognise_nine_point, recognise_potential, recognise_seven_point, tag_structured)
+from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, planes_to_csr, recognise, recognise_27_point,
+                        recognise_five_point, recognise_nine_point, recognise_potential, recognise_seven_point, tag_structured)
 from .plan import get_plan
 from .processor import MGCMTProcessor
 from .stencil_maker import MGCMTStencilMaker
@@ -63,8 +63,9 @@ def _recognise_entry(A, dimension):
     with any potential), which ``recognise`` refuses, is mapped by ``recognise_potential`` to an operator with a point
     diagonal; in 2-D a symmetric 5-point matrix whose off-diagonals vary too (a position-dependent effective mass) is mapped
     by ``recognise_five_point`` to an operator with point bonds and a symmetric 9-point matrix (an inverse-mass tensor) last by
-    ``recognise_nine_point`` to one with a point stencil; in 3-D a symmetric 7-point matrix by ``recognise_seven_point``; what
-    that refuses too raises ``recognise``'s error."""
+    ``recognise_nine_point`` to one with a point stencil; in 3-D a symmetric 7-point matrix by ``recognise_seven_point`` and a
+    symmetric 27-point matrix (an inverse-mass tensor) last by ``recognise_27_point``; what that refuses too raises
+    ``recognise``'s error."""
     try:
         return recognise(A, dimension)
     except UnrecognisedOperator as err:
@@ -75,7 +76,7 @@ def _recognise_entry(A, dimension):
         except UnrecognisedOperator:
             pass
         try:
-            return recognise_nine_point(A) if dimension == "2d" else recognise_seven_point(A)     # (tries recognise_five_point first)
+            return recognise_nine_point(A) if dimension == "2d" else recognise_27_point(A)     # (try recognise_five_point / recognise_seven_point first)
         except UnrecognisedOperator:
             raise err
 
@@ -245,7 +246,12 @@ class MGCMTSolver:
             fs = [plan.factors(level, w) for w in range(3)]
             gl = plan.g >> level
             terms = [tuple(f[m].copy() for f in fs) for m in range(fs[0].shape[0])]
-            if getattr(plan.op, "point_diagonal", None) is not None and level > 0:
+            if getattr(plan.op, "point_stencil", None) is not None and level == 0:
+                op = StructuredOperator("3d", gl, terms, point_stencil=plan.point_stencil(0))      # the factors plus the 27 planes
+                if shift:
+                    op = op.shifted(float(shift))
+                return tag_structured(op.tocsr(), op)
+            if _has_point(plan.op) and level > 0:
                 # the Kronecker part's level plus the 27 planes of R D P the library formed
                 n = gl ** 3
                 M = StructuredOperator("3d", gl, terms).tocsr() + planes_to_csr(plan.point_stencil(level))

@@ -371,6 +371,53 @@ int mgcmt_rq_history(mgcmt_plan* plan, int first, int count, double* out, void* 
  * coarse iterates added on the way up (:116-118) and nu2 more steps per level; vectors as for mgcmt_rqmin, on every level.
  * One launch sequence without a host round trip, replayed as a HIP graph from its second call. */
 int mgcmt_vcycle_rqmg(mgcmt_plan* plan, int slot, const int* vecs, int nu1, int nu2, int robust, double* rho_out, void* stream);
+/* Solve (A - mu I) x = f to a tolerance on level 0 of a whole-grid plan: conjugate gradients preconditioned by one V-cycle per
+ * iteration (an addition: every cycle entry of the reference runs a fixed number of cycles).  mu is the plan's shift 0, the one
+ * a cycle uses for column 0.  Layout: the residual r lives in F[0] column 0 (the cycle's right-hand side, which a cycle leaves
+ * alone), the preconditioned residual z is V[0] column 0 (the cycle's result), and x, p, q and a spare p2 are four distinct
+ * columns vecs[0..3] of slot W on level 0; the plan stores at least 4 vectors.  All scalars (rho, alpha, beta, the norms, the
+ * iteration count, the stop word) and the history of ||r_k|| (MGCMT_RQ_HISTORY numbers) stay on the device.
+ *   mgcmt_pcg_begin: the caller has put f into F[0] column 0 and — unless MGCMT_PCG_ZERO_START — x_0 into x.  Forms
+ *     r = f - (A - mu I) x_0 in place (zero start: no operator application, x <- 0), records ||f|| and ||r_0||, clears the state
+ *     and the history.  MGCMT_PCG_FLEXIBLE: beta = -alpha_old <z, q_old> / rho_old (Polak-Ribiere with r - r_old = -alpha q: no
+ *     extra vector; equal to rho / rho_old for a symmetric preconditioner such as the weighted-Jacobi cycle, and the right
+ *     form for the multicolour cycle, which is not symmetric) instead of beta = rho / rho_old.
+ *   mgcmt_pcg_iterate: queues `iterations` iterations without synchronising.  One iteration: z = one mgcmt_vcycle of r
+ *     (MGCMT_CYCLE_ZERO_START, k = 1; nu1, nu2, nu_coarse, kind, omega are the cycle's); rho = <z, r> and sigma = <z, q> in one
+ *     pass; beta; p <- z + beta p; q <- (A - mu I) p; <p, q>; alpha = rho / <p, q>; x += alpha p, r -= alpha q and <r, r> in one pass;
+ *     ||r|| into the history, and the stop word set when ||r|| <= rtol ||f|| (converged) or when rho or <p, q> is zero or not
+ *     finite (breakdown).  Once the stop word is set the passes and scalar kernels of every later iteration return without
+ *     writing (the cycle and the operator application still run, on scratch): x is the iterate of the first iteration that
+ *     met the tolerance however many were queued.  A negative rho or <p, q> does not stop the iteration — the shifted systems
+ *     next to an eigenvalue are indefinite and converge — and sets MGCMT_PCG_INDEFINITE in the status.  Reductions add
+ *     per-block partial sums in a fixed order: results are bit-reproducible.  A smoother kind the plan's cycle refuses is the
+ *     cycle's error.  Writes: x, p, q of slot W, F[0] column 0, and what mgcmt_vcycle writes; with the marching direction pass
+ *     (MGCMT_OPT_PCG_MARCH) also p2: the direction of iteration k is in p for even k and in p2 for odd k (k = 1 the first).
+ *   mgcmt_pcg_status: the only synchronising call.  iterations_done: iterations completed since the begin; status:
+ *     MGCMT_PCG_RUNNING, _CONVERGED or _BREAKDOWN, plus MGCMT_PCG_INDEFINITE; fnorm: ||f||; history[k] = ||r_{k+1}|| for
+ *     k < min(capacity, MGCMT_RQ_HISTORY).  Any output may be NULL.
+ * MGCMT_ERR_UNSUPPORTED on a sharded plan, MGCMT_ERR_INVALID on a plan with fewer than 4 vectors or vecs that are not distinct.
+ * The general sparse plans (mgcmt_csr_*) have no such entry. */
+#define MGCMT_PCG_ZERO_START 1
+#define MGCMT_PCG_FLEXIBLE 2
+#define MGCMT_PCG_RUNNING 0
+#define MGCMT_PCG_CONVERGED 1
+#define MGCMT_PCG_BREAKDOWN 2
+#define MGCMT_PCG_INDEFINITE 0x100
+int mgcmt_pcg_begin(mgcmt_plan* plan, const int* vecs, double rtol, int flags, void* stream);
+int mgcmt_pcg_iterate(mgcmt_plan* plan, int iterations, int nu1, int nu2, int nu_coarse, int kind, double omega, void* stream);
+int mgcmt_pcg_status(mgcmt_plan* plan, int* iterations_done, int* status, double* fnorm, double* history, int capacity, void* stream);
+/* timing for scripts/bench_pcg.py: average milliseconds of `reps` launches of ONE pass of an iteration together with the scalar
+ * kernel that follows it (one untimed launch first), between two HIP events on `stream`, on the vectors of the solve in progress
+ * (after a mgcmt_pcg_begin and at least one iteration; the solve's vectors and scalars are scratch afterwards, and a stop word
+ * that is set makes every launch return at once).  MGCMT_PCG_PASS_MARCH on a level the marching pass does not cover:
+ * MGCMT_ERR_UNSUPPORTED. */
+#define MGCMT_PCG_PASS_DOTS 0      /* rho, sigma: 24 B per point */
+#define MGCMT_PCG_PASS_DIRECTION 1 /* p <- z + beta p: 24 B */
+#define MGCMT_PCG_PASS_CURVATURE 2 /* <p, q>: 16 B */
+#define MGCMT_PCG_PASS_UPDATE 3    /* x, r, <r, r>: 48 B */
+#define MGCMT_PCG_PASS_MARCH 4     /* direction + application + curvature in one march: 32 B */
+int mgcmt_pcg_time_pass(mgcmt_plan* plan, int pass, int reps, double* ms_out, void* stream);
 /* dst = sum_t coeffs[t] * (slots[t], vecs[t]), 1 <= nterms <= 4; dst may be one of the inputs (the updates
  * x <- x + delta p, MGCMTSolver.py:52, and the residual A x - rho M x, :22-23, in one pass each) */
 int mgcmt_lincomb(mgcmt_plan* plan, int level, int nterms, const double* coeffs, const int* slots, const int* vecs, int dst_slot,
@@ -540,6 +587,12 @@ typedef enum mgcmt_option {
                                Galerkin level below run as ONE down-leg and ONE up-leg launch (fused2_kernel.h; 2 sweeps per leg
                                on the level below, a no-store last down pass on the level itself, no Gram-Schmidt, no strips):
                                the same arithmetic, the same bits; 2: on every eligible level; 0: never */
+  MGCMT_OPT_PCG_MARCH = 9,  /* mgcmt_pcg_iterate on 2-D plans whose level 0 mgcmt_ritz_pair handles in one march (a 5-point operator, with or
+                               without a product potential): 1 = direction, operator application and <p, q> as ONE marching launch
+                               (32 bytes per point instead of 64; the new direction goes to the spare vector p2, which exchanges its
+                               role with p every iteration), 0 = the generic passes; both give the same p and q bit for bit.  Not set
+                               (or a negative value): the environment variable MGCMT_PCG_MARCH, read per call, else 1 (the faster
+                               iteration at 8192^2) */
   MGCMT_OPT_TAIL = 4        /* default 1: the 2-D levels of at most 32 x 32 points below a cycle's top level, coarse solve
                                included, run as ONE launch (needs MGCMT_OPT_FUSED; not with Gram-Schmidt): a dense product
                                with the tail's matrix — the sub-cycle is linear in its right-hand side for fixed shift,

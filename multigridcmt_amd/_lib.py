@@ -30,6 +30,7 @@ OPT_MGS_BLOCK = 7
 OPT_GRAPH = 2
 OPT_RECOMPUTE = 3
 OPT_TWO_LEVEL = 8
+OPT_PCG_MARCH = 9
 
 
 class MgcmtError(RuntimeError):
@@ -77,6 +78,9 @@ PATH3D_GENERAL_POINT = 4        # ... general terms + point diagonal (a fine lev
 PATH3D_SEVEN_BONDS, PATH3D_GENERAL_BONDS = 5, 6    # ... level 0 of a plan with per-point bonds (mgcmt_plan_create3d_bonds)
 PATH3D_SEVEN_PLANES = 7         # ... constant 7-point + 27 planes: level 0 of a plan with a point stencil (mgcmt_plan_create3d_stencil)
 HALO_RING = 0x100
+PCG_ZERO_START, PCG_FLEXIBLE = 1, 2            # flags of mgcmt_pcg_begin
+PCG_PASS_DOTS, PCG_PASS_DIRECTION, PCG_PASS_CURVATURE, PCG_PASS_UPDATE, PCG_PASS_MARCH = range(5)    # mgcmt_pcg_time_pass
+PCG_RUNNING, PCG_CONVERGED, PCG_BREAKDOWN, PCG_INDEFINITE = 0, 1, 2, 0x100    # status of mgcmt_pcg_status (the last one a bit)
 
 _SIGNATURES = {
     "mgcmt_last_error": (c_char_p, []),
@@ -128,6 +132,10 @@ _SIGNATURES = {
     "mgcmt_vcycle_rqmg": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, _dp, c_void_p]),
     "mgcmt_rq_line_step": (c_int, [c_void_p, c_int] + [ctypes.POINTER(c_int)] * 5 + [c_int, c_int, c_void_p]),
     "mgcmt_rq_history": (c_int, [c_void_p, c_int, c_int, _dp, c_void_p]),
+    "mgcmt_pcg_begin": (c_int, [c_void_p, ctypes.POINTER(c_int), c_double, c_int, c_void_p]),
+    "mgcmt_pcg_iterate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_void_p]),
+    "mgcmt_pcg_status": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), _dp, _dp, c_int, c_void_p]),
+    "mgcmt_pcg_time_pass": (c_int, [c_void_p, c_int, c_int, _dp, c_void_p]),
     "mgcmt_lincomb": (c_int, [c_void_p, c_int, c_int, _dp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_int, c_void_p]),
     "mgcmt_scale": (c_int, [c_void_p, c_int, c_double, c_int, c_int, c_void_p]),
     "mgcmt_block_gram": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int), POINTER(c_int),

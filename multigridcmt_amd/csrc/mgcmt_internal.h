@@ -369,4 +369,45 @@ int launch_rq3_pass2(hipStream_t s, const K3Op& A, const K3Op& Mo, int m_identit
 bool launch_rq3_gmg(hipStream_t s, const K3Op& Mo, const double* gv, double* partials, int nblocks);
 bool launch_rq3_small(hipStream_t s, const K3Op& A, const K3Op& Mo, int m_identity, double* x, double* p, double* gv, double* state, int nu, int robust);
 
+// V-cycle-preconditioned conjugate gradients (kernels_pcg.hip; the driver is pcg_host.hip).  One device block per plan:
+// kPcgStateWords state words, MGCMT_RQ_HISTORY residual norms, kPcgSums * kPcgMaxBlocks partial sums.  Every pass works on
+// the contiguous interior of a level vector (n doubles), so one set serves 1-D, 2-D and 3-D levels.  Every kernel but the
+// two of launch_pcg_begin reads the stop word first and returns without writing once it is set.
+enum {
+  kPcgRho = 0,   // <z, r> of the current iteration
+  kPcgRhoOld,    // ... of the previous one
+  kPcgSigma,     // <z, q_old>
+  kPcgBeta,
+  kPcgAlpha,
+  kPcgPq,        // <p, q>
+  kPcgRR,        // <r, r>
+  kPcgFnorm,     // ||f||
+  kPcgR0norm,    // ||r_0||
+  kPcgRtol,
+  kPcgFlexible,  // 1: beta = -alpha_old sigma / rho_old
+  kPcgStop,      // != 0: frozen
+  kPcgStatus,    // 0 running, 1 converged, 2 breakdown
+  kPcgIndefinite,  // 1 once a rho or <p, q> was negative
+  kPcgIter,      // iterations done
+  kPcgStateWords = 32
+};
+constexpr int kPcgSums = 2;
+constexpr int kPcgMaxBlocks = 2048;    // workgroups of a flat pass
+constexpr int kPcgPartialCap = 8192;   // partial sums per result the block holds (the marching pass: one per column group and row chunk)
+inline long pcg_block_doubles() { return kPcgStateWords + MGCMT_RQ_HISTORY + (long)kPcgSums * kPcgPartialCap; }
+inline double* pcg_history(double* block) { return block + kPcgStateWords; }
+inline double* pcg_partials(double* block) { return block + kPcgStateWords + MGCMT_RQ_HISTORY; }
+// r <- r - q (q = (A - mu I) x0; q == nullptr: the start vector is zero, x <- 0 and r stays f), ||f|| and ||r_0|| from the same
+// pass, the state and the history cleared
+void launch_pcg_begin(hipStream_t s, long n, double* r, const double* q, double* x, double* block, double rtol, int flexible);
+void launch_pcg_dots(hipStream_t s, long n, const double* z, const double* r, const double* q, double* block);        // rho, sigma; then beta
+void launch_pcg_direction(hipStream_t s, long n, const double* z, double* p, double* block);                          // p <- z + beta p
+void launch_pcg_curvature(hipStream_t s, long n, const double* p, const double* q, double* block);                    // <p, q>; then alpha
+void launch_pcg_update(hipStream_t s, long n, double* x, const double* p, double* r, const double* q, double* block); // x, r, <r, r>; then the norm, the history, the stop word
+// direction, application and curvature in ONE march on the 2-D levels launch_ritz_pair covers (a 5-point operator, with or
+// without a product potential): p2 <- z + beta p, q <- (A - mu I) p2 and <p2, q>, then alpha; p and p2 are distinct (neighbouring
+// threads read the old p).  The bits of launch_pcg_direction + launch_apply; only the order of the partial sums of <p, q> differs.
+// false: the level is not covered, nothing was launched
+bool launch_pcg_march(hipStream_t s, KGrid g, KOp op, const double* z, const double* p, double* p2, double* q, const double* shifts, double* block);
+
 }  // namespace mgcmt

@@ -497,6 +497,10 @@ int mgcmt_plan_set_option(mgcmt_plan* p, int option, int value) {
     p->graphs_invalidate();
     return MGCMT_OK;
   }
+  if (option == MGCMT_OPT_PCG_MARCH) {
+    p->pcg_march = value < 0 ? -1 : (value != 0 ? 1 : 0);
+    return MGCMT_OK;
+  }
   if (option == MGCMT_OPT_GRAPH) {
     p->use_graph = value != 0;
     return MGCMT_OK;

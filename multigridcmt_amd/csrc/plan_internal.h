@@ -1,5 +1,6 @@
 // Host-side types of libmgcmt_hip.so and what its host files share: hierarchy.hip (Galerkin hierarchy, plan creation),
-// cycle.hip (single-GPU cycle, HIP-graph cache), rq_host.hip (Rayleigh-quotient drivers), plan.hip (checks, vector
+// cycle.hip (single-GPU cycle, HIP-graph cache), rq_host.hip (Rayleigh-quotient drivers), pcg_host.hip (the solve to a
+// tolerance), plan.hip (checks, vector
 // storage, the rest of the C-ABI) and sharded.hip (communicator, sharded cycle).  Not part of the ABI.
 #pragma once
 #include <functional>
@@ -85,6 +86,11 @@ struct mgcmt_plan {
   bool use_mgs_block = true;
   long mgs_block_min = 0;  // points per column from which a single plan takes the blocked form (0: wherever the one-workgroup kernel does not apply)
   double* d_rqhistory = nullptr;  // Rayleigh quotients recorded by mgcmt_rq_line_step (MGCMT_RQ_HISTORY numbers)
+  // preconditioned conjugate gradients (pcg_host.hip): state words, residual history and partial sums in one block
+  // (pcg_block_doubles()), the four vectors of slot W that mgcmt_pcg_begin was given (x, p, q, p2), -1 before a begin
+  double* d_pcg = nullptr;
+  int pcg_vecs[4] = {-1, -1, -1, -1};
+  int pcg_march = -1;  // MGCMT_OPT_PCG_MARCH: 1 / 0 = the marching direction pass on / off, -1 = not set (MGCMT_PCG_MARCH, else the default)
   std::vector<double> h_shifts;
   bool has_mass = false;
   bool has_point = false;  // A carries a per-point part (mgcmt_plan_create_pot / _bonds / mgcmt_plan_create3d_pot / _bonds): KOp::point / K3Op::point on every level

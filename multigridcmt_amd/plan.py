@@ -337,6 +337,35 @@ class Plan:
         check(_lib.lib().mgcmt_rq_history(self._h, int(first), int(count), _lib.as_dp(out), stream))
         return out
 
+    def pcg_begin(self, vecs, rtol, zero_start=False, flexible=False, stream=None):
+        """Start a V-cycle-preconditioned conjugate-gradient solve of (A - mu I) x = f on level 0 (mgcmt_pcg_begin): f is in
+        F[0] column 0 and, unless zero_start, x_0 in column vecs[0] of slot W; vecs = four distinct columns of W (x, p, q, p2).
+        mu is the plan's shift 0.  Nothing synchronises."""
+        v = (ctypes.c_int * 4)(*[int(i) for i in vecs])
+        flags = (_lib.PCG_ZERO_START if zero_start else 0) | (_lib.PCG_FLEXIBLE if flexible else 0)
+        check(_lib.lib().mgcmt_pcg_begin(self._h, v, c_double(rtol), flags, stream))
+
+    def pcg_iterate(self, iterations, nu1, nu2, kind, omega=1.0, nu_coarse=4, stream=None):
+        """Queue `iterations` iterations (one cycle, one operator application and four fused passes each) without
+        synchronising; the ones behind the iteration that meets the tolerance change nothing (mgcmt_pcg_iterate)."""
+        check(_lib.lib().mgcmt_pcg_iterate(self._h, int(iterations), int(nu1), int(nu2), int(nu_coarse), kind, c_double(omega), stream))
+
+    def pcg_status(self, history=0, stream=None):
+        """(iterations done, status, indefinite, ||f||, the first `history` recorded ||r_k||) — the one synchronisation of a
+        solve (mgcmt_pcg_status); status is _lib.PCG_RUNNING, PCG_CONVERGED or PCG_BREAKDOWN."""
+        it, st, fnorm = c_int(0), c_int(0), c_double(0.0)
+        hist = np.zeros(int(history))
+        check(_lib.lib().mgcmt_pcg_status(self._h, ctypes.byref(it), ctypes.byref(st), ctypes.byref(fnorm), as_dp(hist) if hist.size else None,
+                                          hist.size, stream))
+        return it.value, st.value & 0xff, bool(st.value & _lib.PCG_INDEFINITE), fnorm.value, hist
+
+    def pcg_time_pass(self, which, reps, stream=None):
+        """average milliseconds of one pass of a conjugate-gradient iteration (_lib.PCG_PASS_*) with its scalar kernel, on the
+        vectors of the solve in progress, which are scratch afterwards (mgcmt_pcg_time_pass)"""
+        ms = c_double(0.0)
+        check(_lib.lib().mgcmt_pcg_time_pass(self._h, int(which), int(reps), ctypes.byref(ms), stream))
+        return ms.value
+
     def lincomb(self, level, terms, dst, stream=None):
         """dst <- sum of coeff * (slot, vec) over `terms` = [(coeff, (slot, vec)), ...] (at most four)."""
         nt = len(terms)

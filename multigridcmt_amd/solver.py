@@ -440,6 +440,75 @@ class MGCMTSolver:
                 plan.vcycle(int(nu1), int(nu2), kind, omega=omega, k=1, nu_coarse=int(nu_coarse), level=l)
         return plan.download(0, SLOT_V, 0)
 
+    _PCG_X, _PCG_P, _PCG_Q, _PCG_P2 = range(4)      # columns of slot W: the iterate, the direction, (A - shift I) p, a spare
+
+    def solve(self, f, A, stencil_maker, v0=None, nu1=2, nu2=2, smoother=None, shift=0, lowest_level=2, dimension="1d", *,
+              nu_coarse=4, rtol=1e-8, maxiter=100, check_every=4, flexible=None, info=None):
+        """Solve (A - shift I) x = f to ``||f - (A - shift I) x|| <= rtol ||f||`` (an ADDITION: every cycle entry of the reference
+        runs a fixed number of cycles and leaves the convergence test to its caller): conjugate gradients preconditioned by one
+        V-cycle of ``vcycle`` per iteration — V(nu1,nu2) on the fine level, V(nu_coarse,nu_coarse) below, this class's smoothers —
+        resident on the device (mgcmt_pcg_begin / _iterate / _status): the scalars of an iteration never visit the host, which
+        reads the status once per ``check_every`` queued iterations; the iterations queued behind the one that met the tolerance
+        change nothing, so the result does not depend on ``check_every``.  Works where the plain cycle stalls — a shift next to
+        an eigenvalue, where the system is indefinite — and converges in fewer iterations than cycles elsewhere.
+        ``v0=None`` (or zeros): a zero start.  ``flexible``: beta = -alpha <z, q_old> / rho_old, the form for a preconditioner that
+        is not symmetric; None = rho / rho_old for wjacobi (its V(nu,nu) cycle is symmetric), the flexible form for the others.
+        ``info`` (a dict) receives iterations, status ("converged", "maxiter", "breakdown"), indefinite (a negative <z, r> or
+        <p, A p> was met), residuals (the recorded ||r_k|| / ||f||, k = 1 ..) and true_residual (||f - (A - shift I) x|| / ||f||
+        recomputed from x).  Returns x, 1-D; bad sizes print and return None as in ``vcycle``."""
+        kind, omega = self._resolve_smoother(smoother)
+        if kind is None:
+            raise NotImplementedError("solve (an addition, not a reference function) takes this class's smoothers only")
+        if dimension == "3d":
+            _check_3d_smoother(kind)
+        self._check_stencil_maker(stencil_maker, dimension)
+        maxiter, check_every = int(maxiter), int(check_every)
+        if not 0 <= maxiter <= _lib.RQ_HISTORY:
+            raise ValueError("maxiter must be in 0 .. %d (the device-side residual history)" % _lib.RQ_HISTORY)
+        if check_every < 1:
+            raise ValueError("check_every must be at least 1")
+        f = np.asarray(f, dtype=np.float64).reshape(-1)
+        n = len(f)
+        g = self._grid(n, dimension)
+        if not self._check_grid(g, lowest_level):
+            return None
+        op = _recognise_entry(A, dimension)            # (a 1-D matrix only the general sparse path handles raises UnrecognisedOperator)
+        _check_point_smoother(op, kind)
+        plan = get_plan(op, int(lowest_level), nvec=4)
+        plan.set_shifts([float(shift)])
+        X = (SLOT_W, self._PCG_X)
+        zero_start = v0 is None or _all_zero(np.asarray(v0))
+        if not zero_start:
+            v0 = np.asarray(v0, dtype=np.float64).reshape(-1)
+            if len(v0) != n:
+                raise ValueError("dimension mismatch: a start vector of %d for a right-hand side of %d" % (len(v0), n))
+            plan.upload(0, X[0], X[1], v0)
+        plan.upload(0, SLOT_F, 0, f)
+        if flexible is None:
+            flexible = kind != WJACOBI
+        plan.pcg_begin([self._PCG_X, self._PCG_P, self._PCG_Q, self._PCG_P2], float(rtol), zero_start=zero_start, flexible=bool(flexible))
+        queued, status = 0, _lib.PCG_RUNNING
+        while status == _lib.PCG_RUNNING and queued < maxiter:
+            chunk = min(check_every, maxiter - queued)
+            plan.pcg_iterate(chunk, int(nu1), int(nu2), kind, omega=omega, nu_coarse=int(nu_coarse))
+            queued += chunk
+            status = plan.pcg_status()[1]
+        x = plan.download(0, X[0], X[1])
+        if isinstance(info, dict):
+            done, status, indefinite, fnorm, hist = plan.pcg_status(history=maxiter)
+            info["iterations"] = done
+            info["status"] = {_lib.PCG_CONVERGED: "converged", _lib.PCG_BREAKDOWN: "breakdown"}.get(status, "maxiter")
+            info["indefinite"] = indefinite
+            info["residuals"] = hist[:done] / fnorm if fnorm > 0 else hist[:done]
+            # the residual recomputed from x: f again (r has replaced it on the device), one application, one inner product
+            P, Q = (SLOT_W, self._PCG_P), (SLOT_W, self._PCG_Q)
+            plan.upload(0, P[0], P[1], f)
+            plan.apply(0, X, Q, with_shift=True)       # (column 0: the shift of column 0)
+            plan.axpy(0, -1.0, Q, P)
+            rr = plan.dot(0, P, P)
+            info["true_residual"] = math.sqrt(rr) / fnorm if fnorm > 0 else math.sqrt(rr)
+        return x
+
     def twogrid(self, v0, f, A, stencil_maker, nu1=4, nu2=4, smoother=None, shift=0, dimension="1d"):
         """MGCMTSolver.py:331-371 — pre-smooth, exact solve of (R A P - shift I) on the next grid,
         post-smooth.  (The reference sizes the coarse shift as n/2 (:350) and therefore only runs in

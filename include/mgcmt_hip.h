@@ -407,6 +407,37 @@ int mgcmt_vcycle_rqmg(mgcmt_plan* plan, int slot, const int* vecs, int nu1, int 
 int mgcmt_pcg_begin(mgcmt_plan* plan, const int* vecs, double rtol, int flags, void* stream);
 int mgcmt_pcg_iterate(mgcmt_plan* plan, int iterations, int nu1, int nu2, int nu_coarse, int kind, double omega, void* stream);
 int mgcmt_pcg_status(mgcmt_plan* plan, int* iterations_done, int* status, double* fnorm, double* history, int capacity, void* stream);
+/* The same solve for k systems at once, (A - mu_c I) x_c = f_c for c = 0 .. k - 1, 1 <= k <= MGCMT_PCG_MAX_COLUMNS: the shape of
+ * a shift-and-invert step on k columns, one shift per column, each next to its own eigenvalue.  mu_c is the plan's shift c.  The
+ * columns are independent systems (no Gram-Schmidt) that share every launch: the column is a grid dimension of every kernel.
+ * Layout: r_c lives in F[0] column c, z_c is V[0] column c, and vecs[0..3] are the FIRST columns of four ranges of k consecutive
+ * columns of slot W on level 0 — x, p, q and the spare p2; column c uses vecs[a] + c.  The ranges must not overlap and must lie
+ * within the plan's vectors: nvec >= 4 k (k = 16: nvec = 64 <= MGCMT_MAX_STORE_VEC).  One rtol and one beta form for all columns.
+ *   mgcmt_pcg_begin_k: as mgcmt_pcg_begin, per column.  A column whose f is zero, or whose start vector already meets the
+ *     tolerance, sets its own stop word here.  The state (k blocks of scalars, k histories, k sets of partial sums) is one device
+ *     allocation, made by the first batched begin and grown when a later one has more columns.
+ *   mgcmt_pcg_iterate_k: queues `iterations` iterations without synchronising.  One iteration: ONE mgcmt_vcycle on k columns
+ *     (zero start, no Gram-Schmidt), then the passes and scalar kernels of mgcmt_pcg_iterate with k times the workgroups, the
+ *     marching direction pass where mgcmt_pcg_iterate takes it (same gate, same option).  Columns freeze independently: once a
+ *     column's stop word is set (converged or breakdown) every pass and scalar kernel returns for that column before it writes,
+ *     and the other columns go on.  The cycle and the operator application do not know of the stop words: they still run for
+ *     frozen columns, on scratch (z_c and q_c, which nothing reads again) — an iteration costs k columns until the LAST column
+ *     stops.  Per column the workgroup count and the order of every sum are those of the single solve and do not depend on k:
+ *     where the k-column cycle gives each column the bits of its own k = 1 cycle, column c carries the bits of mgcmt_pcg_* run
+ *     alone on (f_c, mu_c).  Writes: the ranges x, p, q (with the marching pass also p2), F[0] columns 0 .. k - 1, and what a
+ *     k-column mgcmt_vcycle writes.
+ *   mgcmt_pcg_status_k: one copy, one synchronisation.  running: the number of columns without a stop word (kept on the device
+ *     as a count of stopped columns, so the host reads one word to decide whether to queue more); iterations_done[k], status[k],
+ *     fnorm[k] as in mgcmt_pcg_status, per column; history: k rows of `capacity` numbers.  Any output may be NULL.
+ * A batched begin ends a single solve on the same plan and the reverse (they share F, V and W): the other kind's iterate /
+ * status then returns MGCMT_ERR_INVALID, as before any begin.  MGCMT_ERR_UNSUPPORTED on a sharded plan; MGCMT_ERR_INVALID for k
+ * out of range and for column ranges that overlap or leave the plan's vectors.  mgcmt_pcg_time_pass after a batched begin times
+ * the pass on the k columns. */
+#define MGCMT_PCG_MAX_COLUMNS 16
+int mgcmt_pcg_begin_k(mgcmt_plan* plan, int k, const int* vecs, double rtol, int flags, void* stream);
+int mgcmt_pcg_iterate_k(mgcmt_plan* plan, int iterations, int nu1, int nu2, int nu_coarse, int kind, double omega, void* stream);
+int mgcmt_pcg_status_k(mgcmt_plan* plan, int* running, int* iterations_done, int* status, double* fnorm, double* history, int capacity,
+                       void* stream);
 /* timing for scripts/bench_pcg.py: average milliseconds of `reps` launches of ONE pass of an iteration together with the scalar
  * kernel that follows it (one untimed launch first), between two HIP events on `stream`, on the vectors of the solve in progress
  * (after a mgcmt_pcg_begin and at least one iteration; the solve's vectors and scalars are scratch afterwards, and a stop word

@@ -79,6 +79,7 @@ PATH3D_SEVEN_BONDS, PATH3D_GENERAL_BONDS = 5, 6    # ... level 0 of a plan with 
 PATH3D_SEVEN_PLANES = 7         # ... constant 7-point + 27 planes: level 0 of a plan with a point stencil (mgcmt_plan_create3d_stencil)
 HALO_RING = 0x100
 PCG_ZERO_START, PCG_FLEXIBLE = 1, 2            # flags of mgcmt_pcg_begin
+PCG_MAX_COLUMNS = 16                          # systems of one mgcmt_pcg_begin_k
 PCG_PASS_DOTS, PCG_PASS_DIRECTION, PCG_PASS_CURVATURE, PCG_PASS_UPDATE, PCG_PASS_MARCH = range(5)    # mgcmt_pcg_time_pass
 PCG_RUNNING, PCG_CONVERGED, PCG_BREAKDOWN, PCG_INDEFINITE = 0, 1, 2, 0x100    # status of mgcmt_pcg_status (the last one a bit)
 
@@ -135,6 +136,9 @@ _SIGNATURES = {
     "mgcmt_pcg_begin": (c_int, [c_void_p, ctypes.POINTER(c_int), c_double, c_int, c_void_p]),
     "mgcmt_pcg_iterate": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_void_p]),
     "mgcmt_pcg_status": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), _dp, _dp, c_int, c_void_p]),
+    "mgcmt_pcg_begin_k": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int), c_double, c_int, c_void_p]),
+    "mgcmt_pcg_iterate_k": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_void_p]),
+    "mgcmt_pcg_status_k": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), _dp, _dp, c_int, c_void_p]),
     "mgcmt_pcg_time_pass": (c_int, [c_void_p, c_int, c_int, _dp, c_void_p]),
     "mgcmt_lincomb": (c_int, [c_void_p, c_int, c_int, _dp, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_int, c_void_p]),
     "mgcmt_scale": (c_int, [c_void_p, c_int, c_double, c_int, c_int, c_void_p]),

@@ -15,6 +15,15 @@
 // Once the stop word is set (convergence, or a rho / <p, q> that is zero or not finite) every kernel of an iteration returns
 // before it writes: x, p, r, the scalars and the history stay those of the iteration that set it, however many iterations
 // the host has queued behind it.
+//
+// Columns.  Every kernel works on k independent systems at once (mgcmt_pcg_begin_k; the single solve is k = 1): the column is
+// a grid dimension — y of the flat passes, z of the marching pass, x of the one-workgroup scalar kernels —, a workgroup works
+// on exactly one column, and the vectors, the state words, the history and the partial sums of column c are those of column 0
+// moved by c strides (PcgCols, mgcmt_internal.h).  The stop test is per column, the first thing a workgroup does and uniform
+// over it (the reductions have barriers): a frozen column's workgroups return while the others go on.  Per column the number of
+// workgroups and the order of every sum are those of k = 1, so a column carries the bits of the same system solved alone.  A
+// column that sets its stop word also adds one to the block's count of stopped columns (an atomic: nothing else passes between
+// workgroups of a launch), which is all the host reads to decide whether to queue more.
 #include <initializer_list>
 
 #include "rq_common.h"
@@ -67,20 +76,30 @@ __device__ __forceinline__ void pcg_totals(const double* __restrict__ partials, 
   __syncthreads();
 }
 
-__device__ __forceinline__ void pcg_break(double* __restrict__ state) {
+// the column's stop word and status (1 converged, 2 breakdown); set once per solve, so the count of stopped columns gets one
+__device__ __forceinline__ void pcg_stop(double* __restrict__ state, unsigned* stopped, double status) {
   state[kPcgStop] = 1.0;
-  state[kPcgStatus] = 2.0;
+  state[kPcgStatus] = status;
+  if (stopped) atomicAdd(stopped, 1u);
 }
+__device__ __forceinline__ void pcg_break(double* __restrict__ state, unsigned* stopped) { pcg_stop(state, stopped, 2.0); }
+
+// column `col` of a block: its state words, history, partial sums
+__device__ __forceinline__ double* pcg_col_state(const PcgCols& c, int col) { return c.state + (long)col * kPcgStateWords; }
+__device__ __forceinline__ double* pcg_col_history(const PcgCols& c, int col) { return c.history + (long)col * MGCMT_RQ_HISTORY; }
+__device__ __forceinline__ double* pcg_col_partials(const PcgCols& c, int col) { return c.partials + (long)col * kPcgColPartials; }
 
 // ---- begin: r = f - (A - mu I) x0 in place, ||f||^2 and ||r_0||^2 ----------------------------------------------------------
 template <bool VEC2>
 __global__ void __launch_bounds__(kPcgThreads) k_pcg_begin(long n, double* __restrict__ r_, const double* __restrict__ q_, double* __restrict__ x_,
-                                                           double* __restrict__ partials) {
+                                                           PcgCols cols) {
   typedef typename PcgElem<VEC2>::type E;
   __shared__ double s_part[kPcgSums][kPcgThreads / 64];
-  E* r = (E*)r_;
-  const E* q = (const E*)q_;
-  E* x = (E*)x_;
+  const int col = blockIdx.y;
+  double* partials = pcg_col_partials(cols, col);
+  E* r = (E*)(r_ + col * cols.stride);
+  const E* q = q_ ? (const E*)(q_ + col * cols.stride) : nullptr;
+  E* x = x_ ? (E*)(x_ + col * cols.stride) : nullptr;
   double acc[kPcgSums] = {0.0, 0.0};
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     E rv = r[i];
@@ -98,10 +117,13 @@ __global__ void __launch_bounds__(kPcgThreads) k_pcg_begin(long n, double* __res
   block_partials<kPcgSums>(acc, s_part, partials, gridDim.x, blockIdx.x);
 }
 
-__global__ void __launch_bounds__(kPcgThreads) k_pcg_begin_scalars(const double* __restrict__ partials, int nblocks, double* __restrict__ state,
-                                                                   double* __restrict__ history, double rtol, int flexible) {
+__global__ void __launch_bounds__(kPcgThreads) k_pcg_begin_scalars(PcgCols cols, int nblocks, double rtol, int flexible) {
   __shared__ double s_part[kPcgSums][kPcgThreads / 64];
   __shared__ double s_tot[kPcgSums];
+  const int col = blockIdx.x;
+  const double* partials = pcg_col_partials(cols, col);
+  double* state = pcg_col_state(cols, col);
+  double* history = pcg_col_history(cols, col);
   pcg_totals<kPcgSums>(partials, nblocks, s_part, s_tot);
   for (int i = threadIdx.x; i < MGCMT_RQ_HISTORY; i += kPcgThreads) history[i] = 0.0;
   if (threadIdx.x != 0) return;
@@ -114,24 +136,25 @@ __global__ void __launch_bounds__(kPcgThreads) k_pcg_begin_scalars(const double*
   state[kPcgRtol] = rtol;
   state[kPcgFlexible] = flexible ? 1.0 : 0.0;
   if (!pcg_finite(ff) || !pcg_finite(rr)) {
-    pcg_break(state);
+    pcg_break(state, cols.stopped);
   } else if (rnorm <= rtol * fnorm) {  // the start vector already solves the system (f = 0 included)
-    state[kPcgStop] = 1.0;
-    state[kPcgStatus] = 1.0;
+    pcg_stop(state, cols.stopped, 1.0);
   }
 }
 
 // ---- dots: rho = <z, r>, sigma = <z, q> (q: the previous iteration's (A - mu I) p; not read on the first) -------------------
 template <bool VEC2>
 __global__ void __launch_bounds__(kPcgThreads) k_pcg_dots(long n, const double* __restrict__ z_, const double* __restrict__ r_,
-                                                          const double* __restrict__ q_, const double* __restrict__ state,
-                                                          double* __restrict__ partials) {
+                                                          const double* __restrict__ q_, PcgCols cols) {
+  const int col = blockIdx.y;
+  const double* state = pcg_col_state(cols, col);
   if (state[kPcgStop] != 0.0) return;
   typedef typename PcgElem<VEC2>::type E;
   __shared__ double s_part[kPcgSums][kPcgThreads / 64];
-  const E* z = (const E*)z_;
-  const E* r = (const E*)r_;
-  const E* q = (const E*)q_;
+  double* partials = pcg_col_partials(cols, col);
+  const E* z = (const E*)(z_ + col * cols.stride);
+  const E* r = (const E*)(r_ + col * cols.stride);
+  const E* q = (const E*)(q_ + col * cols.stride);
   const bool first = state[kPcgIter] == 0.0;
   double acc[kPcgSums] = {0.0, 0.0};
   if (first) {
@@ -148,8 +171,11 @@ __global__ void __launch_bounds__(kPcgThreads) k_pcg_dots(long n, const double* 
 
 // beta: rho / rho_old, or the flexible form -alpha_old sigma / rho_old — Polak-Ribiere's <z, r - r_old> / rho_old with
 // r - r_old = -alpha_old q, which needs no copy of r_old and equals the first form when the preconditioner is symmetric
-__global__ void __launch_bounds__(kPcgThreads) k_pcg_beta(const double* __restrict__ partials, int nblocks, double* __restrict__ state) {
+__global__ void __launch_bounds__(kPcgThreads) k_pcg_beta(PcgCols cols, int nblocks) {
+  const int col = blockIdx.x;
+  double* state = pcg_col_state(cols, col);
   if (state[kPcgStop] != 0.0) return;
+  const double* partials = pcg_col_partials(cols, col);
   __shared__ double s_part[kPcgSums][kPcgThreads / 64];
   __shared__ double s_tot[kPcgSums];
   pcg_totals<kPcgSums>(partials, nblocks, s_part, s_tot);
@@ -157,14 +183,14 @@ __global__ void __launch_bounds__(kPcgThreads) k_pcg_beta(const double* __restri
   const double rho = s_tot[0], sigma = s_tot[1];
   const bool first = state[kPcgIter] == 0.0;
   if (!pcg_finite(rho) || rho == 0.0 || !pcg_finite(sigma)) {
-    pcg_break(state);
+    pcg_break(state, cols.stopped);
     return;
   }
   const double rho_old = state[kPcgRho];
   double beta = 0.0;
   if (!first) beta = state[kPcgFlexible] != 0.0 ? -(state[kPcgAlpha] * sigma) / rho_old : rho / rho_old;
   if (!pcg_finite(beta)) {
-    pcg_break(state);
+    pcg_break(state, cols.stopped);
     return;
   }
   if (rho < 0.0) state[kPcgIndefinite] = 1.0;
@@ -176,12 +202,13 @@ __global__ void __launch_bounds__(kPcgThreads) k_pcg_beta(const double* __restri
 
 // ---- direction: p <- z + beta p (the first iteration: p <- z, p not read) ---------------------------------------------------
 template <bool VEC2>
-__global__ void __launch_bounds__(kPcgThreads) k_pcg_direction(long n, const double* __restrict__ z_, double* __restrict__ p_,
-                                                               const double* __restrict__ state) {
+__global__ void __launch_bounds__(kPcgThreads) k_pcg_direction(long n, const double* __restrict__ z_, double* __restrict__ p_, PcgCols cols) {
+  const int col = blockIdx.y;
+  const double* state = pcg_col_state(cols, col);
   if (state[kPcgStop] != 0.0) return;
   typedef typename PcgElem<VEC2>::type E;
-  const E* z = (const E*)z_;
-  E* p = (E*)p_;
+  const E* z = (const E*)(z_ + col * cols.stride);
+  E* p = (E*)(p_ + col * cols.stride);
   const double beta = state[kPcgBeta];
   if (state[kPcgIter] == 0.0) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = z[i];
@@ -193,19 +220,25 @@ __global__ void __launch_bounds__(kPcgThreads) k_pcg_direction(long n, const dou
 // ---- curvature: <p, q> -----------------------------------------------------------------------------------------------------------
 template <bool VEC2>
 __global__ void __launch_bounds__(kPcgThreads) k_pcg_curvature(long n, const double* __restrict__ p_, const double* __restrict__ q_,
-                                                               const double* __restrict__ state, double* __restrict__ partials) {
+                                                               PcgCols cols) {
+  const int col = blockIdx.y;
+  const double* state = pcg_col_state(cols, col);
   if (state[kPcgStop] != 0.0) return;
   typedef typename PcgElem<VEC2>::type E;
   __shared__ double s_part[1][kPcgThreads / 64];
-  const E* p = (const E*)p_;
-  const E* q = (const E*)q_;
+  double* partials = pcg_col_partials(cols, col);
+  const E* p = (const E*)(p_ + col * cols.stride);
+  const E* q = (const E*)(q_ + col * cols.stride);
   double acc[1] = {0.0};
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) acc[0] += pcg_prod(p[i], q[i]);
   block_partials<1>(acc, s_part, partials, gridDim.x, blockIdx.x);
 }
 
-__global__ void __launch_bounds__(kPcgThreads) k_pcg_alpha(const double* __restrict__ partials, int nblocks, double* __restrict__ state) {
+__global__ void __launch_bounds__(kPcgThreads) k_pcg_alpha(PcgCols cols, int nblocks) {
+  const int col = blockIdx.x;
+  double* state = pcg_col_state(cols, col);
   if (state[kPcgStop] != 0.0) return;
+  const double* partials = pcg_col_partials(cols, col);
   __shared__ double s_part[1][kPcgThreads / 64];
   __shared__ double s_tot[1];
   pcg_totals<1>(partials, nblocks, s_part, s_tot);
@@ -213,7 +246,7 @@ __global__ void __launch_bounds__(kPcgThreads) k_pcg_alpha(const double* __restr
   const double pq = s_tot[0];
   const double alpha = state[kPcgRho] / pq;
   if (!pcg_finite(pq) || pq == 0.0 || !pcg_finite(alpha)) {
-    pcg_break(state);
+    pcg_break(state, cols.stopped);
     return;
   }
   if (pq < 0.0) state[kPcgIndefinite] = 1.0;  // (conjugate gradients go on: the shifted systems next to an eigenvalue converge)
@@ -223,16 +256,18 @@ __global__ void __launch_bounds__(kPcgThreads) k_pcg_alpha(const double* __restr
 
 // ---- update: x += alpha p, r -= alpha q, <r, r> -----------------------------------------------------------------------------
 template <bool VEC2>
-__global__ void __launch_bounds__(kPcgThreads) k_pcg_update(long n, double* __restrict__ x_, const double* __restrict__ p_, double* __restrict__ r_,
-                                                            const double* __restrict__ q_, const double* __restrict__ state,
-                                                            double* __restrict__ partials) {
+__global__ void __launch_bounds__(kPcgThreads) k_pcg_update(long n, double* __restrict__ x_, const double* __restrict__ p_,
+                                                            double* __restrict__ r_, const double* __restrict__ q_, PcgCols cols) {
+  const int col = blockIdx.y;
+  const double* state = pcg_col_state(cols, col);
   if (state[kPcgStop] != 0.0) return;
   typedef typename PcgElem<VEC2>::type E;
   __shared__ double s_part[1][kPcgThreads / 64];
-  E* x = (E*)x_;
-  const E* p = (const E*)p_;
-  E* r = (E*)r_;
-  const E* q = (const E*)q_;
+  double* partials = pcg_col_partials(cols, col);
+  E* x = (E*)(x_ + col * cols.stride);
+  const E* p = (const E*)(p_ + col * cols.stride);
+  E* r = (E*)(r_ + col * cols.stride);
+  const E* q = (const E*)(q_ + col * cols.stride);
   const double alpha = state[kPcgAlpha];
   double acc[1] = {0.0};
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -244,9 +279,12 @@ __global__ void __launch_bounds__(kPcgThreads) k_pcg_update(long n, double* __re
   block_partials<1>(acc, s_part, partials, gridDim.x, blockIdx.x);
 }
 
-__global__ void __launch_bounds__(kPcgThreads) k_pcg_norm(const double* __restrict__ partials, int nblocks, double* __restrict__ state,
-                                                          double* __restrict__ history) {
+__global__ void __launch_bounds__(kPcgThreads) k_pcg_norm(PcgCols cols, int nblocks) {
+  const int col = blockIdx.x;
+  double* state = pcg_col_state(cols, col);
   if (state[kPcgStop] != 0.0) return;
+  const double* partials = pcg_col_partials(cols, col);
+  double* history = pcg_col_history(cols, col);
   __shared__ double s_part[1][kPcgThreads / 64];
   __shared__ double s_tot[1];
   pcg_totals<1>(partials, nblocks, s_part, s_tot);
@@ -258,10 +296,9 @@ __global__ void __launch_bounds__(kPcgThreads) k_pcg_norm(const double* __restri
   state[kPcgIter] = (double)(it + 1);
   state[kPcgRR] = rr;
   if (!pcg_finite(rr)) {
-    pcg_break(state);
+    pcg_break(state, cols.stopped);
   } else if (rnorm <= state[kPcgRtol] * state[kPcgFnorm]) {
-    state[kPcgStop] = 1.0;
-    state[kPcgStatus] = 1.0;
+    pcg_stop(state, cols.stopped, 1.0);
   }
 }
 
@@ -277,9 +314,16 @@ __global__ void __launch_bounds__(kPcgThreads) k_pcg_norm(const double* __restri
 template <int ND>
 __global__ void __launch_bounds__(256) k_pcg_march(KGrid g, KOp op, const double* __restrict__ z, const double* __restrict__ p,
                                                   double* __restrict__ p2, double* __restrict__ qout, const double* __restrict__ shifts, int rows,
-                                                  const double* __restrict__ state, double* __restrict__ partials, int nblocks) {
+                                                  PcgCols cols, int nblocks) {
+  const int col = blockIdx.z;  // its own shift, beta and first flag: a column on its first iteration and one on its fifth share a launch
+  const double* state = pcg_col_state(cols, col);
   if (state[kPcgStop] != 0.0) return;
   __shared__ double s_part[1][kPcgThreads / 64];
+  double* partials = pcg_col_partials(cols, col);
+  z += col * cols.stride;
+  p += col * cols.stride;
+  p2 += col * cols.stride;
+  qout += col * cols.stride;
   const long j = 2 * ((long)blockIdx.x * blockDim.x + threadIdx.x);
   const long nc = g.nc;
   const long i0 = (long)blockIdx.y * rows;
@@ -290,7 +334,7 @@ __global__ void __launch_bounds__(256) k_pcg_march(KGrid g, KOp op, const double
   if (j < nc) {
     const bool hw = j > 0, he = j + 2 < nc;
     const long jw = hw ? j - 1 : j, je = he ? j + 2 : j + 1;  // (clamped: the value is discarded)
-    const double cn = op.cn, cw = op.cw, d0 = op.c0 - shifts[0];
+    const double cn = op.cn, cw = op.cw, d0 = op.c0 - shifts[col];
     double qa[ND > 0 ? ND : 1], qb[ND > 0 ? ND : 1];
 #pragma unroll
     for (int m = 0; m < ND; ++m) {
@@ -334,15 +378,17 @@ __global__ void __launch_bounds__(256) k_pcg_march(KGrid g, KOp op, const double
   block_partials<1>(acc, s_part, partials, nblocks, (int)(blockIdx.y * gridDim.x + blockIdx.x));
 }
 
-// 16-byte accesses when every vector allows them
-bool pcg_vec2(long n, std::initializer_list<const void*> ptrs) {
+// 16-byte accesses when every vector allows them (k columns: every column's start, `stride` doubles apart)
+bool pcg_vec2(long n, const PcgCols& c, std::initializer_list<const void*> ptrs) {
   if (n & 1) return false;
+  if (c.k > 1 && (c.stride & 1)) return false;
   for (const void* p : ptrs)
     if (p && ((uintptr_t)p & 15)) return false;
   return true;
 }
 
-// workgroups of a pass over m elements: eight per thread, at most kPcgMaxBlocks
+// workgroups of a pass over m elements of ONE column: eight per thread, at most kPcgMaxBlocks (never a function of the
+// column count: a column's partial sums, and with them its bits, are those of the single solve)
 int pcg_blocks(long m) {
   long b = (m + (long)kPcgThreads * 8 - 1) / ((long)kPcgThreads * 8);
   if (b > kPcgMaxBlocks) b = kPcgMaxBlocks;
@@ -351,47 +397,46 @@ int pcg_blocks(long m) {
 
 }  // namespace
 
-void launch_pcg_begin(hipStream_t s, long n, double* r, const double* q, double* x, double* block, double rtol, int flexible) {
-  double* part = pcg_partials(block);
-  const bool v2 = pcg_vec2(n, {r, q, x});
+// Launch geometry: a flat pass is (pcg_blocks, k) workgroups of 256 threads, the scalar kernel behind it k workgroups.
+
+void launch_pcg_begin(hipStream_t s, long n, double* r, const double* q, double* x, const PcgCols& c, double rtol, int flexible) {
+  const bool v2 = pcg_vec2(n, c, {r, q, x});
   const long m = v2 ? n / 2 : n;
   const int nb = pcg_blocks(m);
-  if (v2) hipLaunchKernelGGL(k_pcg_begin<true>, dim3(nb), dim3(kPcgThreads), 0, s, m, r, q, x, part);
-  else hipLaunchKernelGGL(k_pcg_begin<false>, dim3(nb), dim3(kPcgThreads), 0, s, m, r, q, x, part);
-  hipLaunchKernelGGL(k_pcg_begin_scalars, dim3(1), dim3(kPcgThreads), 0, s, part, nb, block, pcg_history(block), rtol, flexible);
+  if (v2) hipLaunchKernelGGL(k_pcg_begin<true>, dim3(nb, c.k), dim3(kPcgThreads), 0, s, m, r, q, x, c);
+  else hipLaunchKernelGGL(k_pcg_begin<false>, dim3(nb, c.k), dim3(kPcgThreads), 0, s, m, r, q, x, c);
+  hipLaunchKernelGGL(k_pcg_begin_scalars, dim3(c.k), dim3(kPcgThreads), 0, s, c, nb, rtol, flexible);
 }
 
-void launch_pcg_dots(hipStream_t s, long n, const double* z, const double* r, const double* q, double* block) {
-  double* part = pcg_partials(block);
-  const bool v2 = pcg_vec2(n, {z, r, q});
+void launch_pcg_dots(hipStream_t s, long n, const double* z, const double* r, const double* q, const PcgCols& c) {
+  const bool v2 = pcg_vec2(n, c, {z, r, q});
   const long m = v2 ? n / 2 : n;
   const int nb = pcg_blocks(m);
-  if (v2) hipLaunchKernelGGL(k_pcg_dots<true>, dim3(nb), dim3(kPcgThreads), 0, s, m, z, r, q, block, part);
-  else hipLaunchKernelGGL(k_pcg_dots<false>, dim3(nb), dim3(kPcgThreads), 0, s, m, z, r, q, block, part);
-  hipLaunchKernelGGL(k_pcg_beta, dim3(1), dim3(kPcgThreads), 0, s, part, nb, block);
+  if (v2) hipLaunchKernelGGL(k_pcg_dots<true>, dim3(nb, c.k), dim3(kPcgThreads), 0, s, m, z, r, q, c);
+  else hipLaunchKernelGGL(k_pcg_dots<false>, dim3(nb, c.k), dim3(kPcgThreads), 0, s, m, z, r, q, c);
+  hipLaunchKernelGGL(k_pcg_beta, dim3(c.k), dim3(kPcgThreads), 0, s, c, nb);
 }
 
-void launch_pcg_direction(hipStream_t s, long n, const double* z, double* p, double* block) {
-  const bool v2 = pcg_vec2(n, {z, p});
+void launch_pcg_direction(hipStream_t s, long n, const double* z, double* p, const PcgCols& c) {
+  const bool v2 = pcg_vec2(n, c, {z, p});
   const long m = v2 ? n / 2 : n;
   const int nb = pcg_blocks(m);
-  if (v2) hipLaunchKernelGGL(k_pcg_direction<true>, dim3(nb), dim3(kPcgThreads), 0, s, m, z, p, block);
-  else hipLaunchKernelGGL(k_pcg_direction<false>, dim3(nb), dim3(kPcgThreads), 0, s, m, z, p, block);
+  if (v2) hipLaunchKernelGGL(k_pcg_direction<true>, dim3(nb, c.k), dim3(kPcgThreads), 0, s, m, z, p, c);
+  else hipLaunchKernelGGL(k_pcg_direction<false>, dim3(nb, c.k), dim3(kPcgThreads), 0, s, m, z, p, c);
 }
 
-void launch_pcg_curvature(hipStream_t s, long n, const double* p, const double* q, double* block) {
-  double* part = pcg_partials(block);
-  const bool v2 = pcg_vec2(n, {p, q});
+void launch_pcg_curvature(hipStream_t s, long n, const double* p, const double* q, const PcgCols& c) {
+  const bool v2 = pcg_vec2(n, c, {p, q});
   const long m = v2 ? n / 2 : n;
   const int nb = pcg_blocks(m);
-  if (v2) hipLaunchKernelGGL(k_pcg_curvature<true>, dim3(nb), dim3(kPcgThreads), 0, s, m, p, q, block, part);
-  else hipLaunchKernelGGL(k_pcg_curvature<false>, dim3(nb), dim3(kPcgThreads), 0, s, m, p, q, block, part);
-  hipLaunchKernelGGL(k_pcg_alpha, dim3(1), dim3(kPcgThreads), 0, s, part, nb, block);
+  if (v2) hipLaunchKernelGGL(k_pcg_curvature<true>, dim3(nb, c.k), dim3(kPcgThreads), 0, s, m, p, q, c);
+  else hipLaunchKernelGGL(k_pcg_curvature<false>, dim3(nb, c.k), dim3(kPcgThreads), 0, s, m, p, q, c);
+  hipLaunchKernelGGL(k_pcg_alpha, dim3(c.k), dim3(kPcgThreads), 0, s, c, nb);
 }
 
-bool launch_pcg_march(hipStream_t s, KGrid g, KOp op, const double* z, const double* p, double* p2, double* q, const double* shifts, double* block) {
+bool launch_pcg_march(hipStream_t s, KGrid g, KOp op, const double* z, const double* p, double* p2, double* q, const double* shifts, const PcgCols& c) {
   if (op.point) return false;
-  const bool aligned = (((uintptr_t)z | (uintptr_t)p | (uintptr_t)p2 | (uintptr_t)q) & 15) == 0;
+  const bool aligned = (((uintptr_t)z | (uintptr_t)p | (uintptr_t)p2 | (uintptr_t)q) & 15) == 0 && (c.k == 1 || (c.stride & 1) == 0);
   // (the levels launch_ritz_pair and the marching launch_apply take)
   if (!(g.coarsen_rows && g.nr >= 2 && g.nc >= 2 && (g.nc & 1) == 0 && aligned && ((op.five_point && op.cn != 0.0) || (op.five_diag && op.ndiag <= 2))))
     return false;
@@ -399,24 +444,22 @@ bool launch_pcg_march(hipStream_t s, KGrid g, KOp op, const double* z, const dou
   const unsigned gx = (unsigned)((g.nc / 2 + b.x - 1) / b.x);
   long rows = 32;  // row chunks as short as the partial sums allow, not shorter than an application's
   while ((long)gx * ((g.nr + rows - 1) / rows) > kPcgPartialCap) rows *= 2;
-  const dim3 grid(gx, (unsigned)((g.nr + rows - 1) / rows), 1);
+  const dim3 grid(gx, (unsigned)((g.nr + rows - 1) / rows), (unsigned)c.k);  // z: the column
   const int nblocks = (int)(grid.x * grid.y);
-  double* part = pcg_partials(block);
-  if (op.five_point) hipLaunchKernelGGL(k_pcg_march<0>, grid, b, 0, s, g, op, z, p, p2, q, shifts, (int)rows, block, part, nblocks);
-  else if (op.ndiag == 1) hipLaunchKernelGGL(k_pcg_march<1>, grid, b, 0, s, g, op, z, p, p2, q, shifts, (int)rows, block, part, nblocks);
-  else hipLaunchKernelGGL(k_pcg_march<2>, grid, b, 0, s, g, op, z, p, p2, q, shifts, (int)rows, block, part, nblocks);
-  hipLaunchKernelGGL(k_pcg_alpha, dim3(1), dim3(kPcgThreads), 0, s, part, nblocks, block);
+  if (op.five_point) hipLaunchKernelGGL(k_pcg_march<0>, grid, b, 0, s, g, op, z, p, p2, q, shifts, (int)rows, c, nblocks);
+  else if (op.ndiag == 1) hipLaunchKernelGGL(k_pcg_march<1>, grid, b, 0, s, g, op, z, p, p2, q, shifts, (int)rows, c, nblocks);
+  else hipLaunchKernelGGL(k_pcg_march<2>, grid, b, 0, s, g, op, z, p, p2, q, shifts, (int)rows, c, nblocks);
+  hipLaunchKernelGGL(k_pcg_alpha, dim3(c.k), dim3(kPcgThreads), 0, s, c, nblocks);
   return true;
 }
 
-void launch_pcg_update(hipStream_t s, long n, double* x, const double* p, double* r, const double* q, double* block) {
-  double* part = pcg_partials(block);
-  const bool v2 = pcg_vec2(n, {x, p, r, q});
+void launch_pcg_update(hipStream_t s, long n, double* x, const double* p, double* r, const double* q, const PcgCols& c) {
+  const bool v2 = pcg_vec2(n, c, {x, p, r, q});
   const long m = v2 ? n / 2 : n;
   const int nb = pcg_blocks(m);
-  if (v2) hipLaunchKernelGGL(k_pcg_update<true>, dim3(nb), dim3(kPcgThreads), 0, s, m, x, p, r, q, block, part);
-  else hipLaunchKernelGGL(k_pcg_update<false>, dim3(nb), dim3(kPcgThreads), 0, s, m, x, p, r, q, block, part);
-  hipLaunchKernelGGL(k_pcg_norm, dim3(1), dim3(kPcgThreads), 0, s, part, nb, block, pcg_history(block));
+  if (v2) hipLaunchKernelGGL(k_pcg_update<true>, dim3(nb, c.k), dim3(kPcgThreads), 0, s, m, x, p, r, q, c);
+  else hipLaunchKernelGGL(k_pcg_update<false>, dim3(nb, c.k), dim3(kPcgThreads), 0, s, m, x, p, r, q, c);
+  hipLaunchKernelGGL(k_pcg_norm, dim3(c.k), dim3(kPcgThreads), 0, s, c, nb);
 }
 
 }  // namespace mgcmt

@@ -369,8 +369,8 @@ int launch_rq3_pass2(hipStream_t s, const K3Op& A, const K3Op& Mo, int m_identit
 bool launch_rq3_gmg(hipStream_t s, const K3Op& Mo, const double* gv, double* partials, int nblocks);
 bool launch_rq3_small(hipStream_t s, const K3Op& A, const K3Op& Mo, int m_identity, double* x, double* p, double* gv, double* state, int nu, int robust);
 
-// V-cycle-preconditioned conjugate gradients (kernels_pcg.hip; the driver is pcg_host.hip).  One device block per plan:
-// kPcgStateWords state words, MGCMT_RQ_HISTORY residual norms, kPcgSums * kPcgMaxBlocks partial sums.  Every pass works on
+// V-cycle-preconditioned conjugate gradients (kernels_pcg.hip; the driver is pcg_host.hip).  One device block per plan and
+// column: kPcgStateWords state words, MGCMT_RQ_HISTORY residual norms, kPcgSums * kPcgPartialCap partial sums.  Every pass works on
 // the contiguous interior of a level vector (n doubles), so one set serves 1-D, 2-D and 3-D levels.  Every kernel but the
 // two of launch_pcg_begin reads the stop word first and returns without writing once it is set.
 enum {
@@ -394,20 +394,45 @@ enum {
 constexpr int kPcgSums = 2;
 constexpr int kPcgMaxBlocks = 2048;    // workgroups of a flat pass
 constexpr int kPcgPartialCap = 8192;   // partial sums per result the block holds (the marching pass: one per column group and row chunk)
-inline long pcg_block_doubles() { return kPcgStateWords + MGCMT_RQ_HISTORY + (long)kPcgSums * kPcgPartialCap; }
-inline double* pcg_history(double* block) { return block + kPcgStateWords; }
-inline double* pcg_partials(double* block) { return block + kPcgStateWords + MGCMT_RQ_HISTORY; }
+constexpr int kPcgMaxColumns = 16;     // systems of one batched solve (mgcmt_pcg_begin_k)
+constexpr long kPcgColPartials = (long)kPcgSums * kPcgPartialCap;  // partial sums of one column
+constexpr int kPcgHeadWords = 32;      // in front of a batched block; its first 4 bytes: the count of columns whose stop word is set
+// The k columns of a solve, as the kernels see them: column c has the state words state + c * kPcgStateWords, the history
+// history + c * MGCMT_RQ_HISTORY, the partial sums partials + c * kPcgColPartials, and its vectors are column 0's moved by
+// c * stride doubles.  stopped: the count of stopped columns, kept by the kernels that set a stop word (an atomic add each;
+// nullptr: not kept).  The single solve is k = 1 on the block [state | history | partials].  The block of a batched solve
+// with room for `cap` columns is [head | cap states | cap histories | cap x partials]: the head, the states and the
+// histories of the first columns are one contiguous copy for mgcmt_pcg_status_k.
+struct PcgCols {
+  double* state;
+  double* history;
+  double* partials;
+  unsigned* stopped;
+  long stride;
+  int k;
+};
+inline long pcg_block_doubles() { return kPcgStateWords + MGCMT_RQ_HISTORY + kPcgColPartials; }
+inline PcgCols pcg_cols_single(double* block) {
+  return PcgCols{block, block + kPcgStateWords, block + kPcgStateWords + MGCMT_RQ_HISTORY, nullptr, 0, 1};
+}
+inline long pcg_block_k_doubles(int cap) { return kPcgHeadWords + (long)cap * pcg_block_doubles(); }
+inline PcgCols pcg_cols_k(double* block, int cap, int k, long stride) {
+  double* state = block + kPcgHeadWords;
+  double* history = state + (long)cap * kPcgStateWords;
+  return PcgCols{state, history, history + (long)cap * MGCMT_RQ_HISTORY, (unsigned*)block, stride, k};
+}
+// Every launch below covers the c.k columns: the vector arguments are column 0's.
 // r <- r - q (q = (A - mu I) x0; q == nullptr: the start vector is zero, x <- 0 and r stays f), ||f|| and ||r_0|| from the same
 // pass, the state and the history cleared
-void launch_pcg_begin(hipStream_t s, long n, double* r, const double* q, double* x, double* block, double rtol, int flexible);
-void launch_pcg_dots(hipStream_t s, long n, const double* z, const double* r, const double* q, double* block);        // rho, sigma; then beta
-void launch_pcg_direction(hipStream_t s, long n, const double* z, double* p, double* block);                          // p <- z + beta p
-void launch_pcg_curvature(hipStream_t s, long n, const double* p, const double* q, double* block);                    // <p, q>; then alpha
-void launch_pcg_update(hipStream_t s, long n, double* x, const double* p, double* r, const double* q, double* block); // x, r, <r, r>; then the norm, the history, the stop word
+void launch_pcg_begin(hipStream_t s, long n, double* r, const double* q, double* x, const PcgCols& c, double rtol, int flexible);
+void launch_pcg_dots(hipStream_t s, long n, const double* z, const double* r, const double* q, const PcgCols& c);        // rho, sigma; then beta
+void launch_pcg_direction(hipStream_t s, long n, const double* z, double* p, const PcgCols& c);                          // p <- z + beta p
+void launch_pcg_curvature(hipStream_t s, long n, const double* p, const double* q, const PcgCols& c);                    // <p, q>; then alpha
+void launch_pcg_update(hipStream_t s, long n, double* x, const double* p, double* r, const double* q, const PcgCols& c); // x, r, <r, r>; then the norm, the history, the stop word
 // direction, application and curvature in ONE march on the 2-D levels launch_ritz_pair covers (a 5-point operator, with or
 // without a product potential): p2 <- z + beta p, q <- (A - mu I) p2 and <p2, q>, then alpha; p and p2 are distinct (neighbouring
 // threads read the old p).  The bits of launch_pcg_direction + launch_apply; only the order of the partial sums of <p, q> differs.
-// false: the level is not covered, nothing was launched
-bool launch_pcg_march(hipStream_t s, KGrid g, KOp op, const double* z, const double* p, double* p2, double* q, const double* shifts, double* block);
+// Column c takes shifts[c].  false: the level is not covered, nothing was launched
+bool launch_pcg_march(hipStream_t s, KGrid g, KOp op, const double* z, const double* p, double* p2, double* q, const double* shifts, const PcgCols& c);
 
 }  // namespace mgcmt

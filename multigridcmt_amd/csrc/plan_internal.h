@@ -90,6 +90,12 @@ struct mgcmt_plan {
   // (pcg_block_doubles()), the four vectors of slot W that mgcmt_pcg_begin was given (x, p, q, p2), -1 before a begin
   double* d_pcg = nullptr;
   int pcg_vecs[4] = {-1, -1, -1, -1};
+  // the batched solve (mgcmt_pcg_begin_k): its block (pcg_block_k_doubles(pcgk_cap), grown when a begin asks for more columns),
+  // the columns of the solve in progress (0: none) and the first columns of its four ranges of slot W.  The two kinds share F, V
+  // and W: a begin of one kind ends the other's solve (pcg_vecs[0] = -1 / pcgk = 0).
+  double* d_pcgk = nullptr;
+  int pcgk_cap = 0, pcgk = 0;
+  int pcgk_vecs[4] = {-1, -1, -1, -1};
   int pcg_march = -1;  // MGCMT_OPT_PCG_MARCH: 1 / 0 = the marching direction pass on / off, -1 = not set (MGCMT_PCG_MARCH, else the default)
   std::vector<double> h_shifts;
   bool has_mass = false;

@@ -359,6 +359,33 @@ class Plan:
                                           hist.size, stream))
         return it.value, st.value & 0xff, bool(st.value & _lib.PCG_INDEFINITE), fnorm.value, hist
 
+    def pcg_begin_k(self, k, vecs, rtol, zero_start=False, flexible=False, stream=None):
+        """Start k conjugate-gradient solves at once, (A - mu_c I) x_c = f_c with mu_c the plan's shift c (mgcmt_pcg_begin_k): f_c is
+        in F[0] column c and, unless zero_start, x_0 of column c in column vecs[0] + c of slot W; vecs = the first columns of four
+        ranges of k consecutive columns of W (x, p, q, p2) that do not overlap, so the plan stores at least 4 k vectors.  Nothing
+        synchronises."""
+        v = (ctypes.c_int * 4)(*[int(i) for i in vecs])
+        flags = (_lib.PCG_ZERO_START if zero_start else 0) | (_lib.PCG_FLEXIBLE if flexible else 0)
+        check(_lib.lib().mgcmt_pcg_begin_k(self._h, int(k), v, c_double(rtol), flags, stream))
+        self._pcg_k = int(k)
+
+    def pcg_iterate_k(self, iterations, nu1, nu2, kind, omega=1.0, nu_coarse=4, stream=None):
+        """Queue `iterations` iterations of the batched solve without synchronising: one k-column cycle and the passes on all
+        columns per iteration; a column that has stopped is frozen while the others go on (mgcmt_pcg_iterate_k)."""
+        check(_lib.lib().mgcmt_pcg_iterate_k(self._h, int(iterations), int(nu1), int(nu2), int(nu_coarse), kind, c_double(omega), stream))
+
+    def pcg_status_k(self, history=0, stream=None):
+        """(columns still running, iterations done[k], status[k], indefinite[k], ||f||[k], the first `history` recorded ||r_k|| of
+        every column as a (k, history) array) — the one synchronisation of a batched solve (mgcmt_pcg_status_k)."""
+        k = getattr(self, "_pcg_k", 1)           # (without a begin the library refuses the call)
+        running = c_int(0)
+        it, st = (ctypes.c_int * k)(), (ctypes.c_int * k)()
+        fnorm, hist = np.zeros(k), np.zeros((k, int(history)))
+        check(_lib.lib().mgcmt_pcg_status_k(self._h, ctypes.byref(running), it, st, as_dp(fnorm), as_dp(hist) if hist.size else None,
+                                            int(history), stream))
+        st = np.array(st[:], dtype=np.int64)
+        return running.value, np.array(it[:], dtype=np.int64), st & 0xff, (st & _lib.PCG_INDEFINITE) != 0, fnorm, hist
+
     def pcg_time_pass(self, which, reps, stream=None):
         """average milliseconds of one pass of a conjugate-gradient iteration (_lib.PCG_PASS_*) with its scalar kernel, on the
         vectors of the solve in progress, which are scratch afterwards (mgcmt_pcg_time_pass)"""

@@ -13,7 +13,7 @@ import numpy as np
 import scipy.linalg
 import scipy.sparse as sp
 
-from . import _lib
+from . import _lib, hostmem
 from ._lib import GS_LEX, GS_MC, OP_A, OP_M, SLOT_F, SLOT_T, SLOT_V, SLOT_W, SOR_LEX, WJACOBI
 from .operators import (StructuredOperator, UnrecognisedOperator, identity_operator, laplacian_operator, planes_to_csr, recognise, recognise_27_point,
                         recognise_five_point, recognise_nine_point, recognise_potential, recognise_seven_point, tag_structured)
@@ -508,6 +508,88 @@ class MGCMTSolver:
             rr = plan.dot(0, P, P)
             info["true_residual"] = math.sqrt(rr) / fnorm if fnorm > 0 else math.sqrt(rr)
         return x
+
+    def solve_matrix(self, f_matrix, A, stencil_maker, v0_matrix=None, nu1=2, nu2=2, smoother=None, shifts=None, lowest_level=2,
+                     dimension="1d", *, nu_coarse=4, rtol=1e-8, maxiter=100, check_every=4, flexible=None, info=None):
+        """``solve`` on k columns at once, one shift per column (an ADDITION; the shape of ``vcycle_matrix`` and of a
+        shift-and-invert step): column c of the result solves (A - shifts[c] I) x = f_matrix[:, c] to
+        ``||f_c - (A - shifts[c] I) x_c|| <= rtol ||f_c||``.  The columns are independent systems — no Gram-Schmidt — that share
+        every launch (mgcmt_pcg_begin_k / _iterate_k / _status_k): one k-column V-cycle per iteration, the column a grid dimension
+        of every pass.  A column that has met the tolerance is frozen while the others go on; the cycle still runs on all k
+        columns until the last one stops.  Each column carries the bits ``solve`` gives for it alone.  At most
+        ``_lib.PCG_MAX_COLUMNS`` columns.  ``shifts=None``: zeros.  ``v0_matrix=None`` (or zeros): a zero start.  The host reads
+        one status per ``check_every`` queued iterations and stops when no column is running, or at ``maxiter``.  ``info``
+        receives per-column lists: iterations, status, indefinite, residuals (one array per column) and true_residual (recomputed
+        from x_c with the column's shift).  Returns an (n, k) array as ``vcycle_matrix`` does; operators, smoothers and refusals
+        are those of ``solve``."""
+        kind, omega = self._resolve_smoother(smoother)
+        if kind is None:
+            raise NotImplementedError("solve_matrix (an addition, not a reference function) takes this class's smoothers only")
+        if dimension == "3d":
+            _check_3d_smoother(kind)
+        self._check_stencil_maker(stencil_maker, dimension)
+        maxiter, check_every = int(maxiter), int(check_every)
+        if not 0 <= maxiter <= _lib.RQ_HISTORY:
+            raise ValueError("maxiter must be in 0 .. %d (the device-side residual history)" % _lib.RQ_HISTORY)
+        if check_every < 1:
+            raise ValueError("check_every must be at least 1")
+        f_matrix = np.asarray(f_matrix, dtype=np.float64)
+        if f_matrix.ndim != 2:
+            raise ValueError("f_matrix must be an (n, k) array, one right-hand side per column")
+        n, k = f_matrix.shape
+        shifts = np.zeros(k) if shifts is None else np.asarray(shifts, dtype=np.float64).reshape(-1)
+        if len(shifts) != k:
+            raise ValueError("dimension mismatch: %d shifts for %d columns" % (len(shifts), k))
+        if not 1 <= k <= _lib.PCG_MAX_COLUMNS:
+            raise ValueError("between 1 and %d columns per call" % _lib.PCG_MAX_COLUMNS)
+        g = self._grid(n, dimension)
+        if not self._check_grid(g, lowest_level):
+            return None
+        op = _recognise_entry(A, dimension)
+        _check_point_smoother(op, kind)
+        plan = get_plan(op, int(lowest_level), nvec=4 * k)
+        plan.set_shifts(shifts)
+        X, P, Q, P2 = 0, k, 2 * k, 3 * k            # first columns of the four ranges of slot W
+        zero_start = v0_matrix is None or _all_zero(np.asarray(v0_matrix))
+        if not zero_start:
+            v0_matrix = np.asarray(v0_matrix, dtype=np.float64)
+            if v0_matrix.shape != (n, k):
+                raise ValueError("dimension mismatch: start vectors %s for right-hand sides %s" % (v0_matrix.shape, (n, k)))
+        for c in range(k):
+            if not zero_start:
+                plan.upload(0, SLOT_W, X + c, v0_matrix[:, c])
+            plan.upload(0, SLOT_F, c, f_matrix[:, c])
+        if flexible is None:
+            flexible = kind != WJACOBI
+        plan.pcg_begin_k(k, [X, P, Q, P2], float(rtol), zero_start=zero_start, flexible=bool(flexible))
+        queued, running = 0, k
+        while running > 0 and queued < maxiter:
+            chunk = min(check_every, maxiter - queued)
+            plan.pcg_iterate_k(chunk, int(nu1), int(nu2), kind, omega=omega, nu_coarse=int(nu_coarse))
+            queued += chunk
+            running = plan.pcg_status_k()[0]
+        # columns are downloaded as contiguous rows of a (k, n) array — one block of recycled page-locked memory where that
+        # pays: every row is one DMA —; the (n, k) result is its transpose, as in vcycle_matrix
+        rows = hostmem.empty(k * n).reshape(k, n)
+        for c in range(k):
+            plan.download_into(0, SLOT_W, X + c, rows[c])
+        if isinstance(info, dict):
+            _, done, status, indefinite, fnorm, hist = plan.pcg_status_k(history=maxiter)
+            names = {_lib.PCG_CONVERGED: "converged", _lib.PCG_BREAKDOWN: "breakdown"}
+            info["iterations"] = [int(d) for d in done]
+            info["status"] = [names.get(int(s), "maxiter") for s in status]
+            info["indefinite"] = [bool(b) for b in indefinite]
+            info["residuals"] = [hist[c, :done[c]] / fnorm[c] if fnorm[c] > 0 else hist[c, :done[c]].copy() for c in range(k)]
+            # the residuals recomputed from x: f again (r has replaced it on the device), per column one application with the
+            # column's shift (x_c is column c of W: mgcmt_apply takes the shift of the source column) and one inner product
+            info["true_residual"] = []
+            for c in range(k):
+                plan.upload(0, SLOT_W, P + c, f_matrix[:, c])
+                plan.apply(0, (SLOT_W, X + c), (SLOT_W, Q + c), with_shift=True)
+                plan.axpy(0, -1.0, (SLOT_W, Q + c), (SLOT_W, P + c))
+                rr = plan.dot(0, (SLOT_W, P + c), (SLOT_W, P + c))
+                info["true_residual"].append(math.sqrt(rr) / fnorm[c] if fnorm[c] > 0 else math.sqrt(rr))
+        return rows.T
 
     def twogrid(self, v0, f, A, stencil_maker, nu1=4, nu2=4, smoother=None, shift=0, dimension="1d"):
         """MGCMTSolver.py:331-371 — pre-smooth, exact solve of (R A P - shift I) on the next grid,

@@ -396,6 +396,7 @@ int mgcmt_vcycle_rqmg(mgcmt_plan* plan, int slot, const int* vecs, int nu1, int 
  *   mgcmt_pcg_status: the only synchronising call.  iterations_done: iterations completed since the begin; status:
  *     MGCMT_PCG_RUNNING, _CONVERGED or _BREAKDOWN, plus MGCMT_PCG_INDEFINITE; fnorm: ||f||; history[k] = ||r_{k+1}|| for
  *     k < min(capacity, MGCMT_RQ_HISTORY).  Any output may be NULL.
+ * The three entries are mgcmt_pcg_*_k below with k = 1, on the same device state, with scalar outputs.
  * MGCMT_ERR_UNSUPPORTED on a sharded plan, MGCMT_ERR_INVALID on a plan with fewer than 4 vectors or vecs that are not distinct.
  * The general sparse plans (mgcmt_csr_*) have no such entry. */
 #define MGCMT_PCG_ZERO_START 1
@@ -415,7 +416,7 @@ int mgcmt_pcg_status(mgcmt_plan* plan, int* iterations_done, int* status, double
  * within the plan's vectors: nvec >= 4 k (k = 16: nvec = 64 <= MGCMT_MAX_STORE_VEC).  One rtol and one beta form for all columns.
  *   mgcmt_pcg_begin_k: as mgcmt_pcg_begin, per column.  A column whose f is zero, or whose start vector already meets the
  *     tolerance, sets its own stop word here.  The state (k blocks of scalars, k histories, k sets of partial sums) is one device
- *     allocation, made by the first batched begin and grown when a later one has more columns.
+ *     allocation per plan, made by the first begin of either kind and grown when a later one has more columns.
  *   mgcmt_pcg_iterate_k: queues `iterations` iterations without synchronising.  One iteration: ONE mgcmt_vcycle on k columns
  *     (zero start, no Gram-Schmidt), then the passes and scalar kernels of mgcmt_pcg_iterate with k times the workgroups, the
  *     marching direction pass where mgcmt_pcg_iterate takes it (same gate, same option).  Columns freeze independently: once a
@@ -429,8 +430,8 @@ int mgcmt_pcg_status(mgcmt_plan* plan, int* iterations_done, int* status, double
  *   mgcmt_pcg_status_k: one copy, one synchronisation.  running: the number of columns without a stop word (kept on the device
  *     as a count of stopped columns, so the host reads one word to decide whether to queue more); iterations_done[k], status[k],
  *     fnorm[k] as in mgcmt_pcg_status, per column; history: k rows of `capacity` numbers.  Any output may be NULL.
- * A batched begin ends a single solve on the same plan and the reverse (they share F, V and W): the other kind's iterate /
- * status then returns MGCMT_ERR_INVALID, as before any begin.  MGCMT_ERR_UNSUPPORTED on a sharded plan; MGCMT_ERR_INVALID for k
+ * A batched begin ends a single solve on the same plan and the reverse (they share F, V, W and the state): the other kind's
+ * iterate / status then returns MGCMT_ERR_INVALID, as before any begin — after mgcmt_pcg_begin_k with k = 1 as well.  MGCMT_ERR_UNSUPPORTED on a sharded plan; MGCMT_ERR_INVALID for k
  * out of range and for column ranges that overlap or leave the plan's vectors.  mgcmt_pcg_time_pass after a batched begin times
  * the pass on the k columns. */
 #define MGCMT_PCG_MAX_COLUMNS 16

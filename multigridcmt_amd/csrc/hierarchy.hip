@@ -786,8 +786,7 @@ int mgcmt_plan_destroy(mgcmt_plan* p) {
   if (p->d_rqstate) (void)hipFree(p->d_rqstate);
   if (p->d_rqhistory) (void)hipFree(p->d_rqhistory);
   if (p->d_mgs) (void)hipFree(p->d_mgs);
-  if (p->d_pcg) (void)hipFree(p->d_pcg);
-  if (p->d_pcgk) (void)hipFree(p->d_pcgk);
+  if (p->d_pcg_block) (void)hipFree(p->d_pcg_block);
   if (p->tailmat.mt) (void)hipFree(p->tailmat.mt);
   if (p->lex_carry) (void)hipFree(p->lex_carry);
   if (p->lex_sync) (void)hipFree(p->lex_sync);

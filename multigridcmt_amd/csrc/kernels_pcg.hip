@@ -80,7 +80,7 @@ __device__ __forceinline__ void pcg_totals(const double* __restrict__ partials, 
 __device__ __forceinline__ void pcg_stop(double* __restrict__ state, unsigned* stopped, double status) {
   state[kPcgStop] = 1.0;
   state[kPcgStatus] = status;
-  if (stopped) atomicAdd(stopped, 1u);
+  atomicAdd(stopped, 1u);
 }
 __device__ __forceinline__ void pcg_break(double* __restrict__ state, unsigned* stopped) { pcg_stop(state, stopped, 2.0); }
 

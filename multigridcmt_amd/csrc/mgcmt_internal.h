@@ -369,8 +369,8 @@ int launch_rq3_pass2(hipStream_t s, const K3Op& A, const K3Op& Mo, int m_identit
 bool launch_rq3_gmg(hipStream_t s, const K3Op& Mo, const double* gv, double* partials, int nblocks);
 bool launch_rq3_small(hipStream_t s, const K3Op& A, const K3Op& Mo, int m_identity, double* x, double* p, double* gv, double* state, int nu, int robust);
 
-// V-cycle-preconditioned conjugate gradients (kernels_pcg.hip; the driver is pcg_host.hip).  One device block per plan and
-// column: kPcgStateWords state words, MGCMT_RQ_HISTORY residual norms, kPcgSums * kPcgPartialCap partial sums.  Every pass works on
+// V-cycle-preconditioned conjugate gradients (kernels_pcg.hip; the driver is pcg_host.hip).  One device block per plan; per
+// column it holds kPcgStateWords state words, MGCMT_RQ_HISTORY residual norms, kPcgSums * kPcgPartialCap partial sums.  Every pass works on
 // the contiguous interior of a level vector (n doubles), so one set serves 1-D, 2-D and 3-D levels.  Every kernel but the
 // two of launch_pcg_begin reads the stop word first and returns without writing once it is set.
 enum {
@@ -396,13 +396,13 @@ constexpr int kPcgMaxBlocks = 2048;    // workgroups of a flat pass
 constexpr int kPcgPartialCap = 8192;   // partial sums per result the block holds (the marching pass: one per column group and row chunk)
 constexpr int kPcgMaxColumns = 16;     // systems of one batched solve (mgcmt_pcg_begin_k)
 constexpr long kPcgColPartials = (long)kPcgSums * kPcgPartialCap;  // partial sums of one column
-constexpr int kPcgHeadWords = 32;      // in front of a batched block; its first 4 bytes: the count of columns whose stop word is set
+constexpr int kPcgHeadWords = 32;      // in front of the block; its first 4 bytes: the count of columns whose stop word is set
 // The k columns of a solve, as the kernels see them: column c has the state words state + c * kPcgStateWords, the history
 // history + c * MGCMT_RQ_HISTORY, the partial sums partials + c * kPcgColPartials, and its vectors are column 0's moved by
-// c * stride doubles.  stopped: the count of stopped columns, kept by the kernels that set a stop word (an atomic add each;
-// nullptr: not kept).  The single solve is k = 1 on the block [state | history | partials].  The block of a batched solve
-// with room for `cap` columns is [head | cap states | cap histories | cap x partials]: the head, the states and the
-// histories of the first columns are one contiguous copy for mgcmt_pcg_status_k.
+// c * stride doubles.  stopped: the count of stopped columns, kept by the kernels that set a stop word (an atomic add each).
+// The plan's one block, with room for `cap` columns, is [head | cap states | cap histories | cap x partials]: the head, the
+// states and the histories of the first columns are one contiguous copy for the status calls.  The single solve is k = 1 on
+// the same block, whatever its capacity.
 struct PcgCols {
   double* state;
   double* history;
@@ -411,12 +411,9 @@ struct PcgCols {
   long stride;
   int k;
 };
-inline long pcg_block_doubles() { return kPcgStateWords + MGCMT_RQ_HISTORY + kPcgColPartials; }
-inline PcgCols pcg_cols_single(double* block) {
-  return PcgCols{block, block + kPcgStateWords, block + kPcgStateWords + MGCMT_RQ_HISTORY, nullptr, 0, 1};
-}
-inline long pcg_block_k_doubles(int cap) { return kPcgHeadWords + (long)cap * pcg_block_doubles(); }
-inline PcgCols pcg_cols_k(double* block, int cap, int k, long stride) {
+inline long pcg_column_doubles() { return kPcgStateWords + MGCMT_RQ_HISTORY + kPcgColPartials; }
+inline long pcg_block_doubles(int cap) { return kPcgHeadWords + (long)cap * pcg_column_doubles(); }
+inline PcgCols pcg_cols(double* block, int cap, int k, long stride) {
   double* state = block + kPcgHeadWords;
   double* history = state + (long)cap * kPcgStateWords;
   return PcgCols{state, history, history + (long)cap * MGCMT_RQ_HISTORY, (unsigned*)block, stride, k};

@@ -86,16 +86,15 @@ struct mgcmt_plan {
   bool use_mgs_block = true;
   long mgs_block_min = 0;  // points per column from which a single plan takes the blocked form (0: wherever the one-workgroup kernel does not apply)
   double* d_rqhistory = nullptr;  // Rayleigh quotients recorded by mgcmt_rq_line_step (MGCMT_RQ_HISTORY numbers)
-  // preconditioned conjugate gradients (pcg_host.hip): state words, residual history and partial sums in one block
-  // (pcg_block_doubles()), the four vectors of slot W that mgcmt_pcg_begin was given (x, p, q, p2), -1 before a begin
-  double* d_pcg = nullptr;
-  int pcg_vecs[4] = {-1, -1, -1, -1};
-  // the batched solve (mgcmt_pcg_begin_k): its block (pcg_block_k_doubles(pcgk_cap), grown when a begin asks for more columns),
-  // the columns of the solve in progress (0: none) and the first columns of its four ranges of slot W.  The two kinds share F, V
-  // and W: a begin of one kind ends the other's solve (pcg_vecs[0] = -1 / pcgk = 0).
-  double* d_pcgk = nullptr;
-  int pcgk_cap = 0, pcgk = 0;
-  int pcgk_vecs[4] = {-1, -1, -1, -1};
+  // preconditioned conjugate gradients (pcg_host.hip): the head, the state words, the residual histories and the partial sums
+  // of pcg_cap columns in one block (pcg_block_doubles(pcg_cap), grown when a begin asks for more columns); the solve in
+  // progress: which entry began it (mgcmt_pcg_begin or mgcmt_pcg_begin_k: the other kind's iterate / status refuse it), its
+  // columns and the first columns of its four ranges of slot W (x, p, q, p2)
+  enum PcgKind { kPcgNone, kPcgSingle, kPcgBatched };
+  double* d_pcg_block = nullptr;
+  int pcg_cap = 0, pcg_k = 0;
+  PcgKind pcg_kind = kPcgNone;
+  int pcg_w[4] = {-1, -1, -1, -1};
   int pcg_march = -1;  // MGCMT_OPT_PCG_MARCH: 1 / 0 = the marching direction pass on / off, -1 = not set (MGCMT_PCG_MARCH, else the default)
   std::vector<double> h_shifts;
   bool has_mass = false;

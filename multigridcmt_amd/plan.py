@@ -337,13 +337,17 @@ class Plan:
         check(_lib.lib().mgcmt_rq_history(self._h, int(first), int(count), _lib.as_dp(out), stream))
         return out
 
+    @staticmethod
+    def _pcg_begin_args(vecs, rtol, zero_start, flexible):
+        """the vector list, the tolerance and the flags as both begins take them"""
+        flags = (_lib.PCG_ZERO_START if zero_start else 0) | (_lib.PCG_FLEXIBLE if flexible else 0)
+        return (ctypes.c_int * 4)(*[int(i) for i in vecs]), c_double(rtol), flags
+
     def pcg_begin(self, vecs, rtol, zero_start=False, flexible=False, stream=None):
         """Start a V-cycle-preconditioned conjugate-gradient solve of (A - mu I) x = f on level 0 (mgcmt_pcg_begin): f is in
         F[0] column 0 and, unless zero_start, x_0 in column vecs[0] of slot W; vecs = four distinct columns of W (x, p, q, p2).
         mu is the plan's shift 0.  Nothing synchronises."""
-        v = (ctypes.c_int * 4)(*[int(i) for i in vecs])
-        flags = (_lib.PCG_ZERO_START if zero_start else 0) | (_lib.PCG_FLEXIBLE if flexible else 0)
-        check(_lib.lib().mgcmt_pcg_begin(self._h, v, c_double(rtol), flags, stream))
+        check(_lib.lib().mgcmt_pcg_begin(self._h, *self._pcg_begin_args(vecs, rtol, zero_start, flexible), stream))
 
     def pcg_iterate(self, iterations, nu1, nu2, kind, omega=1.0, nu_coarse=4, stream=None):
         """Queue `iterations` iterations (one cycle, one operator application and four fused passes each) without
@@ -364,9 +368,7 @@ class Plan:
         in F[0] column c and, unless zero_start, x_0 of column c in column vecs[0] + c of slot W; vecs = the first columns of four
         ranges of k consecutive columns of W (x, p, q, p2) that do not overlap, so the plan stores at least 4 k vectors.  Nothing
         synchronises."""
-        v = (ctypes.c_int * 4)(*[int(i) for i in vecs])
-        flags = (_lib.PCG_ZERO_START if zero_start else 0) | (_lib.PCG_FLEXIBLE if flexible else 0)
-        check(_lib.lib().mgcmt_pcg_begin_k(self._h, int(k), v, c_double(rtol), flags, stream))
+        check(_lib.lib().mgcmt_pcg_begin_k(self._h, int(k), *self._pcg_begin_args(vecs, rtol, zero_start, flexible), stream))
         self._pcg_k = int(k)
 
     def pcg_iterate_k(self, iterations, nu1, nu2, kind, omega=1.0, nu_coarse=4, stream=None):

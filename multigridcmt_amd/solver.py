@@ -440,7 +440,71 @@ class MGCMTSolver:
                 plan.vcycle(int(nu1), int(nu2), kind, omega=omega, k=1, nu_coarse=int(nu_coarse), level=l)
         return plan.download(0, SLOT_V, 0)
 
-    _PCG_X, _PCG_P, _PCG_Q, _PCG_P2 = range(4)      # columns of slot W: the iterate, the direction, (A - shift I) p, a spare
+    def _pcg_solve(self, name, fs, starts, shifts, A, stencil_maker, nu1, nu2, smoother, lowest_level, dimension, nu_coarse, rtol, maxiter,
+                   check_every, flexible, info, single):
+        """What ``solve`` and ``solve_matrix`` share: k = len(fs) systems, column c with the right-hand side fs[c], the start vector
+        starts[c] (starts None: a zero start) and shifts[c], solved on a plan of 4 k vectors whose slot W holds four ranges of k
+        columns — the iterates (from column 0), the directions (from k), (A - shift I) p (from 2 k), a spare (from 3 k).
+        ``single``: through the single-column entries of the library (k = 1).  ``info`` (a dict or None) receives per-column
+        lists.  Returns the plan, the iterates in columns 0 .. k - 1 of slot W, or None where the grid is refused."""
+        kind, omega = self._resolve_smoother(smoother)
+        if kind is None:
+            raise NotImplementedError("%s (an addition, not a reference function) takes this class's smoothers only" % name)
+        if dimension == "3d":
+            _check_3d_smoother(kind)
+        self._check_stencil_maker(stencil_maker, dimension)
+        maxiter, check_every = int(maxiter), int(check_every)
+        if not 0 <= maxiter <= _lib.RQ_HISTORY:
+            raise ValueError("maxiter must be in 0 .. %d (the device-side residual history)" % _lib.RQ_HISTORY)
+        if check_every < 1:
+            raise ValueError("check_every must be at least 1")
+        k = len(fs)
+        g = self._grid(len(fs[0]), dimension)
+        if not self._check_grid(g, lowest_level):
+            return None
+        op = _recognise_entry(A, dimension)            # (a 1-D matrix only the general sparse path handles raises UnrecognisedOperator)
+        _check_point_smoother(op, kind)
+        plan = get_plan(op, int(lowest_level), nvec=4 * k)
+        plan.set_shifts(shifts)
+        X, P, Q, P2 = 0, k, 2 * k, 3 * k            # first columns of the four ranges of slot W
+        for c in range(k):
+            if starts is not None:
+                plan.upload(0, SLOT_W, X + c, starts[c])
+            plan.upload(0, SLOT_F, c, fs[c])
+        if flexible is None:
+            flexible = kind != WJACOBI
+        if single:
+            begin, iterate = plan.pcg_begin, plan.pcg_iterate
+
+            def status(history=0):                  # (the single entries' scalars as one column)
+                done, state, indefinite, fnorm, hist = plan.pcg_status(history=history)
+                return int(state == _lib.PCG_RUNNING), [done], [state], [indefinite], [fnorm], hist[None, :]
+        else:
+            begin, iterate, status = functools.partial(plan.pcg_begin_k, k), plan.pcg_iterate_k, plan.pcg_status_k
+        begin([X, P, Q, P2], float(rtol), zero_start=starts is None, flexible=bool(flexible))
+        queued, running = 0, k
+        while running > 0 and queued < maxiter:
+            chunk = min(check_every, maxiter - queued)
+            iterate(chunk, int(nu1), int(nu2), kind, omega=omega, nu_coarse=int(nu_coarse))
+            queued += chunk
+            running = status()[0]
+        if info is not None:
+            _, done, state, indefinite, fnorm, hist = status(history=maxiter)
+            names = {_lib.PCG_CONVERGED: "converged", _lib.PCG_BREAKDOWN: "breakdown"}
+            info["iterations"] = [int(d) for d in done]
+            info["status"] = [names.get(int(s), "maxiter") for s in state]
+            info["indefinite"] = [bool(b) for b in indefinite]
+            info["residuals"] = [hist[c, :done[c]] / fnorm[c] if fnorm[c] > 0 else hist[c, :done[c]].copy() for c in range(k)]
+            # the residuals recomputed from x: f again (r has replaced it on the device), per column one application with the
+            # column's shift (x_c is column c of W: mgcmt_apply takes the shift of the source column) and one inner product
+            info["true_residual"] = []
+            for c in range(k):
+                plan.upload(0, SLOT_W, P + c, fs[c])
+                plan.apply(0, (SLOT_W, X + c), (SLOT_W, Q + c), with_shift=True)
+                plan.axpy(0, -1.0, (SLOT_W, Q + c), (SLOT_W, P + c))
+                rr = plan.dot(0, (SLOT_W, P + c), (SLOT_W, P + c))
+                info["true_residual"].append(math.sqrt(rr) / fnorm[c] if fnorm[c] > 0 else math.sqrt(rr))
+        return plan
 
     def solve(self, f, A, stencil_maker, v0=None, nu1=2, nu2=2, smoother=None, shift=0, lowest_level=2, dimension="1d", *,
               nu_coarse=4, rtol=1e-8, maxiter=100, check_every=4, flexible=None, info=None):
@@ -456,58 +520,22 @@ class MGCMTSolver:
         ``info`` (a dict) receives iterations, status ("converged", "maxiter", "breakdown"), indefinite (a negative <z, r> or
         <p, A p> was met), residuals (the recorded ||r_k|| / ||f||, k = 1 ..) and true_residual (||f - (A - shift I) x|| / ||f||
         recomputed from x).  Returns x, 1-D; bad sizes print and return None as in ``vcycle``."""
-        kind, omega = self._resolve_smoother(smoother)
-        if kind is None:
-            raise NotImplementedError("solve (an addition, not a reference function) takes this class's smoothers only")
-        if dimension == "3d":
-            _check_3d_smoother(kind)
-        self._check_stencil_maker(stencil_maker, dimension)
-        maxiter, check_every = int(maxiter), int(check_every)
-        if not 0 <= maxiter <= _lib.RQ_HISTORY:
-            raise ValueError("maxiter must be in 0 .. %d (the device-side residual history)" % _lib.RQ_HISTORY)
-        if check_every < 1:
-            raise ValueError("check_every must be at least 1")
         f = np.asarray(f, dtype=np.float64).reshape(-1)
-        n = len(f)
-        g = self._grid(n, dimension)
-        if not self._check_grid(g, lowest_level):
-            return None
-        op = _recognise_entry(A, dimension)            # (a 1-D matrix only the general sparse path handles raises UnrecognisedOperator)
-        _check_point_smoother(op, kind)
-        plan = get_plan(op, int(lowest_level), nvec=4)
-        plan.set_shifts([float(shift)])
-        X = (SLOT_W, self._PCG_X)
-        zero_start = v0 is None or _all_zero(np.asarray(v0))
-        if not zero_start:
+        if v0 is not None and not _all_zero(np.asarray(v0)):
             v0 = np.asarray(v0, dtype=np.float64).reshape(-1)
-            if len(v0) != n:
-                raise ValueError("dimension mismatch: a start vector of %d for a right-hand side of %d" % (len(v0), n))
-            plan.upload(0, X[0], X[1], v0)
-        plan.upload(0, SLOT_F, 0, f)
-        if flexible is None:
-            flexible = kind != WJACOBI
-        plan.pcg_begin([self._PCG_X, self._PCG_P, self._PCG_Q, self._PCG_P2], float(rtol), zero_start=zero_start, flexible=bool(flexible))
-        queued, status = 0, _lib.PCG_RUNNING
-        while status == _lib.PCG_RUNNING and queued < maxiter:
-            chunk = min(check_every, maxiter - queued)
-            plan.pcg_iterate(chunk, int(nu1), int(nu2), kind, omega=omega, nu_coarse=int(nu_coarse))
-            queued += chunk
-            status = plan.pcg_status()[1]
-        x = plan.download(0, X[0], X[1])
-        if isinstance(info, dict):
-            done, status, indefinite, fnorm, hist = plan.pcg_status(history=maxiter)
-            info["iterations"] = done
-            info["status"] = {_lib.PCG_CONVERGED: "converged", _lib.PCG_BREAKDOWN: "breakdown"}.get(status, "maxiter")
-            info["indefinite"] = indefinite
-            info["residuals"] = hist[:done] / fnorm if fnorm > 0 else hist[:done]
-            # the residual recomputed from x: f again (r has replaced it on the device), one application, one inner product
-            P, Q = (SLOT_W, self._PCG_P), (SLOT_W, self._PCG_Q)
-            plan.upload(0, P[0], P[1], f)
-            plan.apply(0, X, Q, with_shift=True)       # (column 0: the shift of column 0)
-            plan.axpy(0, -1.0, Q, P)
-            rr = plan.dot(0, P, P)
-            info["true_residual"] = math.sqrt(rr) / fnorm if fnorm > 0 else math.sqrt(rr)
-        return x
+            if len(v0) != len(f):
+                raise ValueError("dimension mismatch: a start vector of %d for a right-hand side of %d" % (len(v0), len(f)))
+            starts = [v0]
+        else:
+            starts = None
+        columns = {} if isinstance(info, dict) else None
+        plan = self._pcg_solve("solve", [f], starts, [float(shift)], A, stencil_maker, nu1, nu2, smoother, lowest_level, dimension, nu_coarse,
+                               rtol, maxiter, check_every, flexible, columns, single=True)
+        if plan is None:
+            return None
+        if columns is not None:
+            info.update({key: values[0] for key, values in columns.items()})
+        return plan.download(0, SLOT_W, 0)
 
     def solve_matrix(self, f_matrix, A, stencil_maker, v0_matrix=None, nu1=2, nu2=2, smoother=None, shifts=None, lowest_level=2,
                      dimension="1d", *, nu_coarse=4, rtol=1e-8, maxiter=100, check_every=4, flexible=None, info=None):
@@ -522,17 +550,6 @@ class MGCMTSolver:
         receives per-column lists: iterations, status, indefinite, residuals (one array per column) and true_residual (recomputed
         from x_c with the column's shift).  Returns an (n, k) array as ``vcycle_matrix`` does; operators, smoothers and refusals
         are those of ``solve``."""
-        kind, omega = self._resolve_smoother(smoother)
-        if kind is None:
-            raise NotImplementedError("solve_matrix (an addition, not a reference function) takes this class's smoothers only")
-        if dimension == "3d":
-            _check_3d_smoother(kind)
-        self._check_stencil_maker(stencil_maker, dimension)
-        maxiter, check_every = int(maxiter), int(check_every)
-        if not 0 <= maxiter <= _lib.RQ_HISTORY:
-            raise ValueError("maxiter must be in 0 .. %d (the device-side residual history)" % _lib.RQ_HISTORY)
-        if check_every < 1:
-            raise ValueError("check_every must be at least 1")
         f_matrix = np.asarray(f_matrix, dtype=np.float64)
         if f_matrix.ndim != 2:
             raise ValueError("f_matrix must be an (n, k) array, one right-hand side per column")
@@ -542,53 +559,22 @@ class MGCMTSolver:
             raise ValueError("dimension mismatch: %d shifts for %d columns" % (len(shifts), k))
         if not 1 <= k <= _lib.PCG_MAX_COLUMNS:
             raise ValueError("between 1 and %d columns per call" % _lib.PCG_MAX_COLUMNS)
-        g = self._grid(n, dimension)
-        if not self._check_grid(g, lowest_level):
-            return None
-        op = _recognise_entry(A, dimension)
-        _check_point_smoother(op, kind)
-        plan = get_plan(op, int(lowest_level), nvec=4 * k)
-        plan.set_shifts(shifts)
-        X, P, Q, P2 = 0, k, 2 * k, 3 * k            # first columns of the four ranges of slot W
-        zero_start = v0_matrix is None or _all_zero(np.asarray(v0_matrix))
-        if not zero_start:
+        starts = None
+        if v0_matrix is not None and not _all_zero(np.asarray(v0_matrix)):
             v0_matrix = np.asarray(v0_matrix, dtype=np.float64)
             if v0_matrix.shape != (n, k):
                 raise ValueError("dimension mismatch: start vectors %s for right-hand sides %s" % (v0_matrix.shape, (n, k)))
-        for c in range(k):
-            if not zero_start:
-                plan.upload(0, SLOT_W, X + c, v0_matrix[:, c])
-            plan.upload(0, SLOT_F, c, f_matrix[:, c])
-        if flexible is None:
-            flexible = kind != WJACOBI
-        plan.pcg_begin_k(k, [X, P, Q, P2], float(rtol), zero_start=zero_start, flexible=bool(flexible))
-        queued, running = 0, k
-        while running > 0 and queued < maxiter:
-            chunk = min(check_every, maxiter - queued)
-            plan.pcg_iterate_k(chunk, int(nu1), int(nu2), kind, omega=omega, nu_coarse=int(nu_coarse))
-            queued += chunk
-            running = plan.pcg_status_k()[0]
+            starts = [v0_matrix[:, c] for c in range(k)]
+        plan = self._pcg_solve("solve_matrix", [f_matrix[:, c] for c in range(k)], starts, shifts, A, stencil_maker, nu1, nu2, smoother,
+                               lowest_level, dimension, nu_coarse, rtol, maxiter, check_every, flexible, info if isinstance(info, dict) else None,
+                               single=False)
+        if plan is None:
+            return None
         # columns are downloaded as contiguous rows of a (k, n) array — one block of recycled page-locked memory where that
         # pays: every row is one DMA —; the (n, k) result is its transpose, as in vcycle_matrix
         rows = hostmem.empty(k * n).reshape(k, n)
         for c in range(k):
-            plan.download_into(0, SLOT_W, X + c, rows[c])
-        if isinstance(info, dict):
-            _, done, status, indefinite, fnorm, hist = plan.pcg_status_k(history=maxiter)
-            names = {_lib.PCG_CONVERGED: "converged", _lib.PCG_BREAKDOWN: "breakdown"}
-            info["iterations"] = [int(d) for d in done]
-            info["status"] = [names.get(int(s), "maxiter") for s in status]
-            info["indefinite"] = [bool(b) for b in indefinite]
-            info["residuals"] = [hist[c, :done[c]] / fnorm[c] if fnorm[c] > 0 else hist[c, :done[c]].copy() for c in range(k)]
-            # the residuals recomputed from x: f again (r has replaced it on the device), per column one application with the
-            # column's shift (x_c is column c of W: mgcmt_apply takes the shift of the source column) and one inner product
-            info["true_residual"] = []
-            for c in range(k):
-                plan.upload(0, SLOT_W, P + c, f_matrix[:, c])
-                plan.apply(0, (SLOT_W, X + c), (SLOT_W, Q + c), with_shift=True)
-                plan.axpy(0, -1.0, (SLOT_W, Q + c), (SLOT_W, P + c))
-                rr = plan.dot(0, (SLOT_W, P + c), (SLOT_W, P + c))
-                info["true_residual"].append(math.sqrt(rr) / fnorm[c] if fnorm[c] > 0 else math.sqrt(rr))
+            plan.download_into(0, SLOT_W, c, rows[c])
         return rows.T
 
     def twogrid(self, v0, f, A, stencil_maker, nu1=4, nu2=4, smoother=None, shift=0, dimension="1d"):

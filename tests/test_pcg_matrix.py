@@ -290,6 +290,61 @@ def test_refusals(backend):
     p.close()
 
 
+# ---- 6a. one block, one driver: a solve of one kind on the block a solve of the other kind left -------------------------------
+
+@pytest.mark.parametrize("opname,g,shifts,march", [("lap", 32, (1.9, 0.0, 3.0), 0), ("well", 64, (0.0, 1.9, 3.0), 1)])
+def test_single_and_batched_solves_share_one_block(backend, opname, g, shifts, march):
+    """The single solve is the batched one with k = 1 on the plan's one block.  A single solve on a block that holds three columns,
+    after a batched solve has used it, on four distinct unsorted columns of W: the bits of the same solve on a fresh plan, whose
+    block holds one column.  Then the reverse: a batched solve after that single one, against the same batched solve on a fresh
+    plan.  64^2 with the marching pass: two row chunks, and the p / p2 roles exchange on the one shared vector list."""
+    n, k = g * g, 3
+    op = MARCH_OPS[opname](g)
+    F = np.random.RandomState(1).rand(n, k)
+    wj = dict(kind=_lib.WJACOBI, omega=2.0 / 3.0)
+
+    def single(p, vecs):
+        p.pcg_begin(vecs, RTOL, zero_start=True, flexible=False)
+        p.pcg_iterate(3, 2, 2, **wj)
+        p.pcg_iterate(20, 2, 2, **wj)                       # converges on the way: the rest returns early
+        return p.pcg_status(history=32), _w(p, vecs[0])
+
+    def batched(p):
+        for c in range(k):
+            p.upload(0, _lib.SLOT_F, c, F[:, c])
+        p.pcg_begin_k(k, [0, 3, 6, 9], RTOL, zero_start=True, flexible=False)
+        p.pcg_iterate_k(40, 2, 2, **wj)
+        return p.pcg_status_k(history=48), [_w(p, c) for c in range(k)]
+
+    a = _plan_k(op, n, 1, shifts, F, nvec=12, march=march)
+    (it_a, st_a, ind_a, fnorm_a, hist_a), x_a = single(a, [0, 1, 2, 3])
+    assert st_a == _lib.PCG_CONVERGED and 3 < it_a < 23 and np.any(x_a)
+
+    b = _plan_k(op, n, k, shifts, F, nvec=12, march=march)
+    b.pcg_begin_k(k, [0, 3, 6, 9], RTOL, zero_start=True, flexible=False)
+    b.pcg_iterate_k(2, 2, 2, **wj)
+    b.upload(0, _lib.SLOT_F, 0, F[:, 0])
+    (it_b, st_b, ind_b, fnorm_b, hist_b), x_b = single(b, [5, 1, 7, 2])
+    print("%s %d^2: single solve, fresh plan %d iterations, after a batched solve %d; max |dx| %.3e" % (opname, g, it_a, it_b, np.max(np.abs(x_a - x_b))))
+    assert (it_b, st_b, ind_b) == (it_a, st_a, ind_a) and fnorm_b == fnorm_a
+    assert np.array_equal(hist_b, hist_a) and np.array_equal(x_b, x_a)
+    for call in (lambda: b.pcg_iterate_k(1, 2, 2, **wj), lambda: b.pcg_status_k()):
+        with pytest.raises(MgcmtError, match="mgcmt error -1"):
+            call()
+
+    (run_b, done_b, status_b, _, fnorm_kb, hist_kb), xs_b = batched(b)
+    c = _plan_k(op, n, k, shifts, F, nvec=12, march=march)
+    (run_c, done_c, status_c, _, fnorm_kc, hist_kc), xs_c = batched(c)
+    print("%s %d^2: batched solve, fresh plan %s iterations, after a single solve %s" % (opname, g, done_c.tolist(), done_b.tolist()))
+    assert run_c == 0 and list(status_c) == [_lib.PCG_CONVERGED] * k
+    assert run_b == run_c and np.array_equal(done_b, done_c) and np.array_equal(status_b, status_c) and np.array_equal(fnorm_kb, fnorm_kc)
+    assert np.array_equal(hist_kb, hist_kc)
+    for col in range(k):
+        assert np.array_equal(xs_b[col], xs_c[col]), col
+    for p in (a, b, c):
+        p.close()
+
+
 # ---- 7. bit-reproducibility ---------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("name,smoother", [("lap2d_s0", "rb"), ("pot3d", "wjacobi")])

@@ -1,6 +1,7 @@
 // The single-GPU cycle: smoothers, the legs of a V-cycle as fused passes, two-level passes and single launches, the
 // cycle's tail, the 3-D legs, Gram-Schmidt between the levels, the HIP-graph cache that replays whole launch sequences,
-// and the C-ABI entries of the cycle and its pieces.  Host code only; every kernel it enqueues is in kernels_*.hip.
+// and the C-ABI entries of the cycle and its pieces.  Residual + restriction is chosen in one place (residual_to_coarse) and
+// the coarsest level is (re)factored in one (factor_coarse).  Host code only; every kernel it enqueues is in kernels_*.hip.
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -206,6 +207,24 @@ bool bonds_restrict_ok(const mgcmt_plan* p, int l) {
   return p->dim == 2 && (F.dA.k.point == kPointPlanes || F.dA.k.point == kPointBonds) && C.nr * 2 == F.nr && C.gc * 2 == F.gc;
 }
 
+// F[l+1] <- R (F[l] - (A - mu) V[l]) and, with clear_coarse, V[l+1] <- 0; the slots V, F, T of level l and V, F of level l + 1
+// are in place.  One pass that stores no fine residual where the level has one — a 3-D level; a 2-D level with bonds or planes
+// whose kernels take it — otherwise the residual into T and its restriction.
+int residual_to_coarse(mgcmt_plan* p, int l, int k, bool clear_coarse, hipStream_t s) {
+  const KVec v = p->kvec(l, MGCMT_SLOT_V), f = p->kvec(l, MGCMT_SLOT_F), fc = p->kvec(l + 1, MGCMT_SLOT_F);
+  const KVec vc = clear_coarse ? p->kvec(l + 1, MGCMT_SLOT_V) : KVec{nullptr, 0};
+  if (p->dim == 3) {
+    launch3_residual_restrict(s, p->levels[l].dA.k3, v, f, fc, vc, p->d_shifts, k);
+    return post_launch();
+  }
+  if (bonds_restrict_ok(p, l) && launch_point_residual_restrict(s, p->kgrid(l), p->levels[l].dA.k, v, f, fc, vc, p->d_shifts, k)) return post_launch();
+  launch_residual(s, p->kgrid(l), p->levels[l].dA.k, v, f, p->kvec(l, MGCMT_SLOT_T), p->d_shifts, k);
+  launch_restrict(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l, MGCMT_SLOT_T), fc, k);
+  if (clear_coarse)
+    for (int q = 0; q < k; ++q) launch_fill(s, p->kvec(l + 1, MGCMT_SLOT_V, q).p, p->interior(l + 1), 0.0);
+  return post_launch();
+}
+
 int residual_restrict_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {
   if (l + 1 >= (int)p->levels.size()) return fail(MGCMT_ERR_INVALID, "no coarser level");
   MG_TRY(ensure_slot(p, l, MGCMT_SLOT_V));
@@ -213,19 +232,7 @@ int residual_restrict_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {
   MG_TRY(ensure_slot(p, l, MGCMT_SLOT_T));
   MG_TRY(ensure_slot(p, l + 1, MGCMT_SLOT_V));
   MG_TRY(ensure_slot(p, l + 1, MGCMT_SLOT_F));
-  if (p->dim == 3) {  // one pass: F[l+1] and V[l+1] = 0 written, no fine residual stored
-    launch3_residual_restrict(s, p->levels[l].dA.k3, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l + 1, MGCMT_SLOT_F),
-                              p->kvec(l + 1, MGCMT_SLOT_V), p->d_shifts, k);
-    return post_launch();
-  }
-  // a level with bonds on the marching kernels: one pass, F[l+1] and V[l+1] = 0 written, no fine residual stored
-  if (bonds_restrict_ok(p, l) && launch_point_residual_restrict(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F),
-                                                                p->kvec(l + 1, MGCMT_SLOT_F), p->kvec(l + 1, MGCMT_SLOT_V), p->d_shifts, k))
-    return post_launch();
-  launch_residual(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, k);
-  launch_restrict(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l, MGCMT_SLOT_T), p->kvec(l + 1, MGCMT_SLOT_F), k);
-  for (int q = 0; q < k; ++q) launch_fill(s, p->kvec(l + 1, MGCMT_SLOT_V, q).p, p->interior(l + 1), 0.0);
-  return post_launch();
+  return residual_to_coarse(p, l, k, true, s);
 }
 
 int prolong_correct_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {
@@ -234,6 +241,25 @@ int prolong_correct_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {
   MG_TRY(ensure_slot(p, l + 1, MGCMT_SLOT_V));
   if (p->dim == 3) launch3_prolong(s, p->levels[l].gr, p->kvec(l + 1, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_V), 1, k);
   else launch_prolong(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l + 1, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_V), 1, k);
+  return post_launch();
+}
+
+// The coarsest-level matrix (the per-point entries ride in the assembly) for the current shifts, factored and, where the
+// explicit inverse is kept, inverted; nothing to do while the first k shifts are those of the last time.  The band storage exists.
+int factor_coarse(mgcmt_plan* p, int l, int k, hipStream_t s) {
+  Level& L = p->levels[l];
+  BandState& B = L.band;
+  bool same = B.valid && B.k >= k;
+  if (same)
+    for (int q = 0; q < k; ++q) same = same && B.shifts[q] == p->h_shifts[q];
+  if (same) return MGCMT_OK;
+  if (p->dim == 3) launch3_band_assemble(s, L.dA.k3, p->d_shifts, B.b, k);
+  else launch_band_assemble(s, p->kgrid(l), L.dA.k, p->d_shifts, B.b, k);
+  launch_band_factor(s, B.b, k);
+  if (B.inv) launch_band_invert(s, B.b, B.inv, (long)B.b.n * B.b.n, k);
+  B.valid = true;
+  B.k = k;
+  B.shifts.assign(p->h_shifts.begin(), p->h_shifts.begin() + k);
   return post_launch();
 }
 
@@ -260,18 +286,7 @@ int ensure_coarse_ready(mgcmt_plan* p, int l, int k, hipStream_t s) {
     MG_HIP(hipMalloc((void**)&B.b.piv, sizeof(int) * B.b.piv_stride * cols));
     if (n <= 1024) MG_HIP(hipMalloc((void**)&B.inv, sizeof(double) * n * n * cols));
   }
-  bool same = B.valid && B.k >= k;
-  if (same)
-    for (int q = 0; q < k; ++q) same = same && B.shifts[q] == p->h_shifts[q];
-  if (!same) {
-    if (p->dim == 3) launch3_band_assemble(s, L.dA.k3, p->d_shifts, B.b, k);
-    else launch_band_assemble(s, p->kgrid(l), L.dA.k, p->d_shifts, B.b, k);
-    launch_band_factor(s, B.b, k);
-    if (B.inv) launch_band_invert(s, B.b, B.inv, n * n, k);
-    B.valid = true;
-    B.k = k;
-    B.shifts.assign(p->h_shifts.begin(), p->h_shifts.begin() + k);
-  }
+  MG_TRY(factor_coarse(p, l, k, s));
   return post_launch();
 }
 
@@ -302,11 +317,6 @@ int down_leg(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, bool z
   if (zero_in && !(nu >= 1 && fused_level(p, l, kind)))
     for (int q = 0; q < k; ++q) launch_fill(s, p->kvec(l, MGCMT_SLOT_V, q).p, p->interior(l), 0.0);
   if (nu >= 1 && fused_level(p, l, kind)) {
-    MG_TRY(ensure_slot(p, l, MGCMT_SLOT_V));
-    MG_TRY(ensure_slot(p, l, MGCMT_SLOT_F));
-    MG_TRY(ensure_slot(p, l, MGCMT_SLOT_T));
-    MG_TRY(ensure_slot(p, l + 1, MGCMT_SLOT_V));
-    MG_TRY(ensure_slot(p, l + 1, MGCMT_SLOT_F));
     int left = nu, zi = zero_in ? 4 : 0;
     while (left > pass_sweeps(p, l, kind, left)) {
       const int n = pass_sweeps(p, l, kind, left);
@@ -331,12 +341,7 @@ int down_leg(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, bool z
   }
   MG_TRY(smooth_impl(p, l, kind, nu, omega, k, s));
   // (V[l+1] is cleared by the level below, which starts from "zero, uncleared")
-  if (bonds_restrict_ok(p, l) && launch_point_residual_restrict(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F),
-                                                                p->kvec(l + 1, MGCMT_SLOT_F), KVec{nullptr, 0}, p->d_shifts, k))
-    return post_launch();
-  launch_residual(s, p->kgrid(l), p->levels[l].dA.k, p->kvec(l, MGCMT_SLOT_V), p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->d_shifts, k);
-  launch_restrict(s, p->kgrid(l), p->kgrid(l + 1), p->kvec(l, MGCMT_SLOT_T), p->kvec(l + 1, MGCMT_SLOT_F), k);
-  return post_launch();
+  return residual_to_coarse(p, l, k, false, s);
 }
 
 // prolongation + correction + post-smoothing (MGCMTSolver.py:323-326)
@@ -490,21 +495,8 @@ namespace {
 
 // (re)factor the coarsest-level matrix when the shifts changed; no-op otherwise
 int ensure_coarse_factor(mgcmt_plan* p, int l, int k, hipStream_t s) {
-  Level& L = p->levels[l];
-  BandState& B = L.band;
-  bool same = B.b.ab && B.valid && B.k >= k;
-  if (same)
-    for (int q = 0; q < k; ++q) same = same && B.shifts[q] == p->h_shifts[q];
-  if (same) return MGCMT_OK;
-  if (!B.b.ab) return MGCMT_OK;  // first use: coarse_solve_impl allocates and factors
-  if (p->dim == 3) launch3_band_assemble(s, L.dA.k3, p->d_shifts, B.b, k);
-  else launch_band_assemble(s, p->kgrid(l), L.dA.k, p->d_shifts, B.b, k);
-  launch_band_factor(s, B.b, k);
-  if (B.inv) launch_band_invert(s, B.b, B.inv, (long)B.b.n * B.b.n, k);
-  B.valid = true;
-  B.k = k;
-  B.shifts.assign(p->h_shifts.begin(), p->h_shifts.begin() + k);
-  return post_launch();
+  if (!p->levels[l].band.b.ab) return MGCMT_OK;  // first use: coarse_solve_impl allocates and factors
+  return factor_coarse(p, l, k, s);
 }
 
 // First level of the cycle's tail: the levels of at most 32 x 32 points below the level the cycle starts on run as

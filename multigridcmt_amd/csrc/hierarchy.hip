@@ -1,5 +1,8 @@
 // The level hierarchy of a plan: the host Galerkin factors of every level, their upload (with the classification of
 // the operator the kernels branch on), plan creation for 1, 2 and 3 axes, destruction and the entries that describe levels.
+// A per-point part (a diagonal, bonds or a stencil; 2-D or 3-D) has ONE description here: PointPart (what a creator hands
+// over), point_planes (how many planes a level holds), build_point_part (every level's planes), create_point (the checks all
+// six creators share, with check_bonds / check_stencil) and point_of (what the entries that describe levels read).
 // Host code only.
 #include <cstdlib>
 #include <cstring>
@@ -275,6 +278,17 @@ int upload_op3(const HostOp& h, int64_t n, DevOp* d) {
   return MGCMT_OK;
 }
 
+// The per-point part of A as a creator hands it over (host arrays).  kPointDiag: planes = {D}; kPointBonds: {D, b_0, ..,
+// b_dim-1}, the bond plane of axis a counted from the fastest index — 2-D: E (towards (i, j + 1)), S (towards (i + 1, j));
+// 3-D: Bx, By, Bz —; kPointPlanes: {G}, the 3^dim planes of a 9- / 27-point stencil one behind the other.  g^dim numbers a plane.
+struct PointPart {
+  int kind = kPointNone;
+  const double* planes[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+
+// how many planes a level of a dim-axis plan with this kind of per-point part holds
+int point_planes(int dim, int kind) { return kind == kPointDiag ? 1 : kind == kPointBonds ? dim + 1 : dim == 3 ? 27 : 9; }
+
 // What a creator asks for.  fac / m_fac: the factor arrays of A / M per axis as HostOp holds them — {X, Y, Z}, i.e.
 // 3-D: {z, y, x}; 2-D: {rows, columns}; 1-D: {none, the vector} (X is the 1 x 1 identity there) — nterms blocks of 3 g each
 struct PlanSpec {
@@ -285,145 +299,94 @@ struct PlanSpec {
   const double* m_fac[3];
   int64_t row_begin, row_end;  // a 2-D plan's rows of level 0, (0, 0) = all; ignored otherwise
   int strip_levels;
-  const double* point_diag = nullptr;  // g x g (2-D, mgcmt_plan_create_pot) or g^3 (3-D, mgcmt_plan_create3d_pot) numbers added to the diagonal of A, host
-  const double* point_east = nullptr;  // 2-D, mgcmt_plan_create_bonds: g x g numbers each, added to the entries between (i, j) and
-  const double* point_south = nullptr;  // (i, j + 1) / (i + 1, j); both or neither
-  const double* point_bonds3[3] = {nullptr, nullptr, nullptr};  // 3-D, mgcmt_plan_create3d_bonds: Bx, By, Bz, g^3 numbers each; all or none
-  const double* point_nine = nullptr;  // 2-D, mgcmt_plan_create_nine: nine planes of g x g numbers (instead of point_diag)
-  const double* point_stencil3 = nullptr;  // 3-D, mgcmt_plan_create3d_stencil: 27 planes of g^3 numbers (instead of point_diag)
+  PointPart point{};  // 2-D and 3-D (create_point)
 };
 
-// The per-point part of A on every level (kernels_pointwise.hip): the diagonal D on level 0 in the level's padded row
-// layout (zero halo rows), below it the nine planes of R D P, R (R D P) P, ... formed on the device, one launch per level.
-// The Kronecker part's operators (upload_op) are in place; this adds the pointers to them.
-// With bonds (east, south: mgcmt_plan_create_bonds) level 0 holds three such planes — D, E, S, each with its zero halo
-// rows — and KOp::point = kPointBonds; their Galerkin product is the same nine planes, so the levels below are what they always were.
-// With a 9-point stencil (nine: mgcmt_plan_create_nine) level 0 is a nine-plane level itself — KOp::point = kPointPlanes, the layout of
-// the levels below, whose planes k_pw_coarsen forms from it as it forms level 2 from level 1.
-int build_point_part(mgcmt_plan* p, const double* point_diag, const double* east, const double* south, const double* nine) {
-  // which nine-plane levels take the tile kernels (KOp::pmarch; kernels_nine_tile.hip).  Unset or "1": level 0 of a plan with a
-  // 9-point stencil, every pass (each measured faster than its flat form at 4096^2; nine_tiled adds the size rule);
-  // "0": none (A/B tests); "2": the Galerkin levels of every plan with a per-point part as well (measurements; not the default:
-  // existing plans run the launches they always ran).
-  const char* nt = getenv("MGCMT_NINE_TILE");
-  const int tile_mode = !nt || !nt[0] ? 1 : nt[0] == '0' ? 0 : nt[0] == '2' ? 2 : 1;
-  const int tile_all = kNineColour | kNineJacobi | kNineResidual;
-  // which passes of the fine level of a plan with bonds march (KOp::pmarch; kernels_bonds.hip).  Unset: those that measured
-  // faster than their flat form at 8192^2 — the parity stages and residual + restriction (bit 0); the weighted-Jacobi sweep
-  // and the applied operator measured level with it and stay flat.  "1": every pass (bit 1 as well); "0": none (A/B tests).
-  const char* e = getenv("MGCMT_BONDS_MARCH");
-  const int march = !e || !e[0] ? 1 : e[0] == '0' ? 0 : 3;
+PlanSpec spec_of(const mgcmt_plan_desc& d) {
+  return PlanSpec{d.dim, d.nvec, d.device, d.g, d.lowest, d.nterms, d.m_nterms, {d.xfac, d.yfac, nullptr}, {d.m_xfac, d.m_yfac, nullptr},
+                  d.row_begin, d.row_end, d.strip_levels};
+}
+
+PlanSpec spec_of(const mgcmt_plan3d_desc& d) {
+  return PlanSpec{3, d.nvec, d.device, d.g, d.lowest, d.nterms, 0, {d.zfac, d.yfac, d.xfac}, {nullptr, nullptr, nullptr}, 0, 0, 0};
+}
+
+// the per-point part of level l as the kernels see it, whichever of KOp / K3Op holds it
+struct PointView {
+  int kind;
+  const double* pg;
+  long pplane;
+};
+
+PointView point_of(const mgcmt_plan* p, int l) {
+  const DevOp& d = p->levels[l].dA;
+  return p->dim == 3 ? PointView{d.k3.point, d.k3.pg, d.k3.pplane} : PointView{d.k.point, d.k.pg, d.k.pplane};
+}
+
+// The per-point part of A on every level (2-D: kernels_pointwise.hip, 3-D: kernels_3d_point.hip).  Level 0 holds the
+// caller's planes (PointPart), pplane apart, and KOp::point / K3Op::point = their kind; every level below holds the 3^dim
+// planes of the Galerkin product R (.) P of the level above (kPointPlanes), formed on the device, one launch per level — the
+// same launch whatever the kind above, so a stencil's level 1 is formed from level 0 as level 2 is from level 1.  The Kronecker
+// part's operators (upload_op / upload_op3) are in place; this adds the pointers to them.
+// Layout of level 0: a 2-D diagonal or D, E, S sit in the level's padded row layout each (zero halo rows, pg at the interior:
+// the marching kernels read S(-1, j) as an exact zero); 2-D stencil planes and everything in 3-D (the kernels predicate all
+// directions) are g^dim numbers a plane, at the index of the right-hand side.
+int build_point_part(mgcmt_plan* p, const PointPart& pt) {
+  const bool three = p->dim == 3;
+  // Which levels of planes take the tile kernels (pmarch; 2-D: kernels_nine_tile.hip, nine_tiled adds the size rule, MGCMT_NINE_TILE;
+  // 3-D: kernels_3d_stencil.hip, stencil3_tiled adds it, MGCMT_3D_STENCIL_TILE).  Unset or "1": level 0 of a plan with a stencil,
+  // the passes in tile_all (2-D: each measured faster than its flat form at 4096^2; 3-D: those that measured no slower than
+  // 1.03 x their flat form at 256^3: DESIGN par. 4.18); "0": none (A/B tests); "2": the Galerkin levels of every plan with a
+  // per-point part as well (measurements; not the default: existing plans run the launches they always ran).
+  const char* t = getenv(three ? "MGCMT_3D_STENCIL_TILE" : "MGCMT_NINE_TILE");
+  const int tile_mode = !t || !t[0] ? 1 : t[0] == '0' ? 0 : t[0] == '2' ? 2 : 1;
+  const int tile_all = three ? kStencil3Colour | kStencil3Residual : kNineColour | kNineJacobi | kNineResidual;
+  // Which passes of a fine level with a diagonal or bonds march (pmarch).  3-D (point3_marching adds the size rule): all of them,
+  // MGCMT_3D_POINT_MARCH = "0": none (A/B tests).  2-D, bonds only (kernels_bonds.hip; MGCMT_BONDS_MARCH): unset, those that
+  // measured faster than their flat form at 8192^2 — the parity stages and residual + restriction (bit 0); the weighted-Jacobi
+  // sweep and the applied operator measured level with it and stay flat; "1": every pass (bit 1 as well); "0": none.
+  const char* e = getenv(three ? "MGCMT_3D_POINT_MARCH" : "MGCMT_BONDS_MARCH");
+  int march = three ? kMarch3Jacobi | kMarch3Parity | kMarch3Residual | kMarch3Prolong : pt.kind != kPointBonds ? 0 : !e || !e[0] ? 1 : 3;
+  if (e && e[0] == '0') march = 0;
+  auto set = [&](Level& L, int kind, int pmarch, const double* pg, size_t pplane) {
+    auto fill = [&](auto& k) {  // (KOp and K3Op name these alike)
+      k.point = kind;
+      k.pmarch = pmarch;
+      k.pg = pg;
+      k.pplane = (long)pplane;
+    };
+    if (three) {
+      fill(L.dA.k3);
+    } else {
+      fill(L.dA.k);
+      L.dA.k.pld = L.gc;
+    }
+  };
   for (size_t l = 0; l < p->levels.size(); ++l) {
     Level& L = p->levels[l];
-    KOp& k = L.dA.k;
+    const size_t N = (size_t)L.nr * L.gc;
     double* q = nullptr;
-    if (l == 0 && nine) {
-      const size_t plane = (size_t)L.nr * L.gc;
-      MG_HIP(hipMalloc((void**)&q, 9 * plane * sizeof(double)));
-      L.dA.owned.push_back(q);
-      MG_HIP(hipMemcpy(q, nine, 9 * plane * sizeof(double), hipMemcpyHostToDevice));
-      k.point = kPointPlanes;
-      k.pmarch = tile_mode >= 1 ? tile_all : 0;
-      k.pg = q;
-      k.pld = L.gc;
-      k.pplane = (long)plane;
-      continue;
-    }
-    if (l == 0 && east) {
-      const size_t padded = (size_t)(L.nr + 2 * L.halo) * L.gc, rows = (size_t)L.nr * L.gc, first = (size_t)L.halo * L.gc;
-      MG_HIP(hipMalloc((void**)&q, 3 * padded * sizeof(double)));
-      L.dA.owned.push_back(q);
-      MG_HIP(hipMemset(q, 0, 3 * padded * sizeof(double)));
-      MG_HIP(hipMemcpy(q + first, point_diag, rows * sizeof(double), hipMemcpyHostToDevice));
-      MG_HIP(hipMemcpy(q + padded + first, east, rows * sizeof(double), hipMemcpyHostToDevice));
-      MG_HIP(hipMemcpy(q + 2 * padded + first, south, rows * sizeof(double), hipMemcpyHostToDevice));
-      k.point = kPointBonds;
-      k.pmarch = march;
-      k.pg = q + first;
-      k.pld = L.gc;
-      k.pplane = (long)padded;
-      continue;
-    }
     if (l == 0) {
-      const size_t padded = (size_t)(L.nr + 2 * L.halo) * L.gc;
-      MG_HIP(hipMalloc((void**)&q, padded * sizeof(double)));
+      const int np = point_planes(p->dim, pt.kind);
+      const bool padded = !three && pt.kind != kPointPlanes;
+      const size_t first = padded ? (size_t)L.halo * L.gc : 0, plane = N + 2 * first;
+      MG_HIP(hipMalloc((void**)&q, np * plane * sizeof(double)));
       L.dA.owned.push_back(q);
-      MG_HIP(hipMemset(q, 0, padded * sizeof(double)));
-      MG_HIP(hipMemcpy(q + (size_t)L.halo * L.gc, point_diag, (size_t)L.nr * L.gc * sizeof(double), hipMemcpyHostToDevice));
-      k.point = kPointDiag;
-      k.pg = q + (size_t)L.halo * L.gc;
-      k.pld = L.gc;
-      k.pplane = 0;
+      if (padded) MG_HIP(hipMemset(q, 0, np * plane * sizeof(double)));
+      if (pt.kind == kPointPlanes) MG_HIP(hipMemcpy(q, pt.planes[0], np * N * sizeof(double), hipMemcpyHostToDevice));
+      else
+        for (int a = 0; a < np; ++a) MG_HIP(hipMemcpy(q + a * plane + first, pt.planes[a], N * sizeof(double), hipMemcpyHostToDevice));
+      set(L, pt.kind, pt.kind == kPointPlanes ? (tile_mode >= 1 ? tile_all : 0) : march, q + first, pt.kind == kPointDiag ? 0 : plane);
       continue;
     }
     const Level& F = p->levels[l - 1];
-    const KOp& kf = F.dA.k;
-    MG_HIP(hipMalloc((void**)&q, (size_t)9 * L.nr * L.gc * sizeof(double)));
+    const PointView f = point_of(p, (int)l - 1);
+    MG_HIP(hipMalloc((void**)&q, point_planes(p->dim, kPointPlanes) * N * sizeof(double)));
     L.dA.owned.push_back(q);
-    launch_point_coarsen(nullptr, F.nr, F.gc, kf.pg, kf.point == kPointDiag ? 1 : kf.point == kPointBonds ? 3 : 9, kf.pld, kf.pplane, q, L.gc, L.nr * L.gc);
+    if (three) launch3p_coarsen(nullptr, F.dA.k3.n, f.pg, point_planes(3, f.kind), f.pplane, q, (long)N);
+    else launch_point_coarsen(nullptr, F.nr, F.gc, f.pg, point_planes(2, f.kind), F.gc, f.pplane, q, L.gc, L.nr * L.gc);
     MG_TRY(post_launch());
-    k.point = kPointPlanes;
-    k.pmarch = tile_mode == 2 ? tile_all : 0;
-    k.pg = q;
-    k.pld = L.gc;
-    k.pplane = L.nr * L.gc;
-  }
-  MG_HIP(hipDeviceSynchronize());
-  p->has_point = true;
-  return MGCMT_OK;
-}
-
-// The same on a 3-D plan (kernels_3d_point.hip): D as g^3 numbers at the index of the right-hand side (no halo planes: the
-// kernels predicate all three directions), below it the 27 planes of R D P, R (R D P) P, ...
-// With bonds (mgcmt_plan_create3d_bonds) level 0 holds four such planes — D, Bx, By, Bz — and K3Op::point = kPointBonds; their
-// Galerkin product is the same 27 planes, so the levels below are what they always were.
-// With a 27-point stencil (stencil: mgcmt_plan_create3d_stencil) level 0 is a 27-plane level itself — K3Op::point = kPointPlanes,
-// the layout of the levels below, whose planes k3p_coarsen forms from it as it forms level 2 from level 1.
-int build_point_part3(mgcmt_plan* p, const double* point_diag, const double* const* bonds, const double* stencil) {
-  // which 27-plane levels take the kernels of kernels_3d_stencil.hip (K3Op::pmarch; stencil3_tiled adds the size rule).  Unset
-  // or "1": level 0 of a plan with a 27-point stencil, the passes in tile_default (those that measured no slower than 1.03 x
-  // their flat form at 256^3: DESIGN par. 4.18); "0": none (A/B tests); "2": every pass, on the Galerkin levels of every plan
-  // with a per-point part as well (measurements; not the default: existing plans run the launches they always ran).
-  const char* st = getenv("MGCMT_3D_STENCIL_TILE");
-  const int tile_mode = !st || !st[0] ? 1 : st[0] == '0' ? 0 : st[0] == '2' ? 2 : 1;
-  const int tile_all = kStencil3Colour | kStencil3Residual, tile_default = kStencil3Colour | kStencil3Residual;
-  const char* e = getenv("MGCMT_3D_POINT_MARCH");  // "0": the fine level on the flat kernels (A/B tests)
-  // the passes of the fine level that march (K3Op::pmarch; point3_marching adds the size rule)
-  const int march = e && e[0] == '0' ? 0 : (kMarch3Jacobi | kMarch3Parity | kMarch3Residual | kMarch3Prolong);
-  for (size_t l = 0; l < p->levels.size(); ++l) {
-    Level& L = p->levels[l];
-    K3Op& k = L.dA.k3;
-    const size_t N = (size_t)L.nr * L.gc;
-    double* q = nullptr;
-    MG_HIP(hipMalloc((void**)&q, (l == 0 && !stencil ? (bonds[0] ? 4 : 1) : 27) * N * sizeof(double)));
-    L.dA.owned.push_back(q);
-    k.pg = q;
-    k.pmarch = l == 0 ? march : tile_mode == 2 ? tile_all : 0;
-    if (l == 0 && stencil) {
-      MG_HIP(hipMemcpy(q, stencil, 27 * N * sizeof(double), hipMemcpyHostToDevice));
-      k.point = kPointPlanes;
-      k.pplane = (long)N;
-      k.pmarch = tile_mode == 2 ? tile_all : tile_mode == 1 ? tile_default : 0;
-      continue;
-    }
-    if (l == 0 && bonds[0]) {
-      MG_HIP(hipMemcpy(q, point_diag, N * sizeof(double), hipMemcpyHostToDevice));
-      for (int a = 0; a < 3; ++a) MG_HIP(hipMemcpy(q + (a + 1) * N, bonds[a], N * sizeof(double), hipMemcpyHostToDevice));
-      k.point = kPointBonds;
-      k.pplane = (long)N;
-      continue;
-    }
-    if (l == 0) {
-      MG_HIP(hipMemcpy(q, point_diag, N * sizeof(double), hipMemcpyHostToDevice));
-      k.point = kPointDiag;
-      k.pplane = 0;
-      continue;
-    }
-    const K3Op& kf = p->levels[l - 1].dA.k3;
-    launch3p_coarsen(nullptr, kf.n, kf.pg, kf.point == kPointDiag ? 1 : kf.point == kPointBonds ? 4 : 27, kf.pplane, q, (long)N);
-    MG_TRY(post_launch());
-    k.point = kPointPlanes;
-    k.pplane = (long)N;
+    set(L, kPointPlanes, tile_mode == 2 ? tile_all : 0, q, N);
   }
   MG_HIP(hipDeviceSynchronize());
   p->has_point = true;
@@ -531,9 +494,8 @@ int build_plan(const PlanSpec& d, mgcmt_plan** out) {
       return rc;
     }
   }
-  if (d.point_diag || d.point_nine || d.point_stencil3) {
-    const int rc = d.dim == 3 ? build_point_part3(p, d.point_diag, d.point_bonds3, d.point_stencil3)
-                              : build_point_part(p, d.point_diag, d.point_east, d.point_south, d.point_nine);
+  if (d.point.kind != kPointNone) {
+    const int rc = build_point_part(p, d.point);
     if (rc != MGCMT_OK) {
       mgcmt_plan_destroy(p);
       return rc;
@@ -548,6 +510,78 @@ int build_plan(const PlanSpec& d, mgcmt_plan** out) {
   return MGCMT_OK;
 }
 
+// a stencil's 3^dim planes of g^dim numbers (plane index: the offsets + 1 as base-3 digits, slowest axis first): coefficients
+// towards points outside the grid are zero and the stencil is symmetric
+int check_stencil(int dim, int64_t g, const double* G) {
+  if (g < 1) return MGCMT_OK;  // (build_plan refuses it)
+  const int np = point_planes(dim, kPointPlanes);
+  int64_t N = 1;
+  for (int a = 0; a < dim; ++a) N *= g;
+  for (int t = 0; t < np; ++t) {
+    int o[3] = {0, 0, 0};  // the plane's offset per axis, slowest first; off: the same as a distance in the plane
+    int64_t off = 0, w = 1;
+    for (int a = dim - 1, r = t; a >= 0; --a, r /= 3, w *= g) off += (o[a] = r % 3 - 1) * w;
+    const double* P = G + t * N;
+    const double* T = G + (np - 1 - t) * N;  // the plane of the opposite offset
+    int64_t c[3] = {0, 0, 0};  // the slow coordinates of the line of g points at `row`
+    for (int64_t row = 0; row < N; row += g) {
+      bool in = true;
+      for (int a = 0; a < dim - 1; ++a) in = in && c[a] + o[a] >= 0 && c[a] + o[a] < g;
+      for (int64_t x = 0; x < g; ++x) {
+        if (!in || x + o[dim - 1] < 0 || x + o[dim - 1] >= g) {
+          if (P[row + x] != 0.0) return fail(MGCMT_ERR_INVALID, "point stencil: a coefficient towards a point outside the grid must be zero");
+        } else if (P[row + x] != T[row + x + off]) {
+          return fail(MGCMT_ERR_INVALID, dim == 3 ? "point stencil is not symmetric: the coefficient of p' in the row of p must equal that of p in the row of p'"
+                                                  : "point stencil is not symmetric: the coefficient of (i', j') in row (i, j) must equal that of (i, j) in row (i', j')");
+        }
+      }
+      for (int a = dim - 2; a >= 0 && ++c[a] == g; --a) c[a] = 0;
+    }
+  }
+  return MGCMT_OK;
+}
+
+// bonds[a] (axis a counted from the fastest index) is zero where the index along its axis is g - 1: no bond leaves the grid
+int check_bonds(int dim, int64_t g, const double* const* bonds) {
+  if (g < 1) return MGCMT_OK;  // (build_plan refuses it)
+  int64_t N = 1, s = 1;  // s: the distance between neighbours along axis a
+  for (int a = 0; a < dim; ++a) N *= g;
+  for (int a = 0; a < dim; ++a, s *= g)
+    for (int64_t hi = 0; hi < N; hi += s * g)
+      for (int64_t lo = 0; lo < s; ++lo)
+        if (bonds[a][hi + (g - 1) * s + lo] != 0.0)
+          return fail(MGCMT_ERR_INVALID,
+                      dim == 3 ? "bonds towards points outside the grid (bx at x = g - 1, by at y = g - 1, bz at z = g - 1) must be zero"
+                               : "bonds towards points outside the grid (the last column of east, the last row of south) must be zero");
+  return MGCMT_OK;
+}
+
+// A plan with a per-point part, for all six creators: a whole 2-D or 3-D grid without a mass operator.  Desc: mgcmt_plan_desc
+// (dim = 2) or mgcmt_plan3d_desc (dim = 3).
+template <class Desc>
+int create_point(int dim, const Desc* d, const PointPart& pt, mgcmt_plan** out) {
+  static const char* const null_msg[] = {"", "null point diagonal", "null point stencil", "null point diagonal or bond array"};  // by kind
+  static const char* const part[] = {"", "a point diagonal", "a point stencil", "a point diagonal with bonds"};
+  static const char* const plan_with[] = {"", "a plan with a point diagonal", "a plan with a point diagonal (a point stencil)", "a plan with a point diagonal"};
+  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
+  *out = nullptr;
+  for (int a = 0; a < (pt.kind == kPointPlanes ? 1 : point_planes(dim, pt.kind)); ++a)
+    if (!pt.planes[a]) return fail(MGCMT_ERR_INVALID, null_msg[pt.kind]);
+  PlanSpec spec = spec_of(*d);
+  if (spec.dim != dim) return fail(MGCMT_ERR_INVALID, std::string(part[pt.kind]) + " needs a 2-D plan (dim = 2)");  // (a 3-D desc has no dim to get wrong)
+  if (dim == 3 && spec.lowest > 16) return fail(MGCMT_ERR_INVALID, "lowest must be at most 16 on a 3-D plan (the coarsest level is solved directly)");
+  if (spec.m_nterms != 0)
+    return fail(MGCMT_ERR_UNSUPPORTED, std::string(plan_with[pt.kind]) + " takes no mass operator (the Rayleigh-quotient entries do not run on it)");
+  if (!((spec.row_begin == 0 && spec.row_end == 0) || (spec.row_begin == 0 && spec.row_end == spec.g)))
+    return fail(MGCMT_ERR_UNSUPPORTED, std::string(plan_with[pt.kind]) + " is a whole grid (no row strips)");
+  if (pt.kind == kPointBonds) MG_TRY(check_bonds(dim, spec.g, pt.planes + 1));
+  if (pt.kind == kPointPlanes) MG_TRY(check_stencil(dim, spec.g, pt.planes[0]));
+  spec.row_begin = spec.row_end = 0;
+  spec.strip_levels = 0;
+  spec.point = pt;
+  return build_plan(spec, out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -557,71 +591,19 @@ int mgcmt_plan_create(const mgcmt_plan_desc* d, mgcmt_plan** out) {
   *out = nullptr;
   if (d->dim != 1 && d->dim != 2) return fail(MGCMT_ERR_INVALID, "dim must be 1 or 2");
   if (d->m_nterms < 0 || d->m_nterms > kMaxTerms) return fail(MGCMT_ERR_INVALID, "nterms out of range");
-  return build_plan(PlanSpec{d->dim, d->nvec, d->device, d->g, d->lowest, d->nterms, d->m_nterms, {d->xfac, d->yfac, nullptr},
-                             {d->m_xfac, d->m_yfac, nullptr}, d->row_begin, d->row_end, d->strip_levels},
-                    out);
+  return build_plan(spec_of(*d), out);
 }
 
 int mgcmt_plan_create_pot(const mgcmt_plan_desc* d, const double* point_diag, mgcmt_plan** out) {
-  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (!point_diag) return fail(MGCMT_ERR_INVALID, "null point diagonal");
-  if (d->dim != 2) return fail(MGCMT_ERR_INVALID, "a point diagonal needs a 2-D plan (dim = 2)");
-  if (d->m_nterms != 0) return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal takes no mass operator (the Rayleigh-quotient entries do not run on it)");
-  if (!((d->row_begin == 0 && d->row_end == 0) || (d->row_begin == 0 && d->row_end == d->g)))
-    return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal is a whole grid (no row strips)");
-  PlanSpec spec{2, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->xfac, d->yfac, nullptr}, {nullptr, nullptr, nullptr}, 0, 0, 0};
-  spec.point_diag = point_diag;
-  return build_plan(spec, out);
+  return create_point(2, d, PointPart{kPointDiag, {point_diag}}, out);
 }
 
 int mgcmt_plan_create_bonds(const mgcmt_plan_desc* d, const double* point_diag, const double* east, const double* south, mgcmt_plan** out) {
-  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (!point_diag || !east || !south) return fail(MGCMT_ERR_INVALID, "null point diagonal or bond array");
-  if (d->dim != 2) return fail(MGCMT_ERR_INVALID, "a point diagonal with bonds needs a 2-D plan (dim = 2)");
-  if (d->m_nterms != 0) return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal takes no mass operator (the Rayleigh-quotient entries do not run on it)");
-  if (!((d->row_begin == 0 && d->row_end == 0) || (d->row_begin == 0 && d->row_end == d->g)))
-    return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal is a whole grid (no row strips)");
-  if (d->g >= 1)
-    for (int64_t i = 0; i < d->g; ++i)
-      if (east[i * d->g + d->g - 1] != 0.0 || south[(d->g - 1) * d->g + i] != 0.0)
-        return fail(MGCMT_ERR_INVALID, "bonds towards points outside the grid (the last column of east, the last row of south) must be zero");
-  PlanSpec spec{2, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->xfac, d->yfac, nullptr}, {nullptr, nullptr, nullptr}, 0, 0, 0};
-  spec.point_diag = point_diag;
-  spec.point_east = east;
-  spec.point_south = south;
-  return build_plan(spec, out);
+  return create_point(2, d, PointPart{kPointBonds, {point_diag, east, south}}, out);
 }
 
 int mgcmt_plan_create_nine(const mgcmt_plan_desc* d, const double* stencil, mgcmt_plan** out) {
-  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (!stencil) return fail(MGCMT_ERR_INVALID, "null point stencil");
-  if (d->dim != 2) return fail(MGCMT_ERR_INVALID, "a point stencil needs a 2-D plan (dim = 2)");
-  if (d->m_nterms != 0) return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal (a point stencil) takes no mass operator (the Rayleigh-quotient entries do not run on it)");
-  if (!((d->row_begin == 0 && d->row_end == 0) || (d->row_begin == 0 && d->row_end == d->g)))
-    return fail(MGCMT_ERR_UNSUPPORTED, "a plan with a point diagonal (a point stencil) is a whole grid (no row strips)");
-  const int64_t g = d->g, plane = g * g;
-  for (int a = 0; a < 3 && g >= 1; ++a)
-    for (int b = 0; b < 3; ++b) {
-      const double* G = stencil + (3 * a + b) * plane;
-      const double* T = stencil + (3 * (2 - a) + (2 - b)) * plane;  // the plane of the opposite offset
-      for (int64_t i = 0; i < g; ++i) {
-        const int64_t ip = i + a - 1;
-        for (int64_t j = 0; j < g; ++j) {
-          const int64_t jp = j + b - 1;
-          if (ip < 0 || ip >= g || jp < 0 || jp >= g) {
-            if (G[i * g + j] != 0.0) return fail(MGCMT_ERR_INVALID, "point stencil: a coefficient towards a point outside the grid must be zero");
-          } else if (G[i * g + j] != T[ip * g + jp]) {
-            return fail(MGCMT_ERR_INVALID, "point stencil is not symmetric: the coefficient of (i', j') in row (i, j) must equal that of (i, j) in row (i', j')");
-          }
-        }
-      }
-    }
-  PlanSpec spec{2, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->xfac, d->yfac, nullptr}, {nullptr, nullptr, nullptr}, 0, 0, 0};
-  spec.point_nine = stencil;
-  return build_plan(spec, out);
+  return create_point(2, d, PointPart{kPointPlanes, {stencil}}, out);
 }
 
 int mgcmt_plan_level_tiled(const mgcmt_plan* p, int l, int* tiled) {
@@ -634,22 +616,12 @@ int mgcmt_plan_level_tiled(const mgcmt_plan* p, int l, int* tiled) {
 int mgcmt_plan_get_point_stencil(const mgcmt_plan* p, int l, double* out, int64_t capacity) {
   MG_TRY(check_level(p, l));
   if (!p->has_point) return fail(MGCMT_ERR_INVALID, "plan has no point diagonal");
-  const Level& L = p->levels[l];
-  if (p->dim == 3) {
-    const K3Op& k3 = L.dA.k3;
-    const int64_t N = L.nr * L.gc, need3 = k3.point == kPointDiag ? N : k3.point == kPointBonds ? 4 * N : 27 * N;  // (D, Bx, By, Bz lie one behind the other)
-    if (!out || capacity < need3) return fail(MGCMT_ERR_INVALID, "point stencil buffer too small");
-    MG_HIP(hipMemcpy(out, k3.pg, (size_t)need3 * sizeof(double), hipMemcpyDeviceToHost));
-    return MGCMT_OK;
-  }
-  const KOp& k = L.dA.k;
-  const int64_t plane = L.nr * L.gc, need = k.point == kPointDiag ? plane : k.point == kPointBonds ? 3 * plane : 9 * plane;
-  if (!out || capacity < need) return fail(MGCMT_ERR_INVALID, "point stencil buffer too small");
-  if (k.point == kPointBonds) {  // D, E, S: the interior rows of each padded plane
-    for (int a = 0; a < 3; ++a) MG_HIP(hipMemcpy(out + a * plane, k.pg + a * k.pplane, (size_t)plane * sizeof(double), hipMemcpyDeviceToHost));
-    return MGCMT_OK;
-  }
-  MG_HIP(hipMemcpy(out, k.pg, (size_t)need * sizeof(double), hipMemcpyDeviceToHost));  // (level 0: the interior rows are contiguous)
+  const PointView v = point_of(p, l);
+  const int np = point_planes(p->dim, v.kind);
+  const int64_t N = p->levels[l].nr * p->levels[l].gc;
+  if (!out || capacity < np * N) return fail(MGCMT_ERR_INVALID, "point stencil buffer too small");
+  // the interior of every plane (2-D level 0 of a diagonal or bonds: the rows between the halo rows, which are contiguous)
+  for (int a = 0; a < np; ++a) MG_HIP(hipMemcpy(out + a * N, v.pg + a * v.pplane, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
   return MGCMT_OK;
 }
 
@@ -660,74 +632,27 @@ static int create3d(const mgcmt_plan3d_desc* d, int32_t m_nterms, const double* 
   if (d->lowest > 16) return fail(MGCMT_ERR_INVALID, "lowest must be at most 16 on a 3-D plan (the coarsest level is solved directly)");
   if (m_nterms < 0 || m_nterms > kMaxTerms) return fail(MGCMT_ERR_INVALID, "mass nterms out of range");
   if (m_nterms > 0 && (!m_xfac || !m_yfac || !m_zfac)) return fail(MGCMT_ERR_INVALID, "missing mass factor arrays");
-  return build_plan(PlanSpec{3, d->nvec, d->device, d->g, d->lowest, d->nterms, m_nterms, {d->zfac, d->yfac, d->xfac},
-                             {m_zfac, m_yfac, m_xfac}, 0, 0, 0},
-                    out);
+  PlanSpec spec = spec_of(*d);
+  spec.m_nterms = m_nterms;
+  spec.m_fac[0] = m_zfac;
+  spec.m_fac[1] = m_yfac;
+  spec.m_fac[2] = m_xfac;
+  return build_plan(spec, out);
 }
 
 int mgcmt_plan_create3d(const mgcmt_plan3d_desc* d, mgcmt_plan** out) { return create3d(d, 0, nullptr, nullptr, nullptr, out); }
 
 int mgcmt_plan_create3d_pot(const mgcmt_plan3d_desc* d, const double* point_diag, mgcmt_plan** out) {
-  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (!point_diag) return fail(MGCMT_ERR_INVALID, "null point diagonal");
-  if (d->lowest > 16) return fail(MGCMT_ERR_INVALID, "lowest must be at most 16 on a 3-D plan (the coarsest level is solved directly)");
-  PlanSpec spec{3, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->zfac, d->yfac, d->xfac}, {nullptr, nullptr, nullptr}, 0, 0, 0};
-  spec.point_diag = point_diag;
-  return build_plan(spec, out);
+  return create_point(3, d, PointPart{kPointDiag, {point_diag}}, out);
 }
 
 int mgcmt_plan_create3d_bonds(const mgcmt_plan3d_desc* d, const double* point_diag, const double* bx, const double* by, const double* bz,
                               mgcmt_plan** out) {
-  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (!point_diag || !bx || !by || !bz) return fail(MGCMT_ERR_INVALID, "null point diagonal or bond array");
-  if (d->lowest > 16) return fail(MGCMT_ERR_INVALID, "lowest must be at most 16 on a 3-D plan (the coarsest level is solved directly)");
-  const int64_t g = d->g;
-  if (g >= 1)
-    for (int64_t a = 0; a < g; ++a)
-      for (int64_t b = 0; b < g; ++b)
-        if (bx[(a * g + b) * g + g - 1] != 0.0 || by[(a * g + g - 1) * g + b] != 0.0 || bz[((g - 1) * g + a) * g + b] != 0.0)
-          return fail(MGCMT_ERR_INVALID,
-                      "bonds towards points outside the grid (bx at x = g - 1, by at y = g - 1, bz at z = g - 1) must be zero");
-  PlanSpec spec{3, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->zfac, d->yfac, d->xfac}, {nullptr, nullptr, nullptr}, 0, 0, 0};
-  spec.point_diag = point_diag;
-  spec.point_bonds3[0] = bx;
-  spec.point_bonds3[1] = by;
-  spec.point_bonds3[2] = bz;
-  return build_plan(spec, out);
+  return create_point(3, d, PointPart{kPointBonds, {point_diag, bx, by, bz}}, out);
 }
 
 int mgcmt_plan_create3d_stencil(const mgcmt_plan3d_desc* d, const double* stencil, mgcmt_plan** out) {
-  if (!d || !out) return fail(MGCMT_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (!stencil) return fail(MGCMT_ERR_INVALID, "null point stencil");
-  if (d->lowest > 16) return fail(MGCMT_ERR_INVALID, "lowest must be at most 16 on a 3-D plan (the coarsest level is solved directly)");
-  const int64_t g = d->g, g2 = g * g, N = g2 * g;
-  for (int a = 0; a < 3 && g >= 1; ++a)
-    for (int b = 0; b < 3; ++b)
-      for (int c = 0; c < 3; ++c) {
-        const double* G = stencil + (9 * a + 3 * b + c) * N;
-        const double* T = stencil + (9 * (2 - a) + 3 * (2 - b) + (2 - c)) * N;  // the plane of the opposite offset
-        const int64_t off = (a - 1) * g2 + (b - 1) * g + (c - 1);
-        for (int64_t z = 0; z < g; ++z) {
-          const bool zin = z + a - 1 >= 0 && z + a - 1 < g;
-          for (int64_t y = 0; y < g; ++y) {
-            const bool yin = zin && y + b - 1 >= 0 && y + b - 1 < g;
-            const int64_t row = z * g2 + y * g;
-            for (int64_t x = 0; x < g; ++x) {
-              if (!yin || x + c - 1 < 0 || x + c - 1 >= g) {
-                if (G[row + x] != 0.0) return fail(MGCMT_ERR_INVALID, "point stencil: a coefficient towards a point outside the grid must be zero");
-              } else if (G[row + x] != T[row + x + off]) {
-                return fail(MGCMT_ERR_INVALID, "point stencil is not symmetric: the coefficient of p' in the row of p must equal that of p in the row of p'");
-              }
-            }
-          }
-        }
-      }
-  PlanSpec spec{3, d->nvec, d->device, d->g, d->lowest, d->nterms, 0, {d->zfac, d->yfac, d->xfac}, {nullptr, nullptr, nullptr}, 0, 0, 0};
-  spec.point_stencil3 = stencil;
-  return build_plan(spec, out);
+  return create_point(3, d, PointPart{kPointPlanes, {stencil}}, out);
 }
 
 int mgcmt_plan3d_level_path(const mgcmt_plan* p, int l, int* kind, int* marching) {

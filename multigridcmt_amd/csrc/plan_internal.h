@@ -98,7 +98,7 @@ struct mgcmt_plan {
   int pcg_march = -1;  // MGCMT_OPT_PCG_MARCH: 1 / 0 = the marching direction pass on / off, -1 = not set (MGCMT_PCG_MARCH, else the default)
   std::vector<double> h_shifts;
   bool has_mass = false;
-  bool has_point = false;  // A carries a per-point part (mgcmt_plan_create_pot / _bonds / mgcmt_plan_create3d_pot / _bonds): KOp::point / K3Op::point on every level
+  bool has_point = false;  // A carries a per-point part — a diagonal, bonds or a stencil, 2-D or 3-D: all six creators go through create_point / build_point_part (hierarchy.hip) —: KOp::point / K3Op::point on every level
   bool use_fused = true;
   bool use_tail = true;   // levels of at most 32 x 32 points as one launch (kernels_tail.hip)
   bool use_tail_dense = true;  // ... and that launch as ONE dense product with the tail's matrix (formed once per shift set)

@@ -151,6 +151,29 @@ class StructuredOperator:
         self.shape = (n, n)
         self._fingerprint = None
 
+    # -- the per-point part as a plan keeps it -----------------------------------------------------
+    def point_part(self):
+        """(kind, arrays): (None, ()) without a per-point part; ("diag", (D,)); ("bonds", (D, b_0, ..)) with the bonds of axis a
+        counted from the fastest index — 2-D: E, S; 3-D: Bx, By, Bz —; ("planes", (G,)) for a point stencil.  The order of
+        the arrays is the order of the planes on level 0 of a plan (``Plan.point_stencil(0)``)."""
+        if self.point_stencil is not None:
+            return "planes", (self.point_stencil,)
+        if self.point_bonds is not None:
+            return "bonds", (self.point_diagonal,) + self.point_bonds
+        if self.point_diagonal is not None:
+            return "diag", (self.point_diagonal,)
+        return None, ()
+
+    @staticmethod
+    def point_keywords(kind, planes):
+        """The constructor's keywords for a per-point part of `kind` whose planes come as ``Plan.point_stencil(0)`` returns
+        them (the inverse of point_part)."""
+        if kind == "planes":
+            return {"point_stencil": planes}
+        if kind == "bonds":
+            return {"point_diagonal": planes[0], "point_bonds": tuple(planes[1:])}
+        return {"point_diagonal": planes} if kind == "diag" else {}
+
     # -- algebra with scalars ---------------------------------------------------------------------
     def _scaled(self, c):
         c = float(c)

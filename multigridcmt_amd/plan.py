@@ -17,6 +17,13 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+# the creator of a plan whose operator has a per-point part, by (axes, StructuredOperator.point_part kind); it takes the
+# arrays of point_part in their order, and how messages name the kind
+_POINT_CREATORS = {(2, "diag"): "mgcmt_plan_create_pot", (2, "bonds"): "mgcmt_plan_create_bonds", (2, "planes"): "mgcmt_plan_create_nine",
+                   (3, "diag"): "mgcmt_plan_create3d_pot", (3, "bonds"): "mgcmt_plan_create3d_bonds", (3, "planes"): "mgcmt_plan_create3d_stencil"}
+_POINT_NAMES = {"diag": "a point diagonal", "bonds": "a point diagonal and point bonds", "planes": "a point stencil (a point diagonal and more)"}
+
+
 class Plan:
     def __init__(self, op, lowest, nvec=1, mass=None, device=0, row_begin=0, row_end=0, strip_levels=0):
         self._h = c_void_p()
@@ -27,53 +34,37 @@ class Plan:
         self.lowest = int(lowest)
         self.nvec = int(nvec)
         self.device = device
+        sharded = bool(row_begin or row_end or strip_levels)
+        kind, arrays = op.point_part()
+        if kind is not None and (mass is not None or sharded):
+            raise self._point_refusal(kind, mass is not None)
         if self.dim == 3:
-            self._create3d(op, mass, row_begin, row_end, strip_levels)
-            return
-        nterms, xfac, yfac = op.factor_blocks()
-        desc = PlanDesc()
-        desc.dim, desc.nterms, desc.g, desc.lowest = self.dim, nterms, self.g, self.lowest
-        desc.xfac = as_dp(xfac) if xfac is not None else None
-        desc.yfac = as_dp(yfac)
-        keep = [xfac, yfac]
-        if mass is not None:
-            mt, mx, my = mass.factor_blocks()
-            desc.m_nterms = mt
-            desc.m_xfac = as_dp(mx) if mx is not None else None
-            desc.m_yfac = as_dp(my)
-            keep += [mx, my]
-        desc.nvec, desc.device = self.nvec, device
-        desc.row_begin, desc.row_end, desc.strip_levels = row_begin, row_end, strip_levels
-        ps = getattr(op, "point_stencil", None)
-        pd = getattr(op, "point_diagonal", None)
-        if ps is not None:
-            # a per-point 9-point stencil (operators.tensor_mass_operator): level 0 is a nine-plane level like the Galerkin
-            # levels below it; such plans are whole 2-D grids without a mass operator
+            desc, keep = self._desc3d(op, mass, sharded)
+        else:
+            nterms, xfac, yfac = op.factor_blocks()
+            desc = PlanDesc()
+            desc.dim, desc.nterms, desc.g, desc.lowest = self.dim, nterms, self.g, self.lowest
+            desc.xfac = as_dp(xfac) if xfac is not None else None
+            desc.yfac = as_dp(yfac)
+            keep = [xfac, yfac]
             if mass is not None:
-                raise ValueError("an operator with a point stencil takes no mass operator: the Rayleigh-quotient routines (rqmin, "
-                                 "vcycle_rqmg, ...) do not run on it; vcycle / vcycle_matrix / fmg, the smoothers wjacobi and "
-                                 "gseidel_rb, apply and drivers.block_eigensolve do")
-            if row_begin or row_end or strip_levels:
-                raise ValueError("an operator with a point stencil is not sharded")
-            ps = _f64(ps)
-            check(_lib.lib().mgcmt_plan_create_nine(ctypes.byref(desc), as_dp(ps), ctypes.byref(self._h)))
-        elif pd is not None:
-            # an arbitrary potential on the diagonal (operators.potential_operator): the per-point hierarchy R D P is built
-            # at creation; such plans are whole 2-D grids without a mass operator
-            if mass is not None:
-                raise ValueError("an operator with a point diagonal takes no mass operator: the Rayleigh-quotient routines (rqmin, "
-                                 "vcycle_rqmg, ...) do not run on it; vcycle / vcycle_matrix / fmg, the smoothers wjacobi and "
-                                 "gseidel_rb, apply and drivers.block_eigensolve do")
-            if row_begin or row_end or strip_levels:
-                raise ValueError("an operator with a point diagonal is not sharded")
-            pd = _f64(pd)
-            bonds = getattr(op, "point_bonds", None)
-            if bonds is not None:
-                # per-point bonds as well (operators.variable_mass_operator): level 0 keeps the planes D, E, S
-                east, south = _f64(bonds[0]), _f64(bonds[1])
-                check(_lib.lib().mgcmt_plan_create_bonds(ctypes.byref(desc), as_dp(pd), as_dp(east), as_dp(south), ctypes.byref(self._h)))
-            else:
-                check(_lib.lib().mgcmt_plan_create_pot(ctypes.byref(desc), as_dp(pd), ctypes.byref(self._h)))
+                mt, mx, my = mass.factor_blocks()
+                desc.m_nterms = mt
+                desc.m_xfac = as_dp(mx) if mx is not None else None
+                desc.m_yfac = as_dp(my)
+                keep += [mx, my]
+            desc.nvec, desc.device = self.nvec, device
+            desc.row_begin, desc.row_end, desc.strip_levels = row_begin, row_end, strip_levels
+        if kind is not None:
+            # the per-point hierarchy (level 0: the operator's planes, below it R (.) P) is built at creation
+            arrays = [_f64(a) for a in arrays]
+            create = getattr(_lib.lib(), _POINT_CREATORS[self.dim, kind])
+            check(create(ctypes.byref(desc), *[as_dp(a) for a in arrays], ctypes.byref(self._h)))
+        elif self.dim == 3 and mass is not None:
+            mt, mz, my, mx = mass.factor_blocks()
+            check(_lib.lib().mgcmt_plan_create3d_mass(ctypes.byref(desc), mt, as_dp(mz), as_dp(my), as_dp(mx), ctypes.byref(self._h)))
+        elif self.dim == 3:
+            check(_lib.lib().mgcmt_plan_create3d(ctypes.byref(desc), ctypes.byref(self._h)))
         else:
             check(_lib.lib().mgcmt_plan_create(ctypes.byref(desc), ctypes.byref(self._h)))
         del keep
@@ -83,14 +74,23 @@ class Plan:
         self.shapes = [self.level_shape(l) for l in range(self.num_levels)]
         self._shifts = None
 
-    def _create3d(self, op, mass, row_begin, row_end, strip_levels):
+    def _point_refusal(self, kind, mass):
+        """The error of a plan whose operator has a per-point part and that is given a mass operator (`mass`) or a row strip:
+        such plans are whole grids without a mass operator."""
+        subject = "%s operator with %s" % ("a 3-D" if self.dim == 3 else "an", _POINT_NAMES[kind])
+        if not mass:
+            return ValueError(subject + " is not sharded")
+        return ValueError("%s takes no mass operator: the Rayleigh-quotient routines (rqmin, vcycle_rqmg, ...) do not run on it; vcycle / "
+                          "vcycle_matrix%s, the smoothers wjacobi and gseidel_rb, apply and drivers.block_eigensolve do"
+                          % (subject, "" if self.dim == 3 else " / fmg"))
+
+    def _desc3d(self, op, mass, sharded):
+        """the description of a 3-D plan and the arrays it points at"""
         if mass is not None and (mass.dimension != "3d" or mass.g != op.g):
             raise ValueError("the mass operator of a 3-D plan must be a 3-D operator on the same %d^3 grid" % op.g)
         if mass is not None and not 1 <= len(mass.terms) <= _lib.MAX_TERMS:
             raise ValueError("a 3-D mass operator has 1 .. %d Kronecker terms, not %d" % (_lib.MAX_TERMS, len(mass.terms)))
-        if (row_begin or row_end or strip_levels) and getattr(op, "point_stencil", None) is not None:
-            raise ValueError("an operator with a point stencil is not sharded")
-        if row_begin or row_end or strip_levels:
+        if sharded:
             raise ValueError("3-D plans are not sharded")
         if self.lowest > 16:
             raise ValueError("lowest_level=%d: the coarsest 3-D level is solved directly and may be at most 16^3" % self.lowest)
@@ -99,41 +99,7 @@ class Plan:
         desc.nterms, desc.nvec, desc.g, desc.lowest = nterms, self.nvec, self.g, self.lowest
         desc.zfac, desc.yfac, desc.xfac = as_dp(zfac), as_dp(yfac), as_dp(xfac)
         desc.device = self.device
-        pd = getattr(op, "point_diagonal", None)
-        ps = getattr(op, "point_stencil", None)
-        if ps is not None:
-            # a per-point 27-point stencil (operators.tensor_mass_operator(..., dimension="3d")): level 0 is a 27-plane level like
-            # the Galerkin levels below it
-            if mass is not None:
-                raise ValueError("a 3-D operator with a point stencil (a point diagonal and more) takes no mass operator: the "
-                                 "Rayleigh-quotient routines (rqmin, vcycle_rqmg, ...) do not run on it; vcycle / vcycle_matrix, the "
-                                 "smoothers wjacobi and gseidel_rb, apply and drivers.block_eigensolve do")
-            ps = _f64(ps)
-            check(_lib.lib().mgcmt_plan_create3d_stencil(ctypes.byref(desc), as_dp(ps), ctypes.byref(self._h)))
-        elif pd is not None:
-            # an arbitrary potential V(x, y, z) on the diagonal: the per-point hierarchy R D P (27 planes per level) is built at creation
-            if mass is not None:
-                raise ValueError("a 3-D operator with a point diagonal%s takes no mass operator: the Rayleigh-quotient routines (rqmin, "
-                                 "vcycle_rqmg, ...) do not run on it; vcycle / vcycle_matrix, the smoothers wjacobi and gseidel_rb, "
-                                 "apply and drivers.block_eigensolve do" % (" and point bonds" if getattr(op, "point_bonds", None) is not None else ""))
-            pd = _f64(pd)
-            bonds = getattr(op, "point_bonds", None)
-            if bonds is not None:
-                # per-point bonds as well (operators.variable_mass_operator(..., dimension="3d")): level 0 keeps D, Bx, By, Bz
-                bx, by, bz = (_f64(b) for b in bonds)
-                check(_lib.lib().mgcmt_plan_create3d_bonds(ctypes.byref(desc), as_dp(pd), as_dp(bx), as_dp(by), as_dp(bz), ctypes.byref(self._h)))
-            else:
-                check(_lib.lib().mgcmt_plan_create3d_pot(ctypes.byref(desc), as_dp(pd), ctypes.byref(self._h)))
-        elif mass is None:
-            check(_lib.lib().mgcmt_plan_create3d(ctypes.byref(desc), ctypes.byref(self._h)))
-        else:
-            mt, mz, my, mx = mass.factor_blocks()
-            check(_lib.lib().mgcmt_plan_create3d_mass(ctypes.byref(desc), mt, as_dp(mz), as_dp(my), as_dp(mx), ctypes.byref(self._h)))
-        n = c_int(0)
-        check(_lib.lib().mgcmt_plan_num_levels(self._h, ctypes.byref(n)))
-        self.num_levels = n.value
-        self.shapes = [self.level_shape(l) for l in range(self.num_levels)]
-        self._shifts = None
+        return desc, [zfac, yfac, xfac]
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
@@ -173,17 +139,9 @@ class Plan:
         planes D, E, S, array [3, rows, cols]; of an operator with ``point_stencil``: [3, 3, rows, cols] like the levels below.  3-D: [g, g, g] on level 0 ([4, g, g, g] = D, Bx, By, Bz with bonds) and the 27-point stencil
         [3, 3, 3, g_l, g_l, g_l] below — entry [a, b, c, z, y, x] is the coefficient of point (z + a - 1, y + b - 1, x + c - 1); level 0 of
         a 3-D operator with ``point_stencil`` has that shape too."""
-        if self.dim == 3:
-            gl = self.g >> level
-            bonds = getattr(self.op, "point_bonds", None) is not None
-            planes = getattr(self.op, "point_stencil", None) is not None      # level 0 is a 27-plane level too
-            out = np.zeros(((4, gl, gl, gl) if bonds else (gl, gl, gl)) if level == 0 and not planes else (3, 3, 3, gl, gl, gl))
-            check(_lib.lib().mgcmt_plan_get_point_stencil(self._h, level, as_dp(out), out.size))
-            return out
-        r, c, _ = self.shapes[level]
-        bonds = getattr(self.op, "point_bonds", None) is not None
-        nine = getattr(self.op, "point_stencil", None) is not None      # level 0 is a nine-plane level too
-        out = np.zeros(((3, r, c) if bonds else (r, c)) if level == 0 and not nine else (3, 3, r, c))
+        kind = self.op.point_part()[0] if level == 0 else "planes"      # (below level 0: the Galerkin product's 3^dim planes)
+        lead = {"bonds": (self.dim + 1,), "planes": (3,) * self.dim}.get(kind, ())
+        out = np.zeros(lead + (self.g >> level,) * self.dim)
         check(_lib.lib().mgcmt_plan_get_point_stencil(self._h, level, as_dp(out), out.size))
         return out
 

@@ -83,7 +83,7 @@ def _recognise_entry(A, dimension):
 
 def _has_point(op):
     """The operator carries a per-point part: a point diagonal (with or without bonds) or a point stencil."""
-    return getattr(op, "point_diagonal", None) is not None or getattr(op, "point_stencil", None) is not None
+    return op.point_part()[0] is not None
 
 
 def _check_point_smoother(op, kind):
@@ -242,58 +242,20 @@ class MGCMTSolver:
     def _level_matrix(self, plan, level, shift):
         """(A_level - shift I) as the scipy.sparse matrix the reference hands to a smoother (:287-288,313); A_level is
         the Galerkin operator R*A*P of that level (:318), rebuilt from the plan's Kronecker factors."""
-        if plan.dim == 3:
-            fs = [plan.factors(level, w) for w in range(3)]
-            gl = plan.g >> level
-            terms = [tuple(f[m].copy() for f in fs) for m in range(fs[0].shape[0])]
-            if getattr(plan.op, "point_stencil", None) is not None and level == 0:
-                op = StructuredOperator("3d", gl, terms, point_stencil=plan.point_stencil(0))      # the factors plus the 27 planes
-                if shift:
-                    op = op.shifted(float(shift))
-                return tag_structured(op.tocsr(), op)
-            if _has_point(plan.op) and level > 0:
-                # the Kronecker part's level plus the 27 planes of R D P the library formed
-                n = gl ** 3
-                M = StructuredOperator("3d", gl, terms).tocsr() + planes_to_csr(plan.point_stencil(level))
-                if shift:
-                    M = M - float(shift) * sp.identity(n, format="csr")
-                return M.tocsr()
-            pd = plan.point_stencil(0) if getattr(plan.op, "point_diagonal", None) is not None else None
-            if pd is not None and getattr(plan.op, "point_bonds", None) is not None:
-                op = StructuredOperator("3d", gl, terms, point_diagonal=pd[0], point_bonds=(pd[1], pd[2], pd[3]))      # D, Bx, By, Bz
-            else:
-                op = StructuredOperator("3d", gl, terms, point_diagonal=pd)
+        # the factor arrays per axis as a term lists them: (X, Y, Z), (X, Y) or (None, Y)
+        fs = [plan.factors(level, w) if plan.dim > 1 or w == 1 else None for w in range(max(plan.dim, 2))]
+        terms = [tuple(None if f is None else f[m].copy() for f in fs) for m in range(fs[-1].shape[0])]
+        dimension, gl = "%dd" % plan.dim, plan.g >> level
+        kind = plan.op.point_part()[0]
+        if kind is not None and level > 0:
+            # the Kronecker part's level plus the 3^dim planes of R D P the library formed (a foreign smoother sees the true R A P - mu I)
+            M = StructuredOperator(dimension, gl, terms).tocsr() + planes_to_csr(plan.point_stencil(level))
             if shift:
-                op = op.shifted(float(shift))
-            return tag_structured(op.tocsr(), op)
-        xf = plan.factors(level, 0) if plan.dim == 2 else None
-        yf = plan.factors(level, 1)
-        terms = [((xf[m].copy() if xf is not None else None), yf[m].copy()) for m in range(yf.shape[0])]
-        if getattr(plan.op, "point_stencil", None) is not None and level == 0:
-            op = StructuredOperator("2d", plan.g, terms, point_stencil=plan.point_stencil(0))      # the factors plus the nine planes
-            if shift:
-                op = op.shifted(float(shift))
-            return tag_structured(op.tocsr(), op)
-        if _has_point(plan.op):
-            # the Kronecker part's level plus the per-point part the library formed: the diagonal on level 0, the 9-point
-            # stencil R D P below (a foreign smoother sees the true R A P - mu I)
-            gl = plan.g >> level
-            if level == 0 and getattr(plan.op, "point_bonds", None) is not None:
-                G = plan.point_stencil(0)                      # D, E, S: the true matrix with its bonds
-                op = StructuredOperator("2d", gl, terms, point_diagonal=G[0], point_bonds=(G[1], G[2]))
-                if shift:
-                    op = op.shifted(float(shift))
-                return tag_structured(op.tocsr(), op)
-            if level == 0:
-                op = StructuredOperator("2d", gl, terms, point_diagonal=plan.point_stencil(0))
-                if shift:
-                    op = op.shifted(float(shift))
-                return tag_structured(op.tocsr(), op)
-            M = StructuredOperator("2d", gl, terms).tocsr() + planes_to_csr(plan.point_stencil(level))
-            if shift:
-                M = M - float(shift) * sp.identity(gl * gl, format="csr")
+                M = M - float(shift) * sp.identity(gl ** plan.dim, format="csr")
             return M.tocsr()
-        op = StructuredOperator("2d" if plan.dim == 2 else "1d", plan.g >> level, terms)
+        # level 0 of a plan with a per-point part: the factors plus the planes the plan holds (a diagonal; D and the bonds; a stencil)
+        point = StructuredOperator.point_keywords(kind, plan.point_stencil(0)) if kind is not None else {}
+        op = StructuredOperator(dimension, gl, terms, **point)
         if shift:
             op = op.shifted(float(shift))
         return tag_structured(op.tocsr(), op)      # this class's own smoothers map it straight back (9-point levels too)

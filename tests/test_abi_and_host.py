@@ -234,3 +234,49 @@ def test_result_arrays_recycle_their_page_locked_buffers(backend, monkeypatch):
     lib = _lib.lib()
     assert lib.mgcmt_host_free(ctypes.c_void_p(12345)) != 0                  # not one of ours
     assert lib.mgcmt_host_alloc(0, ctypes.byref(ctypes.c_void_p())) != 0
+
+
+def _point_families():
+    """(name, axes, operator, the planes of level 0 as the plan documents them, what level 0 reports) for the six kinds of
+    per-point part: 8^2 points down to 2^2 and 4^3 down to 2^3, the smallest grids with a level 0, a Galerkin level and a coarsest one."""
+    from multigridcmt_amd.operators import potential_operator, tensor_mass_operator, variable_mass_operator
+    r = np.random.RandomState(3)
+    for dim, g in ((2, 8), (3, 4)):
+        shape, dimension = (g,) * dim, "%dd" % dim
+        u = lambda: r.rand(*shape)
+        pot = potential_operator(g, 3.0 * u(), dimension=dimension)
+        bonds = variable_mass_operator(g, 1.0 + 0.5 * u(), V=u(), dimension=dimension)
+        more = {} if dim == 2 else dict(wzz=1.0 + 0.5 * u(), wxz=0.3 * (u() - 0.5), wyz=0.3 * (u() - 0.5))
+        planes = tensor_mass_operator(g, 1.0 + 0.5 * u(), 1.0 + 0.5 * u(), 0.3 * (u() - 0.5), V=u(), dimension=dimension, **more)
+        reports = ((_lib.OPK_POINT_DIAG, _lib.OPK_POINT_BONDS, _lib.OPK_NINE_POINT) if dim == 2 else
+                   ((_lib.PATH3D_SEVEN_POINT, False), (_lib.PATH3D_SEVEN_BONDS, False), (_lib.PATH3D_SEVEN_PLANES, False)))
+        yield "%s diagonal" % dimension, dim, pot, pot.point_diagonal, reports[0]
+        yield "%s bonds" % dimension, dim, bonds, np.stack((bonds.point_diagonal,) + bonds.point_bonds), reports[1]
+        yield "%s stencil" % dimension, dim, planes, planes.point_stencil, reports[2]
+
+
+def test_point_part_round_trip_of_every_family(backend):
+    """Level 0 of a plan with a per-point part holds the caller's planes bit for bit — [g..] for a diagonal, [dim + 1, g..] = D and
+    the bonds from the fastest axis on, [3.., g..] for a stencil —, the level below the 3^dim planes of the Galerkin product; a buffer
+    one number short is refused; level 0 reports its kind."""
+    from multigridcmt_amd.plan import Plan
+    lib = _lib.lib()
+    for name, dim, op, want, reports in _point_families():
+        g = op.g
+        assert want.shape[-dim:] == (g,) * dim and want.shape[:-dim] in ((), (dim + 1,), (3,) * dim), name
+        plan = Plan(op, 2)
+        try:
+            assert plan.num_levels == (3 if dim == 2 else 2), name
+            got = plan.point_stencil(0)
+            assert got.shape == want.shape and got.tobytes() == np.ascontiguousarray(want).tobytes(), name
+            below = plan.point_stencil(1)
+            assert below.shape == (3,) * dim + (g // 2,) * dim and np.isfinite(below).all() and below.any(), name
+            for level, full in ((0, got), (1, below)):
+                buf = np.zeros(full.size)
+                assert lib.mgcmt_plan_get_point_stencil(plan._h, level, _lib.as_dp(buf), buf.size - 1) == -1, (name, level)   # MGCMT_ERR_INVALID
+                assert not buf.any(), (name, level)
+                assert lib.mgcmt_plan_get_point_stencil(plan._h, level, _lib.as_dp(buf), buf.size) == 0, (name, level)
+                assert buf.tobytes() == full.tobytes(), (name, level)
+            assert (plan.operator_kind(0) if dim == 2 else plan.level_path_3d(0)) == reports, name
+        finally:
+            plan.close()

@@ -58,6 +58,7 @@ extern "C" {
                                     only columns 0..31 have a shift (mgcmt_apply with_shift) */
 #define MGCMT_BLOCK_WIDE_MAX 48  /* vectors of mgcmt_block_pencil, inputs of mgcmt_block_combine_wide */
 #define MGCMT_BLOCK_WIDE_OUT 16  /* outputs of mgcmt_block_combine_wide */
+#define MGCMT_BLOCK_LOCKED_MAX 64 /* vectors Q of mgcmt_block_deflate */
 #define MGCMT_HALO_ROWS 16 /* rows of halo kept above and below every vector of a 2-D level (a 1-D level keeps one: its
                               "row" is the whole vector); how many of them a sharded cycle fills: mgcmt_plan_level_halo */
 
@@ -475,6 +476,12 @@ int mgcmt_block_pencil(mgcmt_plan* plan, int level, int m, const int* s_slots, c
                        const int* ms_slots, const int* ms_vecs, double* h_out, double* g_out, void* stream);
 int mgcmt_block_combine_wide(mgcmt_plan* plan, int level, int nin, const int* in_slots, const int* in_vecs, int nout, const int* out_slots,
                              const int* out_vecs, const double* coeffs, void* stream);
+/* W_j <- W_j - sum_i <Q_i, W_j> Q_i   for 1 <= nq <= 64 vectors Q and 1 <= k <= MGCMT_BLOCK_WIDE_OUT distinct vectors W,
+ * none of them a Q.  Two stream-ordered passes; the coefficients stay on the device.  coeffs_out (may be NULL): the nq x k
+ * coefficients row-major; non-NULL synchronises.  Bit-reproducible from call to call.  Scratch and stream rule: those of
+ * the wide entries.  Writes the k vectors W and nothing else. */
+int mgcmt_block_deflate(mgcmt_plan* plan, int level, int nq, const int* q_slots, const int* q_vecs, int k,
+                        const int* w_slots, const int* w_vecs, double* coeffs_out, void* stream);
 /* in-place Gram-Schmidt of vectors 0..k-1 of `slot`: modified != 0 -> MGS (:44-50), else CGS (:34-42) */
 int mgcmt_gramschmidt(mgcmt_plan* plan, int level, int slot, int k, int modified, void* stream);
 /* columns scaled to unit 2-norm (normalize, :52-63) */

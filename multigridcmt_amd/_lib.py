@@ -149,6 +149,8 @@ _SIGNATURES = {
     "mgcmt_block_pencil": (c_int, [c_void_p, c_int, c_int] + [POINTER(c_int)] * 6 + [POINTER(c_double), POINTER(c_double), c_void_p]),
     "mgcmt_block_combine_wide": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int), POINTER(c_int),
                                          POINTER(c_double), c_void_p]),
+    "mgcmt_block_deflate": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int), POINTER(c_int),
+                                    POINTER(c_double), c_void_p]),
     "mgcmt_gramschmidt": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mgcmt_normalize": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "mgcmt_level_operator_kind": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int)]),

@@ -215,6 +215,103 @@ __global__ void __launch_bounds__(kWideThreads) k_block_combine_wide(long n2, co
   }
 }
 
+// Deflation W_j <- W_j - sum_i <Q_i, W_j> Q_i against up to 64 locked vectors Q (drivers.deflated_eigensolve; DESIGN.md
+// par. 4.21) in two launches.  The 64 + 16 pointers travel as kernel arguments (640 bytes): no table is staged.
+struct DeflateArgs {
+  const double* q[kBlockLockedMax];
+  double* w[kBlockWideOut];
+};
+
+// Pass 1: C = Q^T W, TQ x 1 tiles of the pencil's products — A[i][k] = Q_(16 I + i)(p + k), B[k][j] = W_j(p + k) — with the
+// pencil's lane <-> element map, runs, prefetch, trips and sums.  The partial tile of block b and tile I is
+// partials[(I * gridDim.x + b) * 256 + row * 16 + col]; k_pencil_final leaves C row-major, 16 columns per Q.
+template <int TQ>
+__global__ void __launch_bounds__(kWideThreads) k_block_cross(long n, DeflateArgs g, int nq, int k, double* __restrict__ partials) {
+  __shared__ double s_red[kWideWaves - 1][kTileWords];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, kg = lane >> 4;
+  const double *pq[TQ], *pw = col < k ? g.w[col] : nullptr;
+#pragma unroll
+  for (int t = 0; t < TQ; ++t) pq[t] = kTile * t + col < nq ? g.q[kTile * t + col] : nullptr;
+  double acc[TQ][4];
+#pragma unroll
+  for (int t = 0; t < TQ; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[t][r] = 0.0;
+
+  const long nsteps = (n + kStepPoints - 1) / kStepPoints;
+  const long lane_off = (long)(wave * 4 + kg) * kRun;
+  double xq[TQ][kRun], xw[kRun], yq[TQ][kRun], yw[kRun];
+  long step = blockIdx.x;  // (every wave of a block takes the same trips: the emulation's shuffles need whole workgroups)
+  if (step < nsteps) {
+#pragma unroll
+    for (int t = 0; t < TQ; ++t) load_run(pq[t], step * kStepPoints + lane_off, n, xq[t]);
+    load_run(pw, step * kStepPoints + lane_off, n, xw);
+  }
+  for (; step < nsteps; step += gridDim.x) {
+    const long next = step + gridDim.x;
+    if (next < nsteps) {  // the next step's operands are in flight while this step's products run
+#pragma unroll
+      for (int t = 0; t < TQ; ++t) load_run(pq[t], next * kStepPoints + lane_off, n, yq[t]);
+      load_run(pw, next * kStepPoints + lane_off, n, yw);
+    }
+#pragma unroll
+    for (int q = 0; q < kRun; ++q)
+#pragma unroll
+      for (int t = 0; t < TQ; ++t) mfma_f64_16x16x4(xq[t][q], xw[q], acc[t]);
+    if (next < nsteps) {
+#pragma unroll
+      for (int q = 0; q < kRun; ++q) {
+#pragma unroll
+        for (int t = 0; t < TQ; ++t) xq[t][q] = yq[t][q];
+        xw[q] = yw[q];
+      }
+    }
+  }
+
+  // waves 1..3 hand their tile to wave 0 through LDS, one tile at a time; wave 0 adds them in wave order
+#pragma unroll
+  for (int t = 0; t < TQ; ++t) {
+    if (wave > 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s_red[wave - 1][r * 64 + lane] = acc[t][r];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double tot = acc[t][r];
+        for (int w = 0; w < kWideWaves - 1; ++w) tot += s_red[w][r * 64 + lane];
+        partials[((long)t * gridDim.x + blockIdx.x) * kTileWords + (kg + 4 * r) * kTile + col] = tot;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Pass 2: W_j <- W_j - sum_i c[i][j] Q_i on the vector ALUs, as k_block_combine_wide: a thread owns two points, the
+// accumulators start as W_j, the coefficient rows c[i][0..15] (the summed tiles of pass 1, zero beyond k) and the pointers are
+// wave-uniform and come through the scalar cache.  Columns j >= k are neither read nor stored.
+__global__ void __launch_bounds__(kWideThreads) k_block_deflate(long n2, DeflateArgs g, int nq, int k, const double* __restrict__ coef) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x) {
+    double2 acc[kBlockWideOut];
+#pragma unroll
+    for (int j = 0; j < kBlockWideOut; ++j) acc[j] = j < k ? reinterpret_cast<const double2*>(g.w[j])[i] : make_double2(0.0, 0.0);
+#pragma unroll 4
+    for (int t = 0; t < nq; ++t) {
+      const double* c = coef + t * kBlockWideOut;
+      const double2 x = reinterpret_cast<const double2*>(g.q[t])[i];
+#pragma unroll
+      for (int j = 0; j < kBlockWideOut; ++j) {
+        acc[j].x = fma(-c[j], x.x, acc[j].x);
+        acc[j].y = fma(-c[j], x.y, acc[j].y);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kBlockWideOut; ++j)
+      if (j < k) reinterpret_cast<double2*>(g.w[j])[i] = acc[j];
+  }
+}
+
 }  // namespace
 
 int block_pencil_blocks(long n) {
@@ -288,6 +385,36 @@ bool launch_block_combine_wide(hipStream_t s, long n, const double* const* in, i
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(k_block_combine_wide, dim3((unsigned)blocks), dim3(kWideThreads), 0, s, n2, table, nin, nout);
+  return true;
+}
+
+// w_j <- w_j - sum_i <q_i, w_j> q_i for nq <= 64 vectors q and k <= 16 distinct vectors w, none of them a q.  `partials` holds
+// ceil(nq / 16) * block_pencil_blocks(n) * 256 doubles; `out` (ceil(nq / 16) * 256 doubles) is left holding the coefficients
+// <q_i, w_j> at out[i * 16 + j].  false (nothing launched): n is odd or a vector is not 16-byte aligned
+bool launch_block_deflate(hipStream_t s, long n, int nq, const double* const* q, int k, double* const* w, double* partials, double* out) {
+  DeflateArgs g{};
+  uintptr_t bits = (uintptr_t)(n & 1);
+  for (int t = 0; t < kBlockLockedMax; ++t) {
+    g.q[t] = q[t < nq ? t : 0];
+    if (t < nq) bits |= reinterpret_cast<uintptr_t>(q[t]) & 15;
+  }
+  for (int j = 0; j < kBlockWideOut; ++j) {
+    g.w[j] = w[j < k ? j : 0];
+    if (j < k) bits |= reinterpret_cast<uintptr_t>(w[j]) & 15;
+  }
+  if (bits != 0) return false;
+  const int nb = block_pencil_blocks(n), tiles = (nq + kTile - 1) / kTile;
+  const dim3 grid(nb), block(kWideThreads);
+  if (tiles == 1) hipLaunchKernelGGL((k_block_cross<1>), grid, block, 0, s, n, g, nq, k, partials);
+  else if (tiles == 2) hipLaunchKernelGGL((k_block_cross<2>), grid, block, 0, s, n, g, nq, k, partials);
+  else if (tiles == 3) hipLaunchKernelGGL((k_block_cross<3>), grid, block, 0, s, n, g, nq, k, partials);
+  else hipLaunchKernelGGL((k_block_cross<4>), grid, block, 0, s, n, g, nq, k, partials);
+  hipLaunchKernelGGL(k_pencil_final, dim3(tiles), dim3(kTileWords), 0, s, nb, partials, out);
+  const long n2 = n / 2;
+  long blocks = (n2 + kWideThreads - 1) / kWideThreads;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_block_deflate, dim3((unsigned)blocks), dim3(kWideThreads), 0, s, n2, g, nq, k, out);
   return true;
 }
 

@@ -238,6 +238,8 @@ bool launch_block_pencil(hipStream_t s, long n, int m, const double* const* sv, 
                          double* out);
 bool launch_block_combine_wide(hipStream_t s, long n, const double* const* in, int nin, double* const* out, int nout, const double* c,
                                unsigned long long* table);
+constexpr int kBlockLockedMax = MGCMT_BLOCK_LOCKED_MAX;  // vectors a block is deflated against (mgcmt_block_deflate)
+bool launch_block_deflate(hipStream_t s, long n, int nq, const double* const* q, int k, double* const* w, double* partials, double* out);
 void launch_gram(hipStream_t s, long n, const double* const* v, int nv, double* partials, double* out);
 void launch_lincomb(hipStream_t s, long n, const double* const* v, const double* c, int nt, double* dst);
 bool mgs_small_fits(long n);

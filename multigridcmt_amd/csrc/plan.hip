@@ -320,6 +320,21 @@ static int wide_vectors(mgcmt_plan* p, int l, int count, const int* slots, const
   return MGCMT_OK;
 }
 
+// the scratch of the entries that sum tiles: room for `need` doubles of per-workgroup partial tiles, and the summed tiles
+static int wide_scratch(mgcmt_plan* p, size_t need, hipStream_t stream) {
+  if (need > p->wide_partials_doubles) {
+    MG_HIP(hipStreamSynchronize(stream));  // (an earlier pencil on this stream may still read the old buffer)
+    if (p->d_wide_partials) (void)hipFree(p->d_wide_partials);
+    p->d_wide_partials = nullptr;
+    p->wide_partials_doubles = 0;
+    MG_HIP(hipMalloc((void**)&p->d_wide_partials, sizeof(double) * need));
+    p->wide_partials_doubles = need;
+  }
+  constexpr int kMaxTiles = 2 * 3 * 3;  // (the pencil of 48 vectors with a mass operator; a deflation sums four)
+  if (!p->d_wide_out) MG_HIP(hipMalloc((void**)&p->d_wide_out, sizeof(double) * kMaxTiles * 256));
+  return MGCMT_OK;
+}
+
 int mgcmt_block_pencil(mgcmt_plan* p, int l, int m, const int* s_slots, const int* s_vecs, const int* as_slots, const int* as_vecs,
                        const int* ms_slots, const int* ms_vecs, double* h_out, double* g_out, void* stream) {
   MG_TRY(check_level(p, l));
@@ -332,17 +347,7 @@ int mgcmt_block_pencil(mgcmt_plan* p, int l, int m, const int* s_slots, const in
   if (mass) MG_TRY(wide_vectors(p, l, m, ms_slots, ms_vecs, ms));
   const long n = p->interior(l);
   const int tiles = block_pencil_tiles(m, mass), side = (m + 15) / 16;
-  const size_t need = (size_t)tiles * block_pencil_blocks(n) * 256;
-  if (need > p->wide_partials_doubles) {
-    MG_HIP(hipStreamSynchronize(S(stream)));  // (an earlier pencil on this stream may still read the old buffer)
-    if (p->d_wide_partials) (void)hipFree(p->d_wide_partials);
-    p->d_wide_partials = nullptr;
-    p->wide_partials_doubles = 0;
-    MG_HIP(hipMalloc((void**)&p->d_wide_partials, sizeof(double) * need));
-    p->wide_partials_doubles = need;
-  }
-  constexpr int kMaxTiles = 2 * 3 * 3;
-  if (!p->d_wide_out) MG_HIP(hipMalloc((void**)&p->d_wide_out, sizeof(double) * kMaxTiles * 256));
+  MG_TRY(wide_scratch(p, (size_t)tiles * block_pencil_blocks(n) * 256, S(stream)));
   if (!launch_block_pencil(S(stream), n, m, sv, as, mass ? ms : nullptr, p->d_wide_partials, p->d_wide_out))
     return fail(MGCMT_ERR_INVALID, "block_pencil: a vector is not 16-byte aligned");
   MG_TRY(post_launch());
@@ -382,6 +387,37 @@ int mgcmt_block_combine_wide(mgcmt_plan* p, int l, int nin, const int* in_slots,
   if (!launch_block_combine_wide(S(stream), p->interior(l), in, nin, out, nout, coeffs, p->d_wide_table))
     return fail(MGCMT_ERR_INVALID, "block_combine_wide: an odd number of points or a vector that is not 16-byte aligned");
   return post_launch();
+}
+
+int mgcmt_block_deflate(mgcmt_plan* p, int l, int nq, const int* q_slots, const int* q_vecs, int k, const int* w_slots, const int* w_vecs,
+                        double* coeffs_out, void* stream) {
+  MG_TRY(check_level(p, l));
+  if (nq < 1 || nq > kBlockLockedMax || k < 1 || k > kBlockWideOut)
+    return fail(MGCMT_ERR_INVALID, "block_deflate: 1..64 vectors Q, 1..16 vectors W");
+  if (!q_slots || !q_vecs || !w_slots || !w_vecs) return fail(MGCMT_ERR_INVALID, "block_deflate: non-null vector lists");
+  double *q[kBlockLockedMax], *w[kBlockWideOut];
+  MG_TRY(wide_vectors(p, l, nq, q_slots, q_vecs, q));
+  MG_TRY(wide_vectors(p, l, k, w_slots, w_vecs, w));
+  for (int j = 0; j < k; ++j) {
+    for (int i = 0; i < j; ++i)
+      if (w[i] == w[j]) return fail(MGCMT_ERR_INVALID, "block_deflate: a vector W named twice");
+    for (int i = 0; i < nq; ++i)
+      if (q[i] == w[j]) return fail(MGCMT_ERR_INVALID, "block_deflate: a vector W that is also a Q");
+  }
+  const long n = p->interior(l);
+  const int tiles = (nq + 15) / 16;
+  MG_TRY(wide_scratch(p, (size_t)tiles * block_pencil_blocks(n) * 256, S(stream)));
+  if (!launch_block_deflate(S(stream), n, nq, q, k, w, p->d_wide_partials, p->d_wide_out))
+    return fail(MGCMT_ERR_INVALID, "block_deflate: an odd number of points or a vector that is not 16-byte aligned");
+  MG_TRY(post_launch());
+  if (coeffs_out) {
+    std::vector<double> packed((size_t)nq * kBlockWideOut);
+    MG_HIP(hipMemcpyAsync(packed.data(), p->d_wide_out, sizeof(double) * packed.size(), hipMemcpyDeviceToHost, S(stream)));
+    MG_HIP(hipStreamSynchronize(S(stream)));
+    for (int i = 0; i < nq; ++i)
+      for (int j = 0; j < k; ++j) coeffs_out[i * k + j] = packed[(size_t)i * kBlockWideOut + j];
+  }
+  return MGCMT_OK;
 }
 
 int mgcmt_axpy(mgcmt_plan* p, int l, double alpha, int x_slot, int x_vec, int y_slot, int y_vec, void* stream) {

@@ -409,3 +409,149 @@ def block_eigensolve(op, k=4, cycles=12, nu=2, lowest=8, smoother="rb", seed=0, 
         stats["loop_seconds"] = time.perf_counter() - loop_start
     vecs = np.stack([np.asarray(plan.download(0, W, j)) for j in range(k)], axis=1)
     return np.array(rho), vecs
+
+
+DEFLATED_EIGENSOLVE_MAX = 64   # states of deflated_eigensolve: the vectors Q of mgcmt_block_deflate
+
+
+def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, nu=2, lowest=8, smoother="rb", seed=0,
+                        guesses=None, info=None, mass=None):
+    """The k lowest eigenpairs of a structured 2-D or 3-D operator, 1 <= k <= 64, solved TO A TOLERANCE: block_eigensolve's
+    iteration (LOBPCG with a V-cycle preconditioner) with hard locking.  A Ritz pair whose residual meets the tolerance —
+    ||A x - rho x|| <= max(atol, rtol |rho|) — is locked: it leaves the active block for a store of its own, a fresh random
+    vector takes its place, and every preconditioned residual is projected against all locked vectors (one
+    mgcmt_block_deflate call per iteration, after the cycle and before A is applied) ahead of Rayleigh-Ritz.  Only a
+    contiguous prefix of converged pairs is locked, lowest first, and never more than are still wanted.
+
+    The active block holds kb = ``block`` vectors (default min(16, k + 4)) from the first iteration to the last, so the last
+    wanted states have guard vectors behind them; it always goes through the wide entries (mgcmt_block_pencil,
+    mgcmt_block_combine_wide).  On a lock P is dropped for the next iteration, the fresh vectors — drawn in order from
+    np.random.RandomState(seed), uploaded, deflated once, A applied — go to the freed places and Rayleigh-Ritz runs over X
+    again.  A fresh vector is a host upload of n doubles: a run of k states uploads about k + kb of them.
+
+    Memory: ONE plan with nvec = 3 kb + ceil(k / 2) <= 80 vectors per slot, the active ones where block_eigensolve keeps them
+    (X, AX, P in slot W; R, AP, AW in slot F; the cycle's output in V), the locked ones in the columns from 3 kb on of slots
+    W and F only (a cycle exchanges the V / T storage of a level: nothing that must survive lives there).  All four slots
+    have nvec columns on every level: 4 x nvec x 8 B x n x 4/3 in 2-D (x 8/7 in 3-D) — 80 columns at 2048^2 are 14.3 GB.
+
+    ``mass`` is refused (the projection would need M Q next to Q); ``smoother``: "rb" or "wjacobi".  Returns
+    (eigenvalues[k] ascending, eigenvectors[n, k]).  ``info`` (a dict) receives iterations, status ("converged" or
+    "maxiter"), locked_at (the iteration at which each state was locked; -1: not locked), residuals (the final norm per
+    state) and column_cycles (active columns summed over the iterations).  With status "maxiter" the states that were not
+    locked are returned as they stand — as many as the active block holds: min(k, locked + kb) columns in all.
+
+    Known limit (DESIGN.md par. 4.21): 40 states of the 1024^2 and 2048^2 boxes stall on the MI355X once 28 are locked — the
+    Gram matrix of the scaled [X, W, P] loses rank to working accuracy (smallest eigenvalue 1e-12 and below), the Ritz vectors
+    then carry errors of 1e-4 and no residual reaches 1e-8 |rho| again; status is "maxiter".  24 states converge there (34
+    iterations at 1024^2, 36 at 2048^2), 40 states converge at 64^2 and 64 at 32^2.  Check ``info["status"]``."""
+    from . import _lib
+    from .plan import get_plan
+    k = int(k)
+    if not 1 <= k <= DEFLATED_EIGENSOLVE_MAX:
+        raise ValueError("deflated_eigensolve handles 1..%d eigenpairs" % DEFLATED_EIGENSOLVE_MAX)
+    kb = min(BLOCK_EIGENSOLVE_MAX, k + 4) if block is None else int(block)
+    if not 1 <= kb <= BLOCK_EIGENSOLVE_MAX:
+        raise ValueError("deflated_eigensolve: an active block of 1..%d vectors" % BLOCK_EIGENSOLVE_MAX)
+    if mass is not None:
+        raise ValueError("deflated_eigensolve does not take a mass operator (the locked store would have to keep M Q next to Q)")
+    if smoother not in ("rb", "wjacobi"):
+        raise ValueError("deflated_eigensolve: smoother is 'rb' or 'wjacobi'")
+    kind, omega = (_lib.GS_MC, 1.0) if smoother == "rb" else (_lib.WJACOBI, 2. / 3.)
+    V, F, W = _lib.SLOT_V, _lib.SLOT_F, _lib.SLOT_W
+    plan = get_plan(op, int(lowest), nvec=3 * kb + (k + 1) // 2)
+    plan.set_shifts(np.zeros(min(plan.nvec, _lib.MAX_VEC)))
+    n = plan.size(0)
+    X = [(W, j) for j in range(kb)]
+    AX = [(W, kb + j) for j in range(kb)]
+    P = [(W, 2 * kb + j) for j in range(kb)]
+    R = [(F, j) for j in range(kb)]
+    AP = [(F, kb + j) for j in range(kb)]
+    AW = [(F, 2 * kb + j) for j in range(kb)]
+    Wd = [(V, j) for j in range(kb)]
+    Q = [((W, F)[i % 2], 3 * kb + i // 2) for i in range(k)]          # the locked store
+    rng = np.random.RandomState(seed)
+    given = 0 if guesses is None else min(kb, np.asarray(guesses).shape[1])
+    for j in range(kb):
+        plan.upload(0, W, j, np.asarray(guesses)[:, j] if j < given else rng.random_sample(n))
+        plan.apply(0, X[j], AX[j])
+
+    def ritz(S, AS):
+        """the kb lowest Ritz pairs over span S, orthogonal to the locked vectors by construction of S"""
+        H, G = plan.block_pencil(0, S, AS)
+        G, H = 0.5 * (G + G.T), 0.5 * (H + H.T)
+        d = 1.0 / np.sqrt(np.diag(G))                   # (scaling only: the pencil's eigenvectors are rescaled back)
+        evals, evecs = scipy.linalg.eigh(H * np.outer(d, d), G * np.outer(d, d), subset_by_index=[0, kb - 1])
+        return evals, evecs * d[:, None]
+
+    def ritz_over_x():
+        rho, C = ritz(X, AX)
+        plan.block_combine_wide(0, X, X, C)
+        plan.block_combine_wide(0, AX, AX, C)
+        return rho
+
+    vals, norms_locked, locked_at = [], [], []
+    iterations = column_cycles = 0
+
+    def residuals_and_locks(rho):
+        """R = A X - X diag(rho) and its norms; locks the converged prefix, refills the block and repeats while pairs lock.
+        Returns (rho, norms, whether anything was locked)."""
+        locked_any = False
+        while True:
+            for j in range(kb):
+                plan.lincomb(0, [(1.0, AX[j]), (-float(rho[j]), X[j])], R[j])
+            norms = np.sqrt(np.diag(plan.block_pencil(0, R, R)[0]))
+            ok = norms <= np.maximum(atol, rtol * np.abs(rho))
+            nlock = min(kb if ok.all() else int(np.argmin(ok)), k - len(vals))
+            if nlock == 0:
+                return rho, norms, locked_any
+            for j in range(nlock):
+                plan.copy(0, X[j][0], X[j][1], *Q[len(vals)])
+                vals.append(float(rho[j]))
+                norms_locked.append(float(norms[j]))
+                locked_at.append(iterations)
+            locked_any = True
+            if len(vals) == k:
+                return rho[nlock:], norms[nlock:], True
+            for j in range(nlock):
+                plan.upload(0, W, j, rng.random_sample(n))
+            plan.block_deflate(0, Q[:len(vals)], X[:nlock])
+            for j in range(nlock):
+                plan.apply(0, X[j], AX[j])
+            rho = ritz_over_x()
+
+    rho, norms, _ = residuals_and_locks(ritz_over_x())
+    have_p = False
+    while len(vals) < k and iterations < int(maxiter):
+        iterations += 1
+        column_cycles += kb
+        plan.vcycle(nu, nu, kind, omega=omega, k=kb, nu_coarse=nu, zero_start=True)
+        if vals:
+            plan.block_deflate(0, Q[:len(vals)], Wd)
+        for j in range(kb):
+            plan.apply(0, Wd[j], AW[j])
+        S, AS = (X + Wd + P, AX + AW + AP) if have_p else (X + Wd, AX + AW)
+        try:
+            rho, C = ritz(S, AS)
+        except (scipy.linalg.LinAlgError, ValueError):   # the directions have become dependent: restart without P
+            S, AS = X + Wd, AX + AW
+            rho, C = ritz(S, AS)
+        # P' = [W, P] C_wp, X' = X C_x + P' (and their images under A), as block_eigensolve
+        plan.block_combine_wide(0, S[kb:], P, C[kb:])
+        plan.block_combine_wide(0, AS[kb:], AP, C[kb:])
+        plan.block_combine_wide(0, X + P, X, np.vstack([C[:kb], np.eye(kb)]))
+        plan.block_combine_wide(0, AX + AP, AX, np.vstack([C[:kb], np.eye(kb)]))
+        rho, norms, locked_any = residuals_and_locks(rho)
+        have_p = not locked_any
+    plan.sync()
+    nlocked = len(vals)
+    rest = min(k - nlocked, kb)                          # (status "maxiter": the lowest active pairs as they stand)
+    where = Q[:nlocked] + X[:rest]
+    vals = np.array(vals + [float(r) for r in rho[:rest]])
+    norms = np.array(norms_locked + [float(r) for r in norms[:rest]])
+    locked_at = np.array(locked_at + [-1] * rest, dtype=np.int64)
+    order = np.argsort(vals, kind="stable")
+    vecs = np.stack([np.asarray(plan.download(0, *where[j])) for j in order], axis=1)
+    if info is not None:
+        info.update(iterations=iterations, status="converged" if nlocked == k else "maxiter", locked_at=locked_at[order],
+                    residuals=norms[order], column_cycles=column_cycles)
+    return vals[order], vecs

@@ -405,6 +405,17 @@ class Plan:
                                                   (ctypes.c_int * nout)(*[v[0] for v in outputs]),
                                                   (ctypes.c_int * nout)(*[v[1] for v in outputs]), _lib.as_dp(c), stream))
 
+    def block_deflate(self, level, q, w, want_coeffs=False, stream=None):
+        """w[j] <- w[j] - sum_i <q[i], w[j]> q[i] ((slot, vec) pairs; <= 64 vectors q, <= 16 distinct vectors w, none of them a
+        q): two stream-ordered passes, the coefficients staying on the device (mgcmt_block_deflate).  want_coeffs: returns the
+        len(q) x len(w) coefficients <q[i], w[j]> and synchronises."""
+        nq, k = len(q), len(w)
+        c = np.zeros((nq, k)) if want_coeffs else None
+        check(_lib.lib().mgcmt_block_deflate(self._h, level, nq, (ctypes.c_int * nq)(*[v[0] for v in q]), (ctypes.c_int * nq)(*[v[1] for v in q]),
+                                             k, (ctypes.c_int * k)(*[v[0] for v in w]), (ctypes.c_int * k)(*[v[1] for v in w]),
+                                             None if c is None else _lib.as_dp(c), stream))
+        return c
+
     def axpy(self, level, alpha, x, y, stream=None):
         check(_lib.lib().mgcmt_axpy(self._h, level, c_double(alpha), x[0], x[1], y[0], y[1], stream))
 

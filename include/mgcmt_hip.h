@@ -482,6 +482,29 @@ int mgcmt_block_combine_wide(mgcmt_plan* plan, int level, int nin, const int* in
  * the wide entries.  Writes the k vectors W and nothing else. */
 int mgcmt_block_deflate(mgcmt_plan* plan, int level, int nq, const int* q_slots, const int* q_vecs, int k,
                         const int* w_slots, const int* w_vecs, double* coeffs_out, void* stream);
+/* mgcmt_block_deflate with companions that take the same coefficients:
+ *     W_j  <- W_j  - sum_i <B_i, W_j> B_i
+ *     AW_j <- AW_j - sum_i <B_i, W_j> AB_i
+ * for 1 <= nb <= MGCMT_BLOCK_LOCKED_MAX vectors B and 1 <= k <= MGCMT_BLOCK_WIDE_OUT distinct vectors W (with B orthonormal
+ * and AB = A B, AW = A W on entry, AW = A W on return).  ab_slots, ab_vecs, aw_slots and aw_vecs all NULL: W only; given in
+ * part: MGCMT_ERR_INVALID, as are a W or an AW named twice, a W that is a B or an AB, an AW that is a B, an AB or a W.  Pass 1
+ * is the one of mgcmt_block_deflate, pass 2 runs once per pair on the same coefficients, which stay on the device; coeffs_out,
+ * reproducibility, scratch and stream rule as there.  Writes the k vectors W and the k vectors AW and nothing else. */
+int mgcmt_block_project(mgcmt_plan* plan, int level, int nb, const int* b_slots, const int* b_vecs, const int* ab_slots, const int* ab_vecs,
+                        int k, const int* w_slots, const int* w_vecs, const int* aw_slots, const int* aw_vecs, double* coeffs_out, void* stream);
+/* One Cholesky-QR step on 1 <= k <= MGCMT_BLOCK_WIDE_OUT distinct vectors W:  W <- W T  and (aw_slots, aw_vecs not NULL)
+ * AW <- AW T, with T upper triangular, its diagonal positive, T^T (W^T W) T = I.  Three stream-ordered launches: G = W^T W on
+ * the matrix cores (W read once); one workgroup that scales G to a unit diagonal (d_j = G_jj^(-1/2)), factors D G D = R^T R
+ * (Cholesky in column order, no pivoting) and forms T = D R^-1; the in-place product (a second launch for AW).  A column
+ * whose G_jj is zero or not finite, or whose pivot of the scaled matrix is <= drop_tol (0 < drop_tol < 1, else
+ * MGCMT_ERR_INVALID), is DROPPED: its row and column leave the factorisation, its row and column of T are zero, and it comes
+ * back as exact zeros in W and in AW.  t_out (may be NULL): T, k x k row-major; dropped_out (may be NULL): bit j set when
+ * column j was dropped; either one synchronises, with both NULL nothing does.  Applied twice to vectors with
+ * cond(W)^2 u O(nk) < 1 it leaves them orthonormal to working accuracy.  Bit-reproducible from call to call.  Scratch and
+ * stream rule: those of the wide entries.  Refused as there: null lists, k out of range, a W or an AW named twice, an AW that
+ * is also a W, one companion list without the other.  Writes the k vectors W and the k vectors AW and nothing else. */
+int mgcmt_block_orthonormalize(mgcmt_plan* plan, int level, int k, const int* w_slots, const int* w_vecs, const int* aw_slots,
+                               const int* aw_vecs, double drop_tol, double* t_out, unsigned* dropped_out, void* stream);
 /* in-place Gram-Schmidt of vectors 0..k-1 of `slot`: modified != 0 -> MGS (:44-50), else CGS (:34-42) */
 int mgcmt_gramschmidt(mgcmt_plan* plan, int level, int slot, int k, int modified, void* stream);
 /* columns scaled to unit 2-norm (normalize, :52-63) */

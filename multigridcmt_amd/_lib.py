@@ -151,6 +151,9 @@ _SIGNATURES = {
                                          POINTER(c_double), c_void_p]),
     "mgcmt_block_deflate": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int), POINTER(c_int),
                                     POINTER(c_double), c_void_p]),
+    "mgcmt_block_project": (c_int, [c_void_p, c_int, c_int] + [POINTER(c_int)] * 4 + [c_int] + [POINTER(c_int)] * 4 + [POINTER(c_double), c_void_p]),
+    "mgcmt_block_orthonormalize": (c_int, [c_void_p, c_int, c_int] + [POINTER(c_int)] * 4 + [c_double, POINTER(c_double), POINTER(ctypes.c_uint),
+                                           c_void_p]),
     "mgcmt_gramschmidt": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mgcmt_normalize": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "mgcmt_level_operator_kind": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int)]),

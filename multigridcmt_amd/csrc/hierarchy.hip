@@ -708,6 +708,7 @@ int mgcmt_plan_destroy(mgcmt_plan* p) {
   if (p->d_wide_partials) (void)hipFree(p->d_wide_partials);
   if (p->d_wide_out) (void)hipFree(p->d_wide_out);
   if (p->d_wide_table) (void)hipFree(p->d_wide_table);
+  if (p->d_orth_mask) (void)hipFree(p->d_orth_mask);
   if (p->d_rqstate) (void)hipFree(p->d_rqstate);
   if (p->d_rqhistory) (void)hipFree(p->d_rqhistory);
   if (p->d_mgs) (void)hipFree(p->d_mgs);

@@ -312,6 +312,149 @@ __global__ void __launch_bounds__(kWideThreads) k_block_deflate(long n2, Deflate
   }
 }
 
+// One Cholesky-QR step W <- W T on k <= 16 vectors (mgcmt_block_orthonormalize; DESIGN.md par. 4.22) in three launches.
+struct OrthArgs {
+  double* w[kBlockWideOut];
+};
+
+// Launch 1: G = W^T W, one tile of the pencil's products with ONE operand register per vector serving as A and as B (the
+// pencil's G when M = I): W is read once.  Lane <-> element map, runs, prefetch, trips and sums of k_block_pencil; the partial
+// tile of block b is partials[b * 256 + row * 16 + col].
+__global__ void __launch_bounds__(kWideThreads) k_block_gram16(long n, OrthArgs g, int k, double* __restrict__ partials) {
+  __shared__ double s_red[kWideWaves - 1][kTileWords];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, kg = lane >> 4;
+  const double* pw = col < k ? g.w[col] : nullptr;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  const long nsteps = (n + kStepPoints - 1) / kStepPoints;
+  const long lane_off = (long)(wave * 4 + kg) * kRun;
+  double xw[kRun], yw[kRun];
+  long step = blockIdx.x;  // (every wave of a block takes the same trips: the emulation's shuffles need whole workgroups)
+  if (step < nsteps) load_run(pw, step * kStepPoints + lane_off, n, xw);
+  for (; step < nsteps; step += gridDim.x) {
+    const long next = step + gridDim.x;
+    if (next < nsteps) load_run(pw, next * kStepPoints + lane_off, n, yw);  // in flight while this step's products run
+#pragma unroll
+    for (int q = 0; q < kRun; ++q) mfma_f64_16x16x4(xw[q], xw[q], acc);
+    if (next < nsteps) {
+#pragma unroll
+      for (int q = 0; q < kRun; ++q) xw[q] = yw[q];
+    }
+  }
+  // waves 1..3 hand their tile to wave 0 through LDS; wave 0 adds them in wave order
+  if (wave > 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s_red[wave - 1][r * 64 + lane] = acc[r];
+  }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      double tot = acc[r];
+      for (int w = 0; w < kWideWaves - 1; ++w) tot += s_red[w][r * 64 + lane];
+      partials[(long)blockIdx.x * kTileWords + (kg + 4 * r) * kTile + col] = tot;
+    }
+  }
+}
+
+// Launch 2, one workgroup, a thread per entry of the tile: the blocks' partial tiles summed 0..nb-1, G symmetrised and
+// scaled to a unit diagonal (d_j = G_jj^(-1/2); a column whose G_jj is zero or not finite is dropped), the right-looking
+// Cholesky factorisation D G D = R^T R in LDS in column order without pivoting — a column whose pivot is <= drop_tol is
+// dropped: its row and column leave the factorisation —, R inverted by back substitution (a thread per column), and
+// T = D R^-1 stored as the coefficient rows k_block_transform reads (table[i * 16 + j], zero beyond k and in the row and
+// the column of a dropped vector) next to the mask of dropped columns.
+__global__ void __launch_bounds__(kTileWords) k_orth_factor(int nb, int k, double drop_tol, const double* __restrict__ partials, double* __restrict__ table,
+                                                            unsigned* __restrict__ mask_out) {
+  __shared__ double S[kTile][kTile];  // G, then the scaled matrix, overwritten by R (upper triangle)
+  __shared__ double C[kTile][kTile];  // R^-1
+  __shared__ double d[kTile];
+  __shared__ int alive[kTile];
+  const int ti = threadIdx.x / kTile, tj = threadIdx.x % kTile;
+  {
+    const double* src = partials + threadIdx.x;
+    double tot = 0.0;
+    for (int b = 0; b < nb; ++b) tot += src[(long)b * kTileWords];
+    S[ti][tj] = tot;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < kTile) {
+    const int j = threadIdx.x;
+    const double gj = S[j][j];
+    const bool fine = j < k && gj > 0.0 && gj <= 1.7e308;
+    alive[j] = fine ? 1 : 0;
+    d[j] = fine ? 1.0 / sqrt(gj) : 0.0;
+  }
+  __syncthreads();
+  const double sym = 0.5 * (S[ti][tj] + S[tj][ti]);
+  const bool both = alive[ti] && alive[tj];
+  __syncthreads();
+  S[ti][tj] = both ? (ti == tj ? 1.0 : sym * d[ti] * d[tj]) : 0.0;
+  C[ti][tj] = 0.0;
+  __syncthreads();
+  for (int t = 0; t < k; ++t) {
+    if (!alive[t]) continue;  // (every thread reads the same words: uniform)
+    const double piv = S[t][t];
+    __syncthreads();
+    if (!(piv > drop_tol)) {
+      if (ti == t || tj == t) S[ti][tj] = 0.0;
+      if (threadIdx.x == 0) alive[t] = 0;
+      __syncthreads();
+      continue;
+    }
+    const double r = sqrt(piv);
+    if (ti == t && tj >= t) S[t][tj] = tj == t ? r : S[t][tj] / r;
+    __syncthreads();
+    if (ti > t && tj >= ti) S[ti][tj] -= S[t][ti] * S[t][tj];
+    __syncthreads();
+  }
+  if ((int)threadIdx.x < k && alive[threadIdx.x]) {  // column j of C = R^-1 over the vectors that stayed
+    const int j = threadIdx.x;
+    C[j][j] = 1.0 / S[j][j];
+    for (int i = j - 1; i >= 0; --i) {
+      if (!alive[i]) continue;
+      double sum = 0.0;
+      for (int t = i + 1; t <= j; ++t) sum += S[i][t] * C[t][j];
+      C[i][j] = -sum / S[i][i];
+    }
+  }
+  __syncthreads();
+  table[ti * kTile + tj] = d[ti] * C[ti][tj];
+  if (threadIdx.x == 0) {
+    unsigned m = 0;
+    for (int j = 0; j < k; ++j) m |= alive[j] ? 0u : 1u << j;
+    mask_out[0] = m;
+  }
+}
+
+// Launch 3: OUT_j = sum_(i <= j) T_ij W_i in place on the vector ALUs, as k_block_deflate: a thread owns two points (16-byte
+// accesses), loads its k values and forms the k outputs over the unrolled triangle; the coefficient rows and the mask are
+// wave-uniform reads.  A dropped vector is not read and is stored as exact zeros; columns j >= k are neither read nor stored.
+__global__ void __launch_bounds__(kWideThreads) k_block_transform(long n2, OrthArgs g, int k, const double* __restrict__ coef,
+                                                                  const unsigned* __restrict__ mask) {
+  const unsigned dropped = mask[0];
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x) {
+    double2 x[kBlockWideOut];
+#pragma unroll
+    for (int t = 0; t < kBlockWideOut; ++t)
+      x[t] = (t < k && !((dropped >> t) & 1u)) ? reinterpret_cast<const double2*>(g.w[t])[i] : make_double2(0.0, 0.0);
+    // output j needs the inputs i <= j only: from the last column down, each output takes its input's registers
+#pragma unroll
+    for (int j = kBlockWideOut - 1; j >= 0; --j) {
+      if (j < k) {  // (wave-uniform)
+        double2 a = make_double2(coef[j * kBlockWideOut + j] * x[j].x, coef[j * kBlockWideOut + j] * x[j].y);
+#pragma unroll
+        for (int t = 0; t < j; ++t) {
+          a.x = fma(coef[t * kBlockWideOut + j], x[t].x, a.x);
+          a.y = fma(coef[t * kBlockWideOut + j], x[t].y, a.y);
+        }
+        x[j] = ((dropped >> j) & 1u) ? make_double2(0.0, 0.0) : a;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kBlockWideOut; ++j)
+      if (j < k) reinterpret_cast<double2*>(g.w[j])[i] = x[j];
+  }
+}
+
 }  // namespace
 
 int block_pencil_blocks(long n) {
@@ -415,6 +558,64 @@ bool launch_block_deflate(hipStream_t s, long n, int nq, const double* const* q,
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(k_block_deflate, dim3((unsigned)blocks), dim3(kWideThreads), 0, s, n2, g, nq, k, out);
+  return true;
+}
+
+// launch_block_deflate with companions: aw_j <- aw_j - sum_i <b_i, w_j> ab_i with the coefficients of the w (ab == aw ==
+// nullptr: the w only).  Pass 2 is k_block_deflate once per pair on the same coefficient table.
+bool launch_block_project(hipStream_t s, long n, int nb, const double* const* b, const double* const* ab, int k, double* const* w, double* const* aw,
+                          double* partials, double* out) {
+  DeflateArgs g{}, ga{};
+  uintptr_t bits = (uintptr_t)(n & 1);
+  for (int t = 0; t < kBlockLockedMax; ++t) {
+    g.q[t] = b[t < nb ? t : 0];
+    if (ab) ga.q[t] = ab[t < nb ? t : 0];
+    if (t < nb) bits |= (reinterpret_cast<uintptr_t>(b[t]) | (ab ? reinterpret_cast<uintptr_t>(ab[t]) : 0)) & 15;
+  }
+  for (int j = 0; j < kBlockWideOut; ++j) {
+    g.w[j] = w[j < k ? j : 0];
+    if (aw) ga.w[j] = aw[j < k ? j : 0];
+    if (j < k) bits |= (reinterpret_cast<uintptr_t>(w[j]) | (aw ? reinterpret_cast<uintptr_t>(aw[j]) : 0)) & 15;
+  }
+  if (bits != 0) return false;
+  const int blocks1 = block_pencil_blocks(n), tiles = (nb + kTile - 1) / kTile;
+  const dim3 grid(blocks1), block(kWideThreads);
+  if (tiles == 1) hipLaunchKernelGGL((k_block_cross<1>), grid, block, 0, s, n, g, nb, k, partials);
+  else if (tiles == 2) hipLaunchKernelGGL((k_block_cross<2>), grid, block, 0, s, n, g, nb, k, partials);
+  else if (tiles == 3) hipLaunchKernelGGL((k_block_cross<3>), grid, block, 0, s, n, g, nb, k, partials);
+  else hipLaunchKernelGGL((k_block_cross<4>), grid, block, 0, s, n, g, nb, k, partials);
+  hipLaunchKernelGGL(k_pencil_final, dim3(tiles), dim3(kTileWords), 0, s, blocks1, partials, out);
+  const long n2 = n / 2;
+  long blocks = (n2 + kWideThreads - 1) / kWideThreads;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_block_deflate, dim3((unsigned)blocks), dim3(kWideThreads), 0, s, n2, g, nb, k, out);
+  if (ab) hipLaunchKernelGGL(k_block_deflate, dim3((unsigned)blocks), dim3(kWideThreads), 0, s, n2, ga, nb, k, out);
+  return true;
+}
+
+// One Cholesky-QR step w <- w T, aw <- aw T (aw == nullptr: the w only) on k <= 16 distinct vectors: `partials` holds
+// block_pencil_blocks(n) * 256 doubles, `table` (256 doubles) is left holding T row-major in rows of 16, `mask` the dropped
+// columns.  false (nothing launched): n is odd or a vector is not 16-byte aligned
+bool launch_block_orthonormalize(hipStream_t s, long n, int k, double* const* w, double* const* aw, double drop_tol, double* partials, double* table,
+                                 unsigned* mask) {
+  OrthArgs g{}, ga{};
+  uintptr_t bits = (uintptr_t)(n & 1);
+  for (int j = 0; j < kBlockWideOut; ++j) {
+    g.w[j] = w[j < k ? j : 0];
+    if (aw) ga.w[j] = aw[j < k ? j : 0];
+    if (j < k) bits |= (reinterpret_cast<uintptr_t>(w[j]) | (aw ? reinterpret_cast<uintptr_t>(aw[j]) : 0)) & 15;
+  }
+  if (bits != 0) return false;
+  const int nb = block_pencil_blocks(n);
+  hipLaunchKernelGGL(k_block_gram16, dim3(nb), dim3(kWideThreads), 0, s, n, g, k, partials);
+  hipLaunchKernelGGL(k_orth_factor, dim3(1), dim3(kTileWords), 0, s, nb, k, drop_tol, partials, table, mask);
+  const long n2 = n / 2;
+  long blocks = (n2 + kWideThreads - 1) / kWideThreads;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_block_transform, dim3((unsigned)blocks), dim3(kWideThreads), 0, s, n2, g, k, table, mask);
+  if (aw) hipLaunchKernelGGL(k_block_transform, dim3((unsigned)blocks), dim3(kWideThreads), 0, s, n2, ga, k, table, mask);
   return true;
 }
 

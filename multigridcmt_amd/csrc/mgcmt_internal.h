@@ -240,6 +240,11 @@ bool launch_block_combine_wide(hipStream_t s, long n, const double* const* in, i
                                unsigned long long* table);
 constexpr int kBlockLockedMax = MGCMT_BLOCK_LOCKED_MAX;  // vectors a block is deflated against (mgcmt_block_deflate)
 bool launch_block_deflate(hipStream_t s, long n, int nq, const double* const* q, int k, double* const* w, double* partials, double* out);
+// the same with companions (mgcmt_block_project), and one Cholesky-QR step on k <= 16 vectors (mgcmt_block_orthonormalize)
+bool launch_block_project(hipStream_t s, long n, int nb, const double* const* b, const double* const* ab, int k, double* const* w, double* const* aw,
+                          double* partials, double* out);
+bool launch_block_orthonormalize(hipStream_t s, long n, int k, double* const* w, double* const* aw, double drop_tol, double* partials, double* table,
+                                 unsigned* mask);
 void launch_gram(hipStream_t s, long n, const double* const* v, int nv, double* partials, double* out);
 void launch_lincomb(hipStream_t s, long n, const double* const* v, const double* c, int nt, double* dst);
 bool mgs_small_fits(long n);

@@ -420,6 +420,92 @@ int mgcmt_block_deflate(mgcmt_plan* p, int l, int nq, const int* q_slots, const 
   return MGCMT_OK;
 }
 
+int mgcmt_block_project(mgcmt_plan* p, int l, int nb, const int* b_slots, const int* b_vecs, const int* ab_slots, const int* ab_vecs, int k,
+                        const int* w_slots, const int* w_vecs, const int* aw_slots, const int* aw_vecs, double* coeffs_out, void* stream) {
+  MG_TRY(check_level(p, l));
+  if (nb < 1 || nb > kBlockLockedMax || k < 1 || k > kBlockWideOut)
+    return fail(MGCMT_ERR_INVALID, "block_project: 1..64 vectors B, 1..16 vectors W");
+  if (!b_slots || !b_vecs || !w_slots || !w_vecs) return fail(MGCMT_ERR_INVALID, "block_project: non-null vector lists");
+  const bool companions = ab_slots != nullptr;
+  if ((ab_vecs != nullptr) != companions || (aw_slots != nullptr) != companions || (aw_vecs != nullptr) != companions)
+    return fail(MGCMT_ERR_INVALID, "block_project: the companion lists AB and AW are given all four or not at all");
+  double *b[kBlockLockedMax], *ab[kBlockLockedMax], *w[kBlockWideOut], *aw[kBlockWideOut];
+  MG_TRY(wide_vectors(p, l, nb, b_slots, b_vecs, b));
+  MG_TRY(wide_vectors(p, l, k, w_slots, w_vecs, w));
+  if (companions) {
+    MG_TRY(wide_vectors(p, l, nb, ab_slots, ab_vecs, ab));
+    MG_TRY(wide_vectors(p, l, k, aw_slots, aw_vecs, aw));
+  }
+  for (int j = 0; j < k; ++j) {
+    for (int i = 0; i < j; ++i)
+      if (w[i] == w[j]) return fail(MGCMT_ERR_INVALID, "block_project: a vector W named twice");
+    for (int i = 0; i < nb; ++i)
+      if (b[i] == w[j] || (companions && ab[i] == w[j])) return fail(MGCMT_ERR_INVALID, "block_project: a vector W that is also a B or an AB");
+  }
+  for (int j = 0; companions && j < k; ++j) {
+    for (int i = 0; i < j; ++i)
+      if (aw[i] == aw[j]) return fail(MGCMT_ERR_INVALID, "block_project: a vector AW named twice");
+    for (int i = 0; i < k; ++i)
+      if (aw[j] == w[i]) return fail(MGCMT_ERR_INVALID, "block_project: a vector AW that is also a B, an AB or a W");
+    for (int i = 0; i < nb; ++i)
+      if (aw[j] == b[i] || aw[j] == ab[i]) return fail(MGCMT_ERR_INVALID, "block_project: a vector AW that is also a B, an AB or a W");
+  }
+  const long n = p->interior(l);
+  const int tiles = (nb + 15) / 16;
+  MG_TRY(wide_scratch(p, (size_t)tiles * block_pencil_blocks(n) * 256, S(stream)));
+  if (!launch_block_project(S(stream), n, nb, b, companions ? ab : nullptr, k, w, companions ? aw : nullptr, p->d_wide_partials, p->d_wide_out))
+    return fail(MGCMT_ERR_INVALID, "block_project: an odd number of points or a vector that is not 16-byte aligned");
+  MG_TRY(post_launch());
+  if (coeffs_out) {
+    std::vector<double> packed((size_t)nb * kBlockWideOut);
+    MG_HIP(hipMemcpyAsync(packed.data(), p->d_wide_out, sizeof(double) * packed.size(), hipMemcpyDeviceToHost, S(stream)));
+    MG_HIP(hipStreamSynchronize(S(stream)));
+    for (int i = 0; i < nb; ++i)
+      for (int j = 0; j < k; ++j) coeffs_out[i * k + j] = packed[(size_t)i * kBlockWideOut + j];
+  }
+  return MGCMT_OK;
+}
+
+int mgcmt_block_orthonormalize(mgcmt_plan* p, int l, int k, const int* w_slots, const int* w_vecs, const int* aw_slots, const int* aw_vecs,
+                               double drop_tol, double* t_out, unsigned* dropped_out, void* stream) {
+  MG_TRY(check_level(p, l));
+  if (k < 1 || k > kBlockWideOut) return fail(MGCMT_ERR_INVALID, "block_orthonormalize: 1..16 vectors W");
+  if (!w_slots || !w_vecs) return fail(MGCMT_ERR_INVALID, "block_orthonormalize: non-null vector lists");
+  if ((aw_slots != nullptr) != (aw_vecs != nullptr))
+    return fail(MGCMT_ERR_INVALID, "block_orthonormalize: the companion lists are given both or not at all");
+  if (!(drop_tol > 0.0 && drop_tol < 1.0)) return fail(MGCMT_ERR_INVALID, "block_orthonormalize: drop_tol lies in (0, 1)");
+  const bool companions = aw_slots != nullptr;
+  double *w[kBlockWideOut], *aw[kBlockWideOut];
+  MG_TRY(wide_vectors(p, l, k, w_slots, w_vecs, w));
+  if (companions) MG_TRY(wide_vectors(p, l, k, aw_slots, aw_vecs, aw));
+  for (int j = 0; j < k; ++j) {
+    for (int i = 0; i < j; ++i)
+      if (w[i] == w[j]) return fail(MGCMT_ERR_INVALID, "block_orthonormalize: a vector W named twice");
+    for (int i = 0; companions && i < j; ++i)
+      if (aw[i] == aw[j]) return fail(MGCMT_ERR_INVALID, "block_orthonormalize: a vector AW named twice");
+    for (int i = 0; companions && i < k; ++i)
+      if (aw[j] == w[i]) return fail(MGCMT_ERR_INVALID, "block_orthonormalize: a vector AW that is also a W");
+  }
+  const long n = p->interior(l);
+  MG_TRY(wide_scratch(p, (size_t)block_pencil_blocks(n) * 256, S(stream)));
+  if (!p->d_orth_mask) MG_HIP(hipMalloc((void**)&p->d_orth_mask, sizeof(unsigned)));
+  if (!launch_block_orthonormalize(S(stream), n, k, w, companions ? aw : nullptr, drop_tol, p->d_wide_partials, p->d_wide_out, p->d_orth_mask))
+    return fail(MGCMT_ERR_INVALID, "block_orthonormalize: an odd number of points or a vector that is not 16-byte aligned");
+  MG_TRY(post_launch());
+  if (t_out) {
+    double packed[kBlockWideOut * kBlockWideOut];
+    MG_HIP(hipMemcpyAsync(packed, p->d_wide_out, sizeof(packed), hipMemcpyDeviceToHost, S(stream)));
+    MG_HIP(hipStreamSynchronize(S(stream)));
+    for (int i = 0; i < k; ++i)
+      for (int j = 0; j < k; ++j) t_out[i * k + j] = packed[i * kBlockWideOut + j];
+  }
+  if (dropped_out) {
+    MG_HIP(hipMemcpyAsync(dropped_out, p->d_orth_mask, sizeof(unsigned), hipMemcpyDeviceToHost, S(stream)));
+    MG_HIP(hipStreamSynchronize(S(stream)));
+  }
+  return MGCMT_OK;
+}
+
 int mgcmt_axpy(mgcmt_plan* p, int l, double alpha, int x_slot, int x_vec, int y_slot, int y_vec, void* stream) {
   MG_TRY(check_vec(p, l, x_slot, x_vec));
   MG_TRY(check_vec(p, l, y_slot, y_vec));

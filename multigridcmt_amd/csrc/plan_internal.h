@@ -80,6 +80,7 @@ struct mgcmt_plan {
   size_t wide_partials_doubles = 0;
   double* d_wide_out = nullptr;
   unsigned long long* d_wide_table = nullptr;
+  unsigned* d_orth_mask = nullptr;  // the dropped columns of mgcmt_block_orthonormalize (its T lives in d_wide_out)
   double* d_rq = nullptr;       // Gram results of mgcmt_rayleigh_residual, one block per column
   double* d_rqstate = nullptr;  // scalars of the device-resident Rayleigh-quotient minimisation (kernels_rq.hip)
   double* d_mgs = nullptr;  // the blocked Gram-Schmidt's R^-1 and gate word (kernels_blas.hip)

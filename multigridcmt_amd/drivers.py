@@ -412,10 +412,13 @@ def block_eigensolve(op, k=4, cycles=12, nu=2, lowest=8, smoother="rb", seed=0, 
 
 
 DEFLATED_EIGENSOLVE_MAX = 64   # states of deflated_eigensolve: the vectors Q of mgcmt_block_deflate
+# deflated_eigensolve(basis="orthonormal"): a column of W or P whose pivot in the Cholesky factorisation of the unit-diagonal
+# Gram matrix is at most this leaves the basis (mgcmt_block_orthonormalize).  DESIGN.md par. 4.22 derives the value.
+ORTHONORMAL_DROP_TOL = 1e-12
 
 
 def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, nu=2, lowest=8, smoother="rb", seed=0,
-                        guesses=None, info=None, mass=None):
+                        guesses=None, info=None, mass=None, basis="scaled"):
     """The k lowest eigenpairs of a structured 2-D or 3-D operator, 1 <= k <= 64, solved TO A TOLERANCE: block_eigensolve's
     iteration (LOBPCG with a V-cycle preconditioner) with hard locking.  A Ritz pair whose residual meets the tolerance —
     ||A x - rho x|| <= max(atol, rtol |rho|) — is locked: it leaves the active block for a store of its own, a fresh random
@@ -440,10 +443,23 @@ def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, 
     state) and column_cycles (active columns summed over the iterations).  With status "maxiter" the states that were not
     locked are returned as they stand — as many as the active block holds: min(k, locked + kb) columns in all.
 
-    Known limit (DESIGN.md par. 4.21): 40 states of the 1024^2 and 2048^2 boxes stall on the MI355X once 28 are locked — the
-    Gram matrix of the scaled [X, W, P] loses rank to working accuracy (smallest eigenvalue 1e-12 and below), the Ritz vectors
-    then carry errors of 1e-4 and no residual reaches 1e-8 |rho| again; status is "maxiter".  24 states converge there (34
-    iterations at 1024^2, 36 at 2048^2), 40 states converge at 64^2 and 64 at 32^2.  Check ``info["status"]``."""
+    ``basis``: how the trial basis [X, W, P] of Rayleigh-Ritz is conditioned.  "scaled" (the default): the vectors as they
+    come, the pencil scaled to a unit diagonal.  "orthonormal" (DESIGN.md par. 4.22): in every iteration the cycle's output W is
+    projected against the locked vectors and against X and made orthonormal by a Cholesky-QR step, twice
+    (mgcmt_block_deflate, mgcmt_block_orthonormalize), A is applied, and P and AP are projected against [X, W] and made
+    orthonormal together, twice (mgcmt_block_project, mgcmt_block_orthonormalize with companions); X = S C with C^T G C = I
+    stays orthonormal, fresh vectors are also deflated against the X that remain.  The Gram matrix of the Ritz problem is then
+    the identity to rounding.  A column whose pivot falls to ORTHONORMAL_DROP_TOL or below comes back as zeros and leaves the
+    Ritz problem of that iteration.  ``info`` then also receives gram_min (the smallest eigenvalue of the scaled Gram matrix
+    of each main-loop Ritz problem) and dropped (columns dropped, per iteration).
+
+    Known limit of basis="scaled" (DESIGN.md par. 4.21): 40 states of the 1024^2 and 2048^2 boxes stall on the MI355X once 28
+    are locked — the Gram matrix of the scaled [X, W, P] loses rank to working accuracy (smallest eigenvalue 1e-12 and below),
+    the Ritz vectors then carry errors of 1e-4 and no residual reaches 1e-8 |rho| again; status is "maxiter".  24 states
+    converge there (34 iterations at 1024^2, 36 at 2048^2), 40 states converge at 64^2 and 64 at 32^2.  With
+    basis="orthonormal" the 40 states of the 1024^2 box converge on the MI355X in 65 iterations (lowest = 4, gram_min >=
+    1 - 1e-14); 40 states at 2048^2 with lowest = 8 still ended at "maxiter" with it (DESIGN.md par. 4.22: open).
+    Check ``info["status"]``."""
     from . import _lib
     from .plan import get_plan
     k = int(k)
@@ -456,6 +472,9 @@ def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, 
         raise ValueError("deflated_eigensolve does not take a mass operator (the locked store would have to keep M Q next to Q)")
     if smoother not in ("rb", "wjacobi"):
         raise ValueError("deflated_eigensolve: smoother is 'rb' or 'wjacobi'")
+    if basis not in ("scaled", "orthonormal"):
+        raise ValueError("deflated_eigensolve: basis is 'scaled' or 'orthonormal'")
+    orthonormal = basis == "orthonormal"
     kind, omega = (_lib.GS_MC, 1.0) if smoother == "rb" else (_lib.WJACOBI, 2. / 3.)
     V, F, W = _lib.SLOT_V, _lib.SLOT_F, _lib.SLOT_W
     plan = get_plan(op, int(lowest), nvec=3 * kb + (k + 1) // 2)
@@ -482,6 +501,25 @@ def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, 
         d = 1.0 / np.sqrt(np.diag(G))                   # (scaling only: the pencil's eigenvectors are rescaled back)
         evals, evecs = scipy.linalg.eigh(H * np.outer(d, d), G * np.outer(d, d), subset_by_index=[0, kb - 1])
         return evals, evecs * d[:, None]
+
+    gram_min, dropped = [], []
+
+    def ritz_orthonormal(S, AS):
+        """ritz over a basis whose W and P parts mgcmt_block_orthonormalize made: a column it dropped is exact zeros and shows
+        as an exact zero on the diagonal of G — it leaves the Ritz problem and gets a zero coefficient row.  Records the
+        smallest eigenvalue of the scaled G and the number of dropped columns."""
+        H, G = plan.block_pencil(0, S, AS)
+        G, H = 0.5 * (G + G.T), 0.5 * (H + H.T)
+        keep = np.flatnonzero(np.diag(G) != 0.0)
+        H, G = H[np.ix_(keep, keep)], G[np.ix_(keep, keep)]
+        d = 1.0 / np.sqrt(np.diag(G))
+        Gs = G * np.outer(d, d)
+        gram_min.append(float(np.linalg.eigvalsh(Gs)[0]))
+        dropped.append(len(S) - len(keep))
+        evals, evecs = scipy.linalg.eigh(H * np.outer(d, d), Gs, subset_by_index=[0, kb - 1])
+        C = np.zeros((len(S), kb))
+        C[keep] = evecs * d[:, None]
+        return evals, C
 
     def ritz_over_x():
         rho, C = ritz(X, AX)
@@ -515,26 +553,44 @@ def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, 
             for j in range(nlock):
                 plan.upload(0, W, j, rng.random_sample(n))
             plan.block_deflate(0, Q[:len(vals)], X[:nlock])
+            if orthonormal and nlock < kb:              # ... and against the X that remain (orthonormal, and orthogonal to Q)
+                plan.block_deflate(0, X[nlock:], X[:nlock])
             for j in range(nlock):
                 plan.apply(0, X[j], AX[j])
             rho = ritz_over_x()
 
+    main_ritz = ritz_orthonormal if orthonormal else ritz
     rho, norms, _ = residuals_and_locks(ritz_over_x())
     have_p = False
     while len(vals) < k and iterations < int(maxiter):
         iterations += 1
         column_cycles += kb
         plan.vcycle(nu, nu, kind, omega=omega, k=kb, nu_coarse=nu, zero_start=True)
-        if vals:
-            plan.block_deflate(0, Q[:len(vals)], Wd)
-        for j in range(kb):
-            plan.apply(0, Wd[j], AW[j])
+        if orthonormal:
+            # [X, Wd, P] with orthonormal columns: Wd against Q and X, P against X and Wd, each projection and Cholesky-QR step
+            # twice (the second one works on vectors the first left with a condition number near one)
+            for _ in range(2):
+                if vals:
+                    plan.block_deflate(0, Q[:len(vals)], Wd)
+                plan.block_deflate(0, X, Wd)
+                plan.block_orthonormalize(0, Wd, drop_tol=ORTHONORMAL_DROP_TOL)
+            for j in range(kb):                          # (A of a dropped column, exact zeros, is exact zeros)
+                plan.apply(0, Wd[j], AW[j])
+            for _ in range(2 if have_p else 0):
+                plan.block_project(0, X + Wd, P, AX + AW, AP)
+                plan.block_orthonormalize(0, P, AP, drop_tol=ORTHONORMAL_DROP_TOL)
+        else:
+            if vals:
+                plan.block_deflate(0, Q[:len(vals)], Wd)
+            for j in range(kb):
+                plan.apply(0, Wd[j], AW[j])
         S, AS = (X + Wd + P, AX + AW + AP) if have_p else (X + Wd, AX + AW)
         try:
-            rho, C = ritz(S, AS)
+            rho, C = main_ritz(S, AS)
         except (scipy.linalg.LinAlgError, ValueError):   # the directions have become dependent: restart without P
             S, AS = X + Wd, AX + AW
-            rho, C = ritz(S, AS)
+            del gram_min[iterations - 1:], dropped[iterations - 1:]
+            rho, C = main_ritz(S, AS)
         # P' = [W, P] C_wp, X' = X C_x + P' (and their images under A), as block_eigensolve
         plan.block_combine_wide(0, S[kb:], P, C[kb:])
         plan.block_combine_wide(0, AS[kb:], AP, C[kb:])
@@ -554,4 +610,6 @@ def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, 
     if info is not None:
         info.update(iterations=iterations, status="converged" if nlocked == k else "maxiter", locked_at=locked_at[order],
                     residuals=norms[order], column_cycles=column_cycles)
+        if orthonormal:
+            info.update(gram_min=np.array(gram_min), dropped=np.array(dropped, dtype=np.int64))
     return vals[order], vecs

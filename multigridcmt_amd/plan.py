@@ -416,6 +416,40 @@ class Plan:
                                              None if c is None else _lib.as_dp(c), stream))
         return c
 
+    def block_project(self, level, b, w, ab=None, aw=None, want_coeffs=False, stream=None):
+        """block_deflate with companions: w[j] <- w[j] - sum_i <b[i], w[j]> b[i] and, with ab and aw, aw[j] <- aw[j] -
+        sum_i <b[i], w[j]> ab[i] ((slot, vec) pairs; <= 64 vectors b, <= 16 distinct vectors w; mgcmt_block_project).
+        want_coeffs: returns the len(b) x len(w) coefficients and synchronises."""
+        nb, k = len(b), len(w)
+        if (ab is None) != (aw is None) or (ab is not None and (len(ab) != nb or len(aw) != k)):
+            raise ValueError("block_project: ab and aw come together, as long as b and w")
+
+        def ints(vs, which):
+            return None if vs is None else (ctypes.c_int * len(vs))(*[v[which] for v in vs])
+        c = np.zeros((nb, k)) if want_coeffs else None
+        check(_lib.lib().mgcmt_block_project(self._h, level, nb, ints(b, 0), ints(b, 1), ints(ab, 0), ints(ab, 1), k, ints(w, 0), ints(w, 1),
+                                             ints(aw, 0), ints(aw, 1), None if c is None else _lib.as_dp(c), stream))
+        return c
+
+    def block_orthonormalize(self, level, w, aw=None, drop_tol=1e-12, want_t=False, want_dropped=False, stream=None):
+        """One Cholesky-QR step w <- w T and, with aw, aw <- aw T on <= 16 distinct vectors ((slot, vec) pairs;
+        mgcmt_block_orthonormalize): T upper triangular with T^T (w^T w) T = I; a column whose pivot of the scaled Gram
+        matrix is <= drop_tol comes back as exact zeros.  Returns None, T (want_t), the mask of dropped columns
+        (want_dropped) or the pair; either one synchronises."""
+        k = len(w)
+        if aw is not None and len(aw) != k:
+            raise ValueError("block_orthonormalize: aw as long as w")
+
+        def ints(vs, which):
+            return None if vs is None else (ctypes.c_int * len(vs))(*[v[which] for v in vs])
+        t = np.zeros((k, k)) if want_t else None
+        mask = ctypes.c_uint(0)
+        check(_lib.lib().mgcmt_block_orthonormalize(self._h, level, k, ints(w, 0), ints(w, 1), ints(aw, 0), ints(aw, 1), c_double(drop_tol),
+                                                    None if t is None else _lib.as_dp(t), ctypes.byref(mask) if want_dropped else None, stream))
+        if want_t and want_dropped:
+            return t, int(mask.value)
+        return t if want_t else int(mask.value) if want_dropped else None
+
     def axpy(self, level, alpha, x, y, stream=None):
         check(_lib.lib().mgcmt_axpy(self._h, level, c_double(alpha), x[0], x[1], y[0], y[1], stream))
 

@@ -505,6 +505,30 @@ int mgcmt_block_project(mgcmt_plan* plan, int level, int nb, const int* b_slots,
  * is also a W, one companion list without the other.  Writes the k vectors W and the k vectors AW and nothing else. */
 int mgcmt_block_orthonormalize(mgcmt_plan* plan, int level, int k, const int* w_slots, const int* w_vecs, const int* aw_slots,
                                const int* aw_vecs, double drop_tol, double* t_out, unsigned* dropped_out, void* stream);
+/* dst(r) = sum_(t < nq) weights[t] x_t(r)^2   for 1 <= nq <= MGCMT_BLOCK_LOCKED_MAX vectors x of `level` (the charge density of
+ * nq states with their occupations; drivers.schroedinger_poisson).  One stream-ordered pass, nothing synchronises: every named
+ * vector is read once and dst written once, 8 (nq + 1) bytes per point.  weights: nq host numbers, copied on entry.  The
+ * arithmetic is fixed — acc = 0; for t ascending: acc = fma(weights[t] * x_t, x_t, acc) —, so the result is bit-reproducible
+ * from call to call and does not depend on the launch's grid.  MGCMT_ERR_INVALID: null lists, nq out of range, a vector outside
+ * the plan, dst one of the x, a weight that is not finite, an odd number of points or a vector that is not 16-byte aligned
+ * (the rule of the wide entries).  Writes dst and nothing else. */
+int mgcmt_block_density(mgcmt_plan* plan, int level, int nq, const int* x_slots, const int* x_vecs, const double* weights, int dst_slot,
+                        int dst_vec, void* stream);
+/* A new per-point diagonal for a plan that has a per-point part (any of the six creators of such plans):
+ *     D = sum_(t < nterms) coeffs[t] * (slots[t], vecs[t]),   1 <= nterms <= 4, level-0 vectors of this plan,
+ * with the arithmetic of mgcmt_lincomb, written to level 0 — the diagonal of mgcmt_plan_create_pot / create3d_pot, plane D of
+ * the creators with bonds (the bonds stay), the centre plane of a stencil (plane 4 of 9, 13 of 27; the others stay) — and the
+ * planes of every level below formed again by the launches creation used, in its order and with its arguments: the hierarchy
+ * then holds the bits a plan created from that diagonal holds.  Stream-ordered on `stream`; nothing is allocated and the host
+ * is not synchronised.  What is derived from the planes follows: the factorisation (and explicit inverse) of a coarse solve
+ * is redone before its next use, also in front of a replayed cycle graph; the graphs themselves hold pointers to the planes,
+ * which do not move, and are kept.  MGCMT_ERR_INVALID: a plan without a per-point part, null lists, nterms out of range, a
+ * vector outside the plan. */
+int mgcmt_plan_set_point_diagonal(mgcmt_plan* plan, int nterms, const double* coeffs, const int* slots, const int* vecs, void* stream);
+/* (dst_slot, dst_vec) of `dst` <- (src_slot, src_vec) of `src` on `level`: one device-to-device copy of the level vector's
+ * interior between two plans on the same device, of the same dimension, whose level has the same rows and columns (whole
+ * grids).  Stream-ordered.  Anything else — and src == dst naming the same vector — is MGCMT_ERR_INVALID. */
+int mgcmt_copy_across(mgcmt_plan* src, int level, int src_slot, int src_vec, mgcmt_plan* dst, int dst_slot, int dst_vec, void* stream);
 /* in-place Gram-Schmidt of vectors 0..k-1 of `slot`: modified != 0 -> MGS (:44-50), else CGS (:34-42) */
 int mgcmt_gramschmidt(mgcmt_plan* plan, int level, int slot, int k, int modified, void* stream);
 /* columns scaled to unit 2-norm (normalize, :52-63) */

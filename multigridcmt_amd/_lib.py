@@ -20,6 +20,7 @@ HALO_ROWS = 16         # 2-D levels (a 1-D level keeps one halo "row"); exchange
 RQ_HISTORY = 4096      # MGCMT_RQ_HISTORY: Rayleigh quotients Plan.rq_line_step can record on the device
 MAX_TERMS = 4
 MAX_VEC = 32
+MAX_STORE_VEC = 80     # MGCMT_MAX_STORE_VEC: vectors a plan keeps per slot
 ABI_VERSION = 7
 OPT_FUSED = 0
 OPT_FUSED_ROWS = 1
@@ -151,6 +152,9 @@ _SIGNATURES = {
                                          POINTER(c_double), c_void_p]),
     "mgcmt_block_deflate": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int), POINTER(c_int),
                                     POINTER(c_double), c_void_p]),
+    "mgcmt_block_density": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_double), c_int, c_int, c_void_p]),
+    "mgcmt_plan_set_point_diagonal": (c_int, [c_void_p, c_int, _dp, POINTER(c_int), POINTER(c_int), c_void_p]),
+    "mgcmt_copy_across": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "mgcmt_block_project": (c_int, [c_void_p, c_int, c_int] + [POINTER(c_int)] * 4 + [c_int] + [POINTER(c_int)] * 4 + [POINTER(c_double), c_void_p]),
     "mgcmt_block_orthonormalize": (c_int, [c_void_p, c_int, c_int] + [POINTER(c_int)] * 4 + [c_double, POINTER(c_double), POINTER(ctypes.c_uint),
                                            c_void_p]),

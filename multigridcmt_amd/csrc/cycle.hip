@@ -245,11 +245,12 @@ int prolong_correct_impl(mgcmt_plan* p, int l, int k, hipStream_t s) {
 }
 
 // The coarsest-level matrix (the per-point entries ride in the assembly) for the current shifts, factored and, where the
-// explicit inverse is kept, inverted; nothing to do while the first k shifts are those of the last time.  The band storage exists.
+// explicit inverse is kept, inverted; nothing to do while the first k shifts are those of the last time and the per-point
+// planes are the ones that were assembled (mgcmt_plan_set_point_diagonal counts its calls).  The band storage exists.
 int factor_coarse(mgcmt_plan* p, int l, int k, hipStream_t s) {
   Level& L = p->levels[l];
   BandState& B = L.band;
-  bool same = B.valid && B.k >= k;
+  bool same = B.valid && B.k >= k && B.point_version == p->point_version;
   if (same)
     for (int q = 0; q < k; ++q) same = same && B.shifts[q] == p->h_shifts[q];
   if (same) return MGCMT_OK;
@@ -259,6 +260,7 @@ int factor_coarse(mgcmt_plan* p, int l, int k, hipStream_t s) {
   if (B.inv) launch_band_invert(s, B.b, B.inv, (long)B.b.n * B.b.n, k);
   B.valid = true;
   B.k = k;
+  B.point_version = p->point_version;
   B.shifts.assign(p->h_shifts.begin(), p->h_shifts.begin() + k);
   return post_launch();
 }
@@ -823,7 +825,8 @@ int mgcmt_vcycle(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int 
     snprintf(buf, sizeof(buf), "|%p,%p", (void*)L.base[MGCMT_SLOT_V], (void*)L.base[MGCMT_SLOT_T]);
     key += buf;
   }
-  // the coarsest-level factorisation (and the tail's matrix) depend on the shift VALUES; redo them eagerly when they changed
+  // the coarsest-level factorisation (and the tail's matrix) depend on the shift VALUES and on the per-point planes; redo them
+  // eagerly when either changed (factor_coarse compares the shifts and the plan's point_version)
   auto prepare = [&]() {
     MG_TRY(ensure_coarse_factor(p, (int)p->levels.size() - 1, k, s));
     return ensure_tail_for_cycle(p, level, nu_coarse, kind, omega, k, cycle_flags, s);

@@ -436,6 +436,8 @@ int build_plan(const PlanSpec& d, mgcmt_plan** out) {
   p->h_shifts.assign(kMaxVec, 0.0);
   const char* mb = getenv("MGCMT_MGS_BLOCK_MIN");  // points per column from which Gram-Schmidt takes its two-pass form (tests, tuning)
   if (mb && atol(mb) > 1) p->mgs_block_min = atol(mb);
+  const char* db = getenv("MGCMT_DENSITY_BLOCKS");  // the grid limit of mgcmt_block_density (tests: several trips at a small size)
+  if (db && atol(db) >= 1 && atol(db) <= 4096) p->density_max_blocks = (int)atol(db);
   if (d.dim != 3) {
     const char* e = getenv("MGCMT_TAIL_DENSE");  // "0": the tail as the LDS-resident launch by default (the host-only test build:
     p->use_tail_dense = !(e && e[0] == '0');     // emulating the 1024 workgroups that form the matrix takes minutes)
@@ -622,6 +624,41 @@ int mgcmt_plan_get_point_stencil(const mgcmt_plan* p, int l, double* out, int64_
   if (!out || capacity < np * N) return fail(MGCMT_ERR_INVALID, "point stencil buffer too small");
   // the interior of every plane (2-D level 0 of a diagonal or bonds: the rows between the halo rows, which are contiguous)
   for (int a = 0; a < np; ++a) MG_HIP(hipMemcpy(out + a * N, v.pg + a * v.pplane, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+  return MGCMT_OK;
+}
+
+int mgcmt_plan_set_point_diagonal(mgcmt_plan* p, int nterms, const double* coeffs, const int* slots, const int* vecs, void* stream) {
+  if (!p) return fail(MGCMT_ERR_INVALID, "null plan");
+  if (!p->has_point) return fail(MGCMT_ERR_INVALID, "plan has no point diagonal");
+  if (!coeffs || !slots || !vecs || nterms < 1 || nterms > 4) return fail(MGCMT_ERR_INVALID, "set_point_diagonal: 1..4 terms, non-null arguments");
+  const double* v[4];
+  for (int t = 0; t < nterms; ++t) {
+    MG_TRY(check_vec(p, 0, slots[t], vecs[t]));
+    MG_TRY(ensure_slot(p, 0, slots[t]));
+    v[t] = p->kvec(0, slots[t], vecs[t]).p;
+  }
+  hipStream_t s = S(stream);
+  // Level 0: the diagonal, plane D of {D, bonds} or the centre plane of a stencil — in each layout of build_point_part the
+  // interior of that plane is nr * gc contiguous numbers at pg (+ centre * pplane), as the interior of a level vector is: the
+  // halo rows of a padded 2-D plane lie outside it and stay exact zeros
+  const PointView top = point_of(p, 0);
+  const int centre = top.kind == kPointPlanes ? (point_planes(p->dim, kPointPlanes) - 1) / 2 : 0;
+  launch_lincomb(s, p->interior(0), v, coeffs, nterms, const_cast<double*>(top.pg) + centre * top.pplane);
+  MG_TRY(post_launch());
+  // the levels below: the launches of build_point_part, in its order, into the planes it allocated
+  for (size_t l = 1; l < p->levels.size(); ++l) {
+    const Level &F = p->levels[l - 1], &L = p->levels[l];
+    const PointView f = point_of(p, (int)l - 1);
+    double* q = const_cast<double*>(point_of(p, (int)l).pg);
+    const size_t N = (size_t)L.nr * L.gc;
+    if (p->dim == 3) launch3p_coarsen(s, F.dA.k3.n, f.pg, point_planes(3, f.kind), f.pplane, q, (long)N);
+    else launch_point_coarsen(s, F.nr, F.gc, f.pg, point_planes(2, f.kind), F.gc, f.pplane, q, L.gc, L.nr * L.gc);
+    MG_TRY(post_launch());
+  }
+  // What is derived from the planes: the band factorisation and explicit inverse of a coarse solve (factor_coarse compares
+  // this count, also in front of a graph replay).  The tail's matrix is not: a plan with a per-point part runs no tail.  Cached
+  // cycle graphs hold the planes' addresses, which have not changed: they stay.
+  ++p->point_version;
   return MGCMT_OK;
 }
 

@@ -312,6 +312,34 @@ __global__ void __launch_bounds__(kWideThreads) k_block_deflate(long n2, Deflate
   }
 }
 
+// The density of up to 64 weighted vectors, dst(r) = sum_t w_t x_t(r)^2 (mgcmt_block_density; DESIGN.md par. 4.23), in one
+// launch shaped as k_block_deflate: a thread owns two points (16-byte accesses) in a grid-stride loop, the 64 pointers, the 64
+// weights and dst travel as kernel arguments (1032 bytes) and are wave-uniform, the t loop is unrolled by four so that four
+// vector loads are in flight.  Plain stores, no LDS, no atomics, nothing handed from one workgroup to another.  The arithmetic
+// of a point is fixed:
+//     acc = 0;  for t = 0 .. nq - 1 ascending:  acc = fma(w_t * x_t, x_t, acc)
+// (one rounding in the product w_t * x_t, one in the fused multiply-add), so the result is the same bits from call to call
+// and whatever the grid.  Vectors t >= nq are never read.
+struct DensityArgs {
+  const double* x[kBlockLockedMax];
+  double w[kBlockLockedMax];
+  double* dst;
+};
+
+__global__ void __launch_bounds__(kWideThreads) k_block_density(long n2, DensityArgs g, int nq) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x) {
+    double2 acc = make_double2(0.0, 0.0);
+#pragma unroll 4
+    for (int t = 0; t < nq; ++t) {
+      const double w = g.w[t];
+      const double2 x = reinterpret_cast<const double2*>(g.x[t])[i];
+      acc.x = fma(w * x.x, x.x, acc.x);
+      acc.y = fma(w * x.y, x.y, acc.y);
+    }
+    reinterpret_cast<double2*>(g.dst)[i] = acc;
+  }
+}
+
 // One Cholesky-QR step W <- W T on k <= 16 vectors (mgcmt_block_orthonormalize; DESIGN.md par. 4.22) in three launches.
 struct OrthArgs {
   double* w[kBlockWideOut];
@@ -558,6 +586,27 @@ bool launch_block_deflate(hipStream_t s, long n, int nq, const double* const* q,
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(k_block_deflate, dim3((unsigned)blocks), dim3(kWideThreads), 0, s, n2, g, nq, k, out);
+  return true;
+}
+
+// dst = sum_t w[t] x_t^2 for nq <= 64 vectors x, none of them dst; w: host numbers, copied into the launch.  max_blocks > 0:
+// the grid's upper limit in place of 4096 (tests: a small grid takes several trips at a small size; the result does not depend
+// on it).  false (nothing launched): n is odd or a vector is not 16-byte aligned
+bool launch_block_density(hipStream_t s, long n, int nq, const double* const* x, const double* w, double* dst, int max_blocks) {
+  DensityArgs g{};
+  uintptr_t bits = (uintptr_t)(n & 1) | (reinterpret_cast<uintptr_t>(dst) & 15);
+  for (int t = 0; t < kBlockLockedMax; ++t) {
+    g.x[t] = x[t < nq ? t : 0];
+    g.w[t] = t < nq ? w[t] : 0.0;
+    if (t < nq) bits |= reinterpret_cast<uintptr_t>(x[t]) & 15;
+  }
+  g.dst = dst;
+  if (bits != 0) return false;
+  const long n2 = n / 2, cap = max_blocks > 0 ? max_blocks : 4096;
+  long blocks = (n2 + kWideThreads - 1) / kWideThreads;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_block_density, dim3((unsigned)blocks), dim3(kWideThreads), 0, s, n2, g, nq);
   return true;
 }
 

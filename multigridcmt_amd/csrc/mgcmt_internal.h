@@ -240,6 +240,8 @@ bool launch_block_combine_wide(hipStream_t s, long n, const double* const* in, i
                                unsigned long long* table);
 constexpr int kBlockLockedMax = MGCMT_BLOCK_LOCKED_MAX;  // vectors a block is deflated against (mgcmt_block_deflate)
 bool launch_block_deflate(hipStream_t s, long n, int nq, const double* const* q, int k, double* const* w, double* partials, double* out);
+// dst = sum_t w[t] x_t^2, nq <= kBlockLockedMax (mgcmt_block_density); max_blocks > 0: the grid's limit in place of the default
+bool launch_block_density(hipStream_t s, long n, int nq, const double* const* x, const double* w, double* dst, int max_blocks);
 // the same with companions (mgcmt_block_project), and one Cholesky-QR step on k <= 16 vectors (mgcmt_block_orthonormalize)
 bool launch_block_project(hipStream_t s, long n, int nb, const double* const* b, const double* const* ab, int k, double* const* w, double* const* aw,
                           double* partials, double* out);

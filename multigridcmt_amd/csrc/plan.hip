@@ -2,6 +2,7 @@
 // C-ABI that is neither hierarchy (hierarchy.hip), cycle (cycle.hip) nor Rayleigh quotient (rq_host.hip): vector
 // transfer / fill / copy, the BLAS-like entries, plan options, the probes and timers.
 // Host code only; every kernel it enqueues is in kernels_*.hip.
+#include <cmath>
 #include <cstdio>
 #include <string>
 
@@ -156,6 +157,24 @@ int mgcmt_copy(mgcmt_plan* p, int l, int src_slot, int src_vec, int dst_slot, in
   MG_TRY(ensure_slot(p, l, dst_slot));
   MG_HIP(hipMemcpyAsync(p->kvec(l, dst_slot, dst_vec).p, p->kvec(l, src_slot, src_vec).p, sizeof(double) * p->interior(l),
                         hipMemcpyDeviceToDevice, S(stream)));
+  return MGCMT_OK;
+}
+
+int mgcmt_copy_across(mgcmt_plan* src, int l, int src_slot, int src_vec, mgcmt_plan* dst, int dst_slot, int dst_vec, void* stream) {
+  MG_TRY(check_vec(src, l, src_slot, src_vec));
+  MG_TRY(check_vec(dst, l, dst_slot, dst_vec));
+  if (src->dim != dst->dim) return fail(MGCMT_ERR_INVALID, "copy_across: the plans differ in dimension");
+  if (src->device != dst->device) return fail(MGCMT_ERR_INVALID, "copy_across: the plans live on different devices");
+  // the interior of a level vector is nr * gc contiguous numbers behind the halo: equal rows and columns, both whole grids
+  const Level &A = src->levels[l], &B = dst->levels[l];
+  if (A.nr != B.nr || A.gc != B.gc || A.gr != B.gr || A.r0 != B.r0 || A.nr != A.gr)
+    return fail(MGCMT_ERR_INVALID, "copy_across: the level's shape differs between the plans (or one of them is a row strip)");
+  MG_TRY(ensure_slot(src, l, src_slot));
+  MG_TRY(ensure_slot(dst, l, dst_slot));
+  const double* from = src->kvec(l, src_slot, src_vec).p;
+  double* to = dst->kvec(l, dst_slot, dst_vec).p;
+  if (from == to) return fail(MGCMT_ERR_INVALID, "copy_across: source and destination are the same vector");
+  MG_HIP(hipMemcpyAsync(to, from, sizeof(double) * src->interior(l), hipMemcpyDeviceToDevice, S(stream)));
   return MGCMT_OK;
 }
 
@@ -418,6 +437,25 @@ int mgcmt_block_deflate(mgcmt_plan* p, int l, int nq, const int* q_slots, const 
       for (int j = 0; j < k; ++j) coeffs_out[i * k + j] = packed[(size_t)i * kBlockWideOut + j];
   }
   return MGCMT_OK;
+}
+
+int mgcmt_block_density(mgcmt_plan* p, int l, int nq, const int* x_slots, const int* x_vecs, const double* weights, int dst_slot, int dst_vec,
+                        void* stream) {
+  MG_TRY(check_level(p, l));
+  if (nq < 1 || nq > kBlockLockedMax) return fail(MGCMT_ERR_INVALID, "block_density: 1..64 vectors X");
+  if (!x_slots || !x_vecs || !weights) return fail(MGCMT_ERR_INVALID, "block_density: non-null vector lists and weights");
+  double* x[kBlockLockedMax];
+  MG_TRY(wide_vectors(p, l, nq, x_slots, x_vecs, x));
+  MG_TRY(check_vec(p, l, dst_slot, dst_vec));
+  MG_TRY(ensure_slot(p, l, dst_slot));
+  double* dst = p->kvec(l, dst_slot, dst_vec).p;
+  for (int t = 0; t < nq; ++t) {
+    if (x[t] == dst) return fail(MGCMT_ERR_INVALID, "block_density: the destination is also an X");
+    if (!std::isfinite(weights[t])) return fail(MGCMT_ERR_INVALID, "block_density: a weight that is not finite");
+  }
+  if (!launch_block_density(S(stream), p->interior(l), nq, x, weights, dst, p->density_max_blocks))
+    return fail(MGCMT_ERR_INVALID, "block_density: an odd number of points or a vector that is not 16-byte aligned");
+  return post_launch();
 }
 
 int mgcmt_block_project(mgcmt_plan* p, int l, int nb, const int* b_slots, const int* b_vecs, const int* ab_slots, const int* ab_vecs, int k,

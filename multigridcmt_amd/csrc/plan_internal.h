@@ -45,6 +45,7 @@ struct BandState {
   bool valid = false;
   int k = 0;
   std::vector<double> shifts;
+  unsigned long point_version = 0;  // mgcmt_plan::point_version of the planes that were assembled
 };
 
 struct Level {
@@ -100,6 +101,10 @@ struct mgcmt_plan {
   std::vector<double> h_shifts;
   bool has_mass = false;
   bool has_point = false;  // A carries a per-point part — a diagonal, bonds or a stencil, 2-D or 3-D: all six creators go through create_point / build_point_part (hierarchy.hip) —: KOp::point / K3Op::point on every level
+  // how often mgcmt_plan_set_point_diagonal has replaced the per-point diagonal: what is derived from the planes (BandState)
+  // remembers the count it was formed at and is formed again when the plan has moved on
+  unsigned long point_version = 0;
+  int density_max_blocks = 0;  // the grid limit of mgcmt_block_density, 0 = the default (MGCMT_DENSITY_BLOCKS, read at creation: tests)
   bool use_fused = true;
   bool use_tail = true;   // levels of at most 32 x 32 points as one launch (kernels_tail.hip)
   bool use_tail_dense = true;  // ... and that launch as ONE dense product with the tail's matrix (formed once per shift set)

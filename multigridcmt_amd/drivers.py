@@ -9,6 +9,8 @@
 Every V-cycle, interpolation, Gram-Schmidt and operator application runs on the GPU through MGCMTSolver /
 MGCMTProcessor; the coarse-grid ``eigsh`` stays on the host as in the reference (16 .. 256 unknowns).
 """
+import math
+
 import numpy as np
 import scipy.linalg
 import scipy.sparse as sparse
@@ -412,6 +414,7 @@ def block_eigensolve(op, k=4, cycles=12, nu=2, lowest=8, smoother="rb", seed=0, 
 
 
 DEFLATED_EIGENSOLVE_MAX = 64   # states of deflated_eigensolve: the vectors Q of mgcmt_block_deflate
+BLOCK_PENCIL_MAX = 48          # MGCMT_BLOCK_WIDE_MAX: vectors of one mgcmt_block_pencil
 # deflated_eigensolve(basis="orthonormal"): a column of W or P whose pivot in the Cholesky factorisation of the unit-diagonal
 # Gram matrix is at most this leaves the basis (mgcmt_block_orthonormalize).  DESIGN.md par. 4.22 derives the value.
 ORTHONORMAL_DROP_TOL = 1e-12
@@ -460,7 +463,6 @@ def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, 
     basis="orthonormal" the 40 states of the 1024^2 box converge on the MI355X in 65 iterations (lowest = 4, gram_min >=
     1 - 1e-14); 40 states at 2048^2 with lowest = 8 still ended at "maxiter" with it (DESIGN.md par. 4.22: open).
     Check ``info["status"]``."""
-    from . import _lib
     from .plan import get_plan
     k = int(k)
     if not 1 <= k <= DEFLATED_EIGENSOLVE_MAX:
@@ -474,12 +476,33 @@ def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, 
         raise ValueError("deflated_eigensolve: smoother is 'rb' or 'wjacobi'")
     if basis not in ("scaled", "orthonormal"):
         raise ValueError("deflated_eigensolve: basis is 'scaled' or 'orthonormal'")
+    plan = get_plan(op, int(lowest), nvec=3 * kb + (k + 1) // 2)
+    n = plan.size(0)
+    rng = np.random.RandomState(seed)
+    given = 0 if guesses is None else min(kb, np.asarray(guesses).shape[1])
+
+    def place(j, location):
+        """the j-th vector the iteration asks for: a column of the guesses for the first of the start block, else the next draw"""
+        plan.upload(0, location[0], location[1], np.asarray(guesses)[:, j] if j < given else rng.random_sample(n))
+
+    vals, where = _deflated_eigensolve_on(plan, k, kb, place, rtol=rtol, atol=atol, maxiter=maxiter, nu=nu, smoother=smoother, basis=basis,
+                                          info=info)
+    vecs = np.stack([np.asarray(plan.download(0, *v)) for v in where], axis=1)
+    return vals, vecs
+
+
+def _deflated_eigensolve_on(plan, k, kb, place, *, rtol, atol, maxiter, nu, smoother, basis, info):
+    """The iteration of deflated_eigensolve on a plan it is given (at least 3 kb + ceil(k / 2) vectors per slot; columns beyond
+    those are not touched, nor is anything of slots W and F on levels below 0).  Every start vector and every fresh vector
+    comes through ``place(j, (slot, vec))``, j counting the requests from 0: the first kb are the start block X, in order,
+    the rest the fresh vectors after locks; it leaves the vector at that location of level 0, stream-ordered.  Nothing is
+    downloaded: returns (eigenvalues ascending, the (slot, vec) locations of their vectors in that order) — as many as
+    deflated_eigensolve returns.  The arguments have been checked."""
+    from . import _lib
     orthonormal = basis == "orthonormal"
     kind, omega = (_lib.GS_MC, 1.0) if smoother == "rb" else (_lib.WJACOBI, 2. / 3.)
     V, F, W = _lib.SLOT_V, _lib.SLOT_F, _lib.SLOT_W
-    plan = get_plan(op, int(lowest), nvec=3 * kb + (k + 1) // 2)
     plan.set_shifts(np.zeros(min(plan.nvec, _lib.MAX_VEC)))
-    n = plan.size(0)
     X = [(W, j) for j in range(kb)]
     AX = [(W, kb + j) for j in range(kb)]
     P = [(W, 2 * kb + j) for j in range(kb)]
@@ -488,10 +511,10 @@ def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, 
     AW = [(F, 2 * kb + j) for j in range(kb)]
     Wd = [(V, j) for j in range(kb)]
     Q = [((W, F)[i % 2], 3 * kb + i // 2) for i in range(k)]          # the locked store
-    rng = np.random.RandomState(seed)
-    given = 0 if guesses is None else min(kb, np.asarray(guesses).shape[1])
+    placed = 0
     for j in range(kb):
-        plan.upload(0, W, j, np.asarray(guesses)[:, j] if j < given else rng.random_sample(n))
+        place(placed, X[j])
+        placed += 1
         plan.apply(0, X[j], AX[j])
 
     def ritz(S, AS):
@@ -533,6 +556,7 @@ def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, 
     def residuals_and_locks(rho):
         """R = A X - X diag(rho) and its norms; locks the converged prefix, refills the block and repeats while pairs lock.
         Returns (rho, norms, whether anything was locked)."""
+        nonlocal placed
         locked_any = False
         while True:
             for j in range(kb):
@@ -551,7 +575,8 @@ def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, 
             if len(vals) == k:
                 return rho[nlock:], norms[nlock:], True
             for j in range(nlock):
-                plan.upload(0, W, j, rng.random_sample(n))
+                place(placed, X[j])
+                placed += 1
             plan.block_deflate(0, Q[:len(vals)], X[:nlock])
             if orthonormal and nlock < kb:              # ... and against the X that remain (orthonormal, and orthogonal to Q)
                 plan.block_deflate(0, X[nlock:], X[:nlock])
@@ -606,10 +631,163 @@ def deflated_eigensolve(op, k, *, rtol=1e-8, atol=0.0, block=None, maxiter=200, 
     norms = np.array(norms_locked + [float(r) for r in norms[:rest]])
     locked_at = np.array(locked_at + [-1] * rest, dtype=np.int64)
     order = np.argsort(vals, kind="stable")
-    vecs = np.stack([np.asarray(plan.download(0, *where[j])) for j in order], axis=1)
     if info is not None:
         info.update(iterations=iterations, status="converged" if nlocked == k else "maxiter", locked_at=locked_at[order],
                     residuals=norms[order], column_cycles=column_cycles)
         if orthonormal:
             info.update(gram_min=np.array(gram_min), dropped=np.array(dropped, dtype=np.int64))
-    return vals[order], vecs
+    return vals[order], [where[j] for j in order]
+
+
+def schroedinger_poisson(op, poisson_op, k, occupations, *, coupling, mixing=1.0, tol=1e-6, maxiter=50, eigen_rtol=1e-9,
+                         poisson_rtol=1e-10, warm_start=True, block=None, lowest=8, poisson_lowest=None, smoother="rb", basis="scaled",
+                         seed=0, info=None):
+    """The self-consistent Schroedinger-Poisson loop on the device: the k lowest states of H[phi] = op + coupling diag(phi),
+    their density rho = sum_j f_j psi_j^2, poisson_op phi = rho, and again until phi stands still.
+
+    ``op``: a 2-D or 3-D operator with a per-point part (potential_operator, variable_mass_operator, tensor_mass_operator); its
+    diagonal (the centre plane of a stencil) is the external potential.  ``poisson_op``: an operator MGCMTSolver.solve takes, on
+    the same grid — e.g. variable_mass_operator(g, eps) for -div(eps grad), or a sparse matrix that solve recognises (it goes
+    through the same recognition, with op's dimension).  ``occupations``: k weights f_j, or a callable
+    eigenvalues -> k weights (Fermi filling is host arithmetic on k numbers).  Units live in ``coupling`` and ``poisson_op``.
+
+    One step: deflated_eigensolve's iteration to ``eigen_rtol`` on ONE private plan (the same block, locking, ``smoother`` and
+    ``basis``); rho in one pass over the states, each weighted f_j / <psi_j, psi_j> (mgcmt_block_density); a device copy to the
+    right-hand side of a second private plan (mgcmt_copy_across); conjugate gradients with the V-cycle preconditioner to
+    ``poisson_rtol`` there (from a zero start in the first step, from the last solution afterwards);
+    d = ||phi_new - phi||_2 / ||phi_new||_2 (phi = 0 before the first step, so the first d is 1); phi <- (1 - mixing) phi +
+    mixing phi_new; a device copy back; the new diagonal V_ext + coupling phi and the per-point planes of every coarser level
+    (mgcmt_plan_set_point_diagonal).  The loop ends with the step whose d <= tol, or after ``maxiter`` steps.  With
+    coupling == 0 the operator does not depend on phi: the states of the first step stand and no later step solves for them again.
+    The host sees eigenvalues, residual norms, the Ritz matrices, the status words of the solves and d: no grid vector crosses
+    to the host between the upload of V_ext and the downloads at the end (with warm_start=False every step uploads its random
+    start vectors, as deflated_eigensolve does).
+
+    ``warm_start``: the k states of a step are copied to a pool in the plan's own columns and handed to the next step's
+    iteration in order — the first kb as its start block, the others as the fresh vectors after locks —, random vectors only
+    behind them.
+
+    Memory: the eigen-plan holds 3 kb + ceil(k / 2) columns per slot for the iteration (deflated_eigensolve), ceil(k / 2) more
+    in each of slots W and F for the pool and two for V_ext and rho / phi (slot W; a cycle exchanges the storage of V and T) —
+    at most MGCMT_MAX_STORE_VEC = 80, so k <= 30 with the default block.  The Poisson plan holds 6.
+
+    Returns (eigenvalues[k], eigenvectors[n, k], phi[n]): the states are those of the last step's operator, phi the mixed
+    potential after it.  ``info`` (a dict) receives iterations, status ("converged" / "maxiter"), changes (every d),
+    eigen_iterations, eigen_status, poisson_iterations and poisson_status per step, and density (rho of the last step, n
+    numbers).  A Poisson solve that does not reach ``poisson_rtol`` within 200 iterations, breaks down or meets an indefinite
+    operator raises RuntimeError: the loop does not go on with a potential that is not one.
+    Refused with ValueError: what deflated_eigensolve refuses, an ``op`` without a per-point part, operators on different
+    grids, occupations that are not k numbers, a mixing outside (0, 1], more columns than a plan stores."""
+    from . import _lib
+    from .operators import StructuredOperator
+    from .plan import Plan
+    k = int(k)
+    if not 1 <= k <= DEFLATED_EIGENSOLVE_MAX:
+        raise ValueError("schroedinger_poisson handles 1..%d states" % DEFLATED_EIGENSOLVE_MAX)
+    kb = min(BLOCK_EIGENSOLVE_MAX, k + 4) if block is None else int(block)
+    if not 1 <= kb <= BLOCK_EIGENSOLVE_MAX:
+        raise ValueError("schroedinger_poisson: an active block of 1..%d vectors" % BLOCK_EIGENSOLVE_MAX)
+    if smoother not in ("rb", "wjacobi"):
+        raise ValueError("schroedinger_poisson: smoother is 'rb' or 'wjacobi'")
+    if basis not in ("scaled", "orthonormal"):
+        raise ValueError("schroedinger_poisson: basis is 'scaled' or 'orthonormal'")
+    part, arrays = op.point_part()
+    if part is None or op.dimension not in ("2d", "3d"):
+        raise ValueError("schroedinger_poisson: op needs a per-point part (potential_operator, variable_mass_operator, tensor_mass_operator): "
+                         "its diagonal is the external potential")
+    if not isinstance(poisson_op, StructuredOperator):
+        from .solver import _recognise_entry
+        poisson_op = _recognise_entry(poisson_op, op.dimension)          # (raises UnrecognisedOperator, a ValueError, as solve does)
+    if poisson_op.dimension != op.dimension or poisson_op.g != op.g:
+        raise ValueError("schroedinger_poisson: op (%s, g = %d) and poisson_op (%s, g = %d) live on different grids"
+                         % (op.dimension, op.g, poisson_op.dimension, poisson_op.g))
+    if not 0.0 < float(mixing) <= 1.0:
+        raise ValueError("schroedinger_poisson: mixing lies in (0, 1]")
+    if not callable(occupations) and np.asarray(occupations, dtype=np.float64).shape != (k,):
+        raise ValueError("schroedinger_poisson: occupations are k = %d numbers (or a callable eigenvalues -> k numbers)" % k)
+    half = (k + 1) // 2
+    nvec = 3 * kb + 2 * half + 2
+    if nvec > _lib.MAX_STORE_VEC:
+        raise ValueError("schroedinger_poisson: 3 kb + ceil(k / 2) columns for the iteration, ceil(k / 2) for the pool and 2 for V_ext and "
+                         "rho / phi are 3 * %d + %d + %d + 2 = %d columns; a plan stores at most %d (k <= 30 with the default block)"
+                         % (kb, half, half, nvec, _lib.MAX_STORE_VEC))
+    coupling, mixing = float(coupling), float(mixing)
+    kind, omega = (_lib.GS_MC, 1.0) if smoother == "rb" else (_lib.WJACOBI, 2. / 3.)
+    F, W = _lib.SLOT_F, _lib.SLOT_W
+    POOL = [((W, F)[i % 2], 3 * kb + half + i // 2) for i in range(k)]
+    VEXT, RHO = (W, nvec - 2), (W, nvec - 1)                     # (RHO holds rho on the way out and phi on the way back)
+    PX, PPHI, PDIFF = (W, 0), (W, 4), (W, 5)                      # the Poisson plan: columns 0..3 of W are x, p, q, p2 of the solve
+    v_ext = arrays[0] if part != "planes" else arrays[0][(1,) * (arrays[0].ndim // 2)]
+    rng = np.random.RandomState(seed)
+    changes, eig_its, eig_status, poi_its, poi_status = [], [], [], [], []
+    eplan = pplan = None
+    try:
+        eplan = Plan(op, int(lowest), nvec=nvec)
+        pplan = Plan(poisson_op, int(lowest if poisson_lowest is None else poisson_lowest), nvec=6)
+        n = eplan.size(0)
+        eplan.upload(0, VEXT[0], VEXT[1], v_ext)
+        pplan.set_shifts(np.zeros(6))
+        pplan.fill(0, PPHI[0], PPHI[1], 0.0)
+        pooled = 0
+
+        def place(j, location):
+            if warm_start and j < pooled:
+                eplan.copy(0, POOL[j][0], POOL[j][1], location[0], location[1])
+            else:
+                eplan.upload(0, location[0], location[1], rng.random_sample(n))
+
+        vals = where = None
+        status = "maxiter"
+        for step in range(1, int(maxiter) + 1):
+            if where is None or coupling != 0.0:
+                einfo = {}
+                vals, where = _deflated_eigensolve_on(eplan, k, kb, place, rtol=eigen_rtol, atol=0.0, maxiter=200, nu=2, smoother=smoother,
+                                                      basis=basis, info=einfo)
+                eig_its.append(int(einfo["iterations"]))
+                eig_status.append(einfo["status"])
+                if warm_start:
+                    pooled = len(where)
+                    for j, v in enumerate(where):
+                        eplan.copy(0, v[0], v[1], POOL[j][0], POOL[j][1])
+            else:
+                eig_its.append(0)
+                eig_status.append(eig_status[-1])
+            f = np.asarray(occupations(vals) if callable(occupations) else occupations, dtype=np.float64).reshape(-1)[:len(where)]
+            norm2 = np.concatenate([np.diag(eplan.block_pencil(0, where[i:i + BLOCK_PENCIL_MAX], where[i:i + BLOCK_PENCIL_MAX])[0])
+                                    for i in range(0, len(where), BLOCK_PENCIL_MAX)])      # (a pencil takes at most 48 vectors)
+            eplan.block_density(0, where, f / norm2, RHO)
+            eplan.copy_across(0, RHO, pplan, (F, 0))
+            pplan.pcg_begin([0, 1, 2, 3], float(poisson_rtol), zero_start=step == 1, flexible=kind != _lib.WJACOBI)
+            queued, state = 0, _lib.PCG_RUNNING
+            while state == _lib.PCG_RUNNING and queued < 200:
+                pplan.pcg_iterate(4, 2, 2, kind, omega=omega, nu_coarse=4)
+                queued += 4
+                done, state, indefinite = pplan.pcg_status()[:3]
+            poi_its.append(int(done))
+            poi_status.append({_lib.PCG_CONVERGED: "converged", _lib.PCG_BREAKDOWN: "breakdown"}.get(int(state), "maxiter"))
+            if poi_status[-1] != "converged" or indefinite:
+                raise RuntimeError("schroedinger_poisson: the Poisson solve of step %d ended with status %r%s after %d iterations "
+                                   "(poisson_op must be positive definite)" % (step, poi_status[-1], ", indefinite" if indefinite else "", done))
+            pplan.lincomb(0, [(1.0, PX), (-1.0, PPHI)], PDIFF)
+            d = math.sqrt(pplan.dot(0, PDIFF, PDIFF) / pplan.dot(0, PX, PX))
+            changes.append(d)
+            pplan.lincomb(0, [(1.0 - mixing, PPHI), (mixing, PX)], PPHI)
+            if coupling != 0.0:
+                pplan.copy_across(0, PPHI, eplan, RHO)
+                eplan.set_point_diagonal([(1.0, VEXT), (coupling, RHO)])
+            if d <= tol:
+                status = "converged"
+                break
+        if info is not None:
+            info.update(iterations=len(changes), status=status, changes=changes, eigen_iterations=eig_its, eigen_status=eig_status,
+                        poisson_iterations=poi_its, poisson_status=poi_status)
+            if coupling != 0.0:                                   # (RHO holds phi by now: the density once more)
+                eplan.block_density(0, where, f / norm2, RHO)
+            info["density"] = np.array(eplan.download(0, *RHO))
+        vecs = np.stack([np.asarray(eplan.download(0, *v)) for v in where], axis=1)
+        phi = np.array(pplan.download(0, *PPHI))
+        return vals, vecs, phi
+    finally:
+        for p in (eplan, pplan):
+            if p is not None:
+                p.close()

@@ -73,6 +73,7 @@ class Plan:
         self.num_levels = n.value
         self.shapes = [self.level_shape(l) for l in range(self.num_levels)]
         self._shifts = None
+        self.op_stale = False        # set_point_diagonal has replaced the diagonal: the plan no longer describes self.op
 
     def _point_refusal(self, kind, mass):
         """The error of a plan whose operator has a per-point part and that is given a mass operator (`mass`) or a row strip:
@@ -415,6 +416,41 @@ class Plan:
                                              k, (ctypes.c_int * k)(*[v[0] for v in w]), (ctypes.c_int * k)(*[v[1] for v in w]),
                                              None if c is None else _lib.as_dp(c), stream))
         return c
+
+    def block_density(self, level, xs, weights, dst, stream=None):
+        """dst <- sum_t weights[t] * xs[t]^2 point by point ((slot, vec) pairs; <= 64 vectors xs, dst none of them): one
+        stream-ordered pass that reads every vector once (mgcmt_block_density) — the charge density of states with their
+        occupations.  Bit-reproducible."""
+        nq = len(xs)
+        w = np.array([float(f) for f in weights])
+        if w.size != nq:
+            raise ValueError("block_density: one weight per vector")
+        check(_lib.lib().mgcmt_block_density(self._h, level, nq, (ctypes.c_int * nq)(*[v[0] for v in xs]), (ctypes.c_int * nq)(*[v[1] for v in xs]),
+                                             _lib.as_dp(w), dst[0], dst[1], stream))
+
+    def set_point_diagonal(self, terms, stream=None):
+        """The per-point diagonal of the plan's operator <- sum of coeff * (slot, vec) over `terms` = [(coeff, (slot, vec)), ...]
+        (at most four level-0 vectors of this plan, the arithmetic of lincomb), and the per-point planes of every level below
+        formed again on the device (mgcmt_plan_set_point_diagonal): the plan then holds the bits of a plan created from that
+        diagonal; bonds and the off-centre planes of a stencil stay.  Stream-ordered, no allocation, no synchronisation.
+        From here on the plan no longer describes ``self.op`` (``op_stale`` is set; ``point_stencil(level)`` stays the truth),
+        so it leaves get_plan's cache if it is in it: no later caller is handed a plan with this diagonal.  A plan that left the
+        cache this way belongs to whoever holds it: release_plans() no longer closes it, its holder's close() (or the last
+        reference going away) does."""
+        nt = len(terms)
+        coeffs = np.array([float(c) for c, _ in terms])
+        slots = (ctypes.c_int * nt)(*[v[0] for _, v in terms])
+        vecs = (ctypes.c_int * nt)(*[v[1] for _, v in terms])
+        check(_lib.lib().mgcmt_plan_set_point_diagonal(self._h, nt, _lib.as_dp(coeffs), slots, vecs, stream))
+        self.op_stale = True
+        for key, cached in list(_PLANS.items()):
+            if cached is self:
+                del _PLANS[key]
+
+    def copy_across(self, level, src, other, dst, stream=None):
+        """(slot, vec) `dst` of the plan `other` <- (slot, vec) `src` of this plan on `level`: a device-to-device copy between two
+        plans of the same dimension and level shape on one device (mgcmt_copy_across)."""
+        check(_lib.lib().mgcmt_copy_across(self._h, level, src[0], src[1], other._h, dst[0], dst[1], stream))
 
     def block_project(self, level, b, w, ab=None, aw=None, want_coeffs=False, stream=None):
         """block_deflate with companions: w[j] <- w[j] - sum_i <b[i], w[j]> b[i] and, with ab and aw, aw[j] <- aw[j] -

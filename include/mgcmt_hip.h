@@ -265,7 +265,9 @@ int mgcmt_plan_level_shape(const mgcmt_plan* plan, int level, int64_t* rows, int
 /* host copy of a level's factors, [nterms][3][n] with n = global rows (which=0) or cols (which=1) */
 int mgcmt_plan_get_factors(const mgcmt_plan* plan, int op, int level, int which, double* out, int64_t capacity);
 /* device address of the interior (row 0, col 0) of vector `vec` in `slot` of `level`; rows -halo..-1 and
- * rows..rows+halo-1 are addressable halo rows (halo: mgcmt_plan_level_halo) */
+ * rows..rows+halo-1 are addressable halo rows (halo: mgcmt_plan_level_halo).  The address can be written with no
+ * further call into the library, so from the first mgcmt_vec_ptr on a plan no cycle of that plan carries a right-hand
+ * side to the next (MGCMT_OPT_CARRY), for the rest of the plan's life. */
 int mgcmt_vec_ptr(const mgcmt_plan* plan, int level, int slot, int vec, void** device_ptr);
 /* halo_rows: rows kept above and below every vector of `level` (MGCMT_HALO_ROWS on 2-D levels, 1 on 1-D levels);
  * exchanged_rows: how many of them — the ones next to the strip — a sharded cycle fills with the neighbours' rows and its
@@ -312,7 +314,14 @@ int mgcmt_coarse_solve(mgcmt_plan* plan, int level, int k, void* stream);
 /* State after a cycle: V[level] holds the new iterate and F[l] of every coarser fused level the restricted residual;
  * the iterates V[l] of the coarser levels are scratch (a level run inside a two-level pass, MGCMT_OPT_TWO_LEVEL, is
  * never written).  A caller that wants a coarse iterate sets MGCMT_OPT_TWO_LEVEL to 0.  Slots V, F and T of the coarser
- * levels and slot T of `level` are the cycle's scratch (columns q < k); F[level] and every slot W are not touched. */
+ * levels and slot T of `level` are the cycle's scratch (columns q < k); F[level] and every slot W are not touched.
+ * A carried right-hand side (MGCMT_OPT_CARRY): where the cycle's last launch is the two-level up pass of `level`, the
+ * iterate is not flagged zero and there is no Gram-Schmidt, that pass also computes what the NEXT cycle's down pass would
+ * write to F[level+1] and leaves it in T[level+1] (scratch by the above; F[level+1] keeps this cycle's restricted
+ * residual).  A next mgcmt_vcycle with the same arguments exchanges the two buffers' roles and skips the fine down pass:
+ * the same bits.  Anything else that may change V[level], F[level], T[level+1], the shifts or the options drops the
+ * carry: every entry that takes a non-const plan, except this one, the readers (mgcmt_dot, mgcmt_gram, mgcmt_download)
+ * and mgcmt_apply / _axpy / _copy / _lincomb / _scale into another vector.  mgcmt_vec_ptr turns carrying off for good. */
 int mgcmt_vcycle(mgcmt_plan* plan, int level, int nu1, int nu2, int nu_coarse, int kind, double omega, int k,
                  int cycle_flags, void* stream);
 /* twogrid (:331-371): exact solve of (R A P - mu I) on level+1; scratch: T[level] and V, F, T of level+1 */
@@ -679,6 +688,10 @@ typedef enum mgcmt_option {
                                role with p every iteration), 0 = the generic passes; both give the same p and q bit for bit.  Not set
                                (or a negative value): the environment variable MGCMT_PCG_MARCH, read per call, else 1 (the faster
                                iteration at 8192^2) */
+  MGCMT_OPT_CARRY = 10,     /* default 1: on fine levels of >= 2^22 points a V(nu1 <= 2, 2) weighted-Jacobi cycle on a nonzero iterate
+                               whose top pair runs as two-level passes ends in an up pass that carries the next cycle's F[level+1]
+                               (see mgcmt_vcycle); after two carries in a row that the caller let go unused, none is produced until a
+                               cycle again follows one with the same arguments; 2: wherever eligible; 0: never.  The same bits */
   MGCMT_OPT_TAIL = 4        /* default 1: the 2-D levels of at most 32 x 32 points below a cycle's top level, coarse solve
                                included, run as ONE launch (needs MGCMT_OPT_FUSED; not with Gram-Schmidt): a dense product
                                with the tail's matrix — the sub-cycle is linear in its right-hand side for fixed shift,
@@ -687,6 +700,8 @@ typedef enum mgcmt_option {
                                dense form's arithmetic in another summation order); 0: one launch per pass */
 } mgcmt_option;
 int mgcmt_plan_set_option(mgcmt_plan* plan, int option, int value);
+/* pending = 1 while T[level+1] holds a right-hand side that the last mgcmt_vcycle carried for its successor, else 0 */
+int mgcmt_carry_pending(const mgcmt_plan* plan, int* pending);
 
 /* timing of the dominant kernel for bench.py: runs `reps` fine-level smoother sweeps between two
  * HIP events on `stream` and returns the elapsed milliseconds */

@@ -32,6 +32,7 @@ OPT_GRAPH = 2
 OPT_RECOMPUTE = 3
 OPT_TWO_LEVEL = 8
 OPT_PCG_MARCH = 9
+OPT_CARRY = 10
 
 
 class MgcmtError(RuntimeError):
@@ -184,6 +185,7 @@ _SIGNATURES = {
     "mgcmt_csr_smooth": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p]),
     "mgcmt_csr_vcycle": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p]),
     "mgcmt_plan_set_option": (c_int, [c_void_p, c_int, c_int]),
+    "mgcmt_carry_pending": (c_int, [c_void_p, POINTER(c_int)]),
     "mgcmt_bandwidth_probe": (c_int, [c_void_p, c_int, c_int, c_int, c_int, _dp, c_void_p]),
     "mgcmt_lex_wave_stats": (c_int, [c_void_p, POINTER(ctypes.c_uint32), c_int64]),
     "mgcmt_time_smoother": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_int, _dp, c_void_p]),

@@ -396,11 +396,13 @@ bool two_level_ok(const mgcmt_plan* p, int l, int bottom, int kind, int nu, int 
   return p->two_level == 2 || p->interior(l) >= (1L << 22);
 }
 
-int two_level_launch(mgcmt_plan* p, int l, int up, int nf, bool zero_in, double omega, int k, hipStream_t s) {
+// carry (an up pass on a nonzero iterate only): the pass also leaves the next cycle's F[l+1] in T[l+1]
+int two_level_launch(mgcmt_plan* p, int l, int up, int nf, bool zero_in, double omega, int k, hipStream_t s, bool carry = false) {
   const Level &L0 = p->levels[l], &L1 = p->levels[l + 1], &L2 = p->levels[l + 2];
   launch_fused2(s, up, nf, zero_in ? 1 : 0, L0.dA.k, L1.dA.k, L0.gr, L0.gc, L1.gr, L1.gc, L2.gc, p->kvec(l, MGCMT_SLOT_V),
                 p->kvec(l, MGCMT_SLOT_F), p->kvec(l, MGCMT_SLOT_T), p->kvec(l + 1, MGCMT_SLOT_F),
-                p->kvec(l + 2, up ? MGCMT_SLOT_V : MGCMT_SLOT_F), p->d_shifts, omega, k, p->fused_rows);
+                p->kvec(l + 2, up ? MGCMT_SLOT_V : MGCMT_SLOT_F), p->d_shifts, omega, k, p->fused_rows,
+                carry ? p->kvec(l + 1, MGCMT_SLOT_T).p : nullptr);
   return post_launch();
 }
 
@@ -427,14 +429,29 @@ int two_level_down(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, 
 
 // up legs of levels l+1 and l: the two-level pass (V[l] -> V', level l+1's correction and smoothing in registers),
 // then level l's remaining post-smoothing passes
-int two_level_up(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, hipStream_t s, int nf, bool still_zero) {
-  MG_TRY(two_level_launch(p, l, 1, nf, still_zero, omega, k, s));
+int two_level_up(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, hipStream_t s, int nf, bool still_zero, bool carry = false) {
+  MG_TRY(two_level_launch(p, l, 1, nf, still_zero, omega, k, s, carry));
   std::swap(p->levels[l].base[MGCMT_SLOT_V], p->levels[l].base[MGCMT_SLOT_T]);
   for (int left = nu - 2; left > 0;) {
     const int n = pass_sweeps(p, l, kind, left);
     MG_TRY(fused_pass(p, l, kind, n, omega, 0, k, s));
     left -= n;
   }
+  return post_launch();
+}
+
+// The down legs of levels l and l+1 when T[l+1] holds the right-hand side that the last cycle's up pass carried: it
+// becomes F[l+1] (the two roles swap, as V and T do behind a pass), the fine level has nothing left to do, and level
+// l+1 runs its own down pass alone — nu_coarse = 2 sweeps from zero, not stored, residual, restriction to F[l+2] —, which
+// is what the two-level down pass computes behind the fine stages.
+int carried_down(mgcmt_plan* p, int l, int kind, double omega, int k, hipStream_t s) {
+  for (int m = l; m <= l + 2; ++m) {
+    MG_TRY(ensure_slot(p, m, MGCMT_SLOT_V));
+    MG_TRY(ensure_slot(p, m, MGCMT_SLOT_F));
+    MG_TRY(ensure_slot(p, m, MGCMT_SLOT_T));
+  }
+  std::swap(p->levels[l + 1].base[MGCMT_SLOT_F], p->levels[l + 1].base[MGCMT_SLOT_T]);
+  MG_TRY(fused_pass(p, l + 1, kind, 2, omega, 2 | 4 | 8, k, s));
   return post_launch();
 }
 
@@ -672,8 +689,11 @@ int vcycle3_body(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int 
   return MGCMT_OK;
 }
 
+// carry_mode: kCarryProduce — the cycle's last launch, the two-level up pass of `level`, carries the next cycle's
+// F[level+1] (carry_eligible holds); kCarryConsume — the last cycle did, for these parameters
+enum { kCarryProduce = 1, kCarryConsume = 2 };
 int vcycle_body(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int kind, double omega, int k, int cycle_flags,
-                hipStream_t s) {
+                hipStream_t s, int carry_mode = 0) {
   if (p->dim == 3) return vcycle3_body(p, level, nu1, nu2, nu_coarse, kind, omega, k, cycle_flags, s);
   const int gram_schmidt = cycle_flags & MGCMT_CYCLE_GRAM_SCHMIDT;
   // MGCMT_CYCLE_ZERO_START: the caller vouches that the iterate on `level` is zero — the first pass takes that as a
@@ -688,6 +708,13 @@ int vcycle_body(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int k
   for (int l = level; l < bottom; ++l) {
     const int nu_up = l == level ? nu2 : nu_coarse;
     bool sz = false;
+    if (l == level && (carry_mode & kCarryConsume)) {
+      MG_TRY(carried_down(p, l, kind, omega, k, s));
+      recompute[l] = nu1;  // what the skipped down pass would have left: nu1 sweeps to recompute, V not zero
+      paired[l] = 1;
+      ++l;
+      continue;
+    }
     if (two_level_ok(p, l, bottom, kind, l == level ? nu1 : nu_coarse, nu_up, nu_coarse, gram_schmidt)) {
       MG_TRY(two_level_down(p, l, kind, l == level ? nu1 : nu_coarse, omega, k, l > level || zero_start, s, &recompute[l], &sz));
       still_zero[l] = sz;
@@ -704,13 +731,28 @@ int vcycle_body(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int k
   for (int l = bottom - 1; l >= level; --l) {
     if (l > level && paired[l - 1]) continue;  // runs inside level l - 1's up pass
     if (paired[l]) {
-      MG_TRY(two_level_up(p, l, kind, l == level ? nu2 : nu_coarse, omega, k, s, recompute[l], still_zero[l] != 0));
+      MG_TRY(two_level_up(p, l, kind, l == level ? nu2 : nu_coarse, omega, k, s, recompute[l], still_zero[l] != 0,
+                          l == level && (carry_mode & kCarryProduce)));
       continue;
     }
     MG_TRY(up_leg(p, l, kind, l == level ? nu2 : nu_coarse, omega, k, s, recompute[l], still_zero[l] != 0));
     if (gram_schmidt) MG_TRY(gramschmidt_impl(p, l, MGCMT_SLOT_V, k, 1, s));
   }
   return MGCMT_OK;
+}
+
+// May a cycle with these parameters end in a carrying up pass (and the next one start from what it carried)?  The pair
+// (level, level + 1) runs as two-level passes, the up pass is the cycle's last launch (nu2 == 2), the down leg is the
+// single no-store launch (so the up pass recomputes nu1 <= 2 sweeps), no Gram-Schmidt, and the iterate is not flagged
+// zero: a caller that does starts a new problem with every call, one that cycles on a nonzero iterate is iterating.
+bool carry_eligible(const mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int kind, int cycle_flags) {
+  if (p->carry_opt == 0 || p->carry.disabled || p->dim != 2 || cycle_flags != 0 || nu2 != 2 || nu1 < 1 || nu1 > 2) return false;
+  const int last = (int)p->levels.size() - 1;
+  const int lt = tail_level(p, level, kind, nu_coarse, 0);
+  const int bottom = lt > 0 ? lt : last;
+  if (level >= bottom || !two_level_ok(p, level, bottom, kind, nu1, nu2, nu_coarse, 0)) return false;
+  if (last_pass_sweeps(p, level, kind, nu1) != nu1) return false;
+  return p->carry_opt == 2 || p->interior(level) >= (1L << 22);
 }
 
 }  // namespace
@@ -728,6 +770,7 @@ int mgcmt::graph_run(mgcmt_plan* p, const std::string& params, const std::string
       for (Level& L : p->levels) {
         L.base[MGCMT_SLOT_V] = hit->second.post_state[i++];
         L.base[MGCMT_SLOT_T] = hit->second.post_state[i++];
+        L.base[MGCMT_SLOT_F] = hit->second.post_state[i++];
       }
     return MGCMT_OK;
   }
@@ -772,6 +815,7 @@ int mgcmt::graph_run(mgcmt_plan* p, const std::string& params, const std::string
     for (const Level& L : p->levels) {
       cg.post_state.push_back(L.base[MGCMT_SLOT_V]);
       cg.post_state.push_back(L.base[MGCMT_SLOT_T]);
+      cg.post_state.push_back(L.base[MGCMT_SLOT_F]);
     }
   MG_HIP(hipGraphLaunch(cg.exec, s));
   p->graphs[key] = cg;
@@ -781,6 +825,7 @@ int mgcmt::graph_run(mgcmt_plan* p, const std::string& params, const std::string
 extern "C" {
 
 int mgcmt_smooth(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   MG_TRY(check_k(p, k));
   if (nu < 0) return fail(MGCMT_ERR_INVALID, "nu must be >= 0");
@@ -788,18 +833,21 @@ int mgcmt_smooth(mgcmt_plan* p, int l, int kind, int nu, double omega, int k, vo
 }
 
 int mgcmt_residual_restrict(mgcmt_plan* p, int l, int k, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   MG_TRY(check_k(p, k));
   return residual_restrict_impl(p, l, k, S(stream));
 }
 
 int mgcmt_prolong_correct(mgcmt_plan* p, int l, int k, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   MG_TRY(check_k(p, k));
   return prolong_correct_impl(p, l, k, S(stream));
 }
 
 int mgcmt_coarse_solve(mgcmt_plan* p, int l, int k, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   MG_TRY(check_k(p, k));
   return coarse_solve_impl(p, l, k, S(stream));
@@ -807,22 +855,46 @@ int mgcmt_coarse_solve(mgcmt_plan* p, int l, int k, void* stream) {
 
 int mgcmt_vcycle(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int kind, double omega, int k, int cycle_flags,
                  void* stream) {
+  // (no entry_drops_carry: this entry decides itself what becomes of a carried right-hand side)
   MG_TRY(check_level(p, level));
   MG_TRY(check_k(p, k));
-  if (nu1 < 0 || nu2 < 0 || nu_coarse < 0) return fail(MGCMT_ERR_INVALID, "sweep counts must be >= 0");
-  if (cycle_flags & ~(MGCMT_CYCLE_GRAM_SCHMIDT | MGCMT_CYCLE_ZERO_START)) return fail(MGCMT_ERR_INVALID, "unknown cycle flag");
-  MG_TRY(unsupported_point_smoother(p, kind));
-  hipStream_t s = S(stream);
-  auto body = [&](hipStream_t on) { return vcycle_body(p, level, nu1, nu2, nu_coarse, kind, omega, k, cycle_flags, on); };
-  if (!p->use_graph) return body(s);
-
-  // HIP-graph replay: the launch sequence is fixed by the parameters and by which buffer of every level currently is V
   char buf[160];
   snprintf(buf, sizeof(buf), "%d/%d/%d/%d/%d/%.17g/%d/%d", level, nu1, nu2, nu_coarse, kind, omega, k, cycle_flags);
   const std::string params(buf);
-  std::string key = params;
+  // The carry: used if the last cycle left one for exactly these parameters and nothing has touched the plan since
+  // (any entry that could have dropped it), produced if this cycle may and the caller has not let two in a row go unused
+  // — until a cycle again follows one of its own kind.
+  mgcmt_plan::Carry& C = p->carry;
+  const bool consume = C.valid && C.level == level && C.nu1 == nu1 && C.nu2 == nu2 && C.nu_coarse == nu_coarse && C.kind == kind &&
+                       C.omega == omega && C.k == k && C.flags == cycle_flags &&
+                       carry_eligible(p, level, nu1, nu2, nu_coarse, kind, cycle_flags);  // (still: nothing that changes it keeps a carry)
+  const bool follows_its_kind = C.prev == params;
+  p->carry_drop();
+  if (consume || follows_its_kind) C.unused_drops = 0;
+  if (nu1 < 0 || nu2 < 0 || nu_coarse < 0) return fail(MGCMT_ERR_INVALID, "sweep counts must be >= 0");
+  if (cycle_flags & ~(MGCMT_CYCLE_GRAM_SCHMIDT | MGCMT_CYCLE_ZERO_START)) return fail(MGCMT_ERR_INVALID, "unknown cycle flag");
+  MG_TRY(unsupported_point_smoother(p, kind));
+  const bool produce = C.unused_drops < 2 && carry_eligible(p, level, nu1, nu2, nu_coarse, kind, cycle_flags);
+  const int carry_mode = (produce ? kCarryProduce : 0) | (consume ? kCarryConsume : 0);
+  hipStream_t s = S(stream);
+  auto body = [&](hipStream_t on) { return vcycle_body(p, level, nu1, nu2, nu_coarse, kind, omega, k, cycle_flags, on, carry_mode); };
+  auto done = [&](int rc) {
+    if (rc != MGCMT_OK) return rc;
+    C.prev = params;
+    C.level = level, C.nu1 = nu1, C.nu2 = nu2, C.nu_coarse = nu_coarse, C.kind = kind, C.k = k, C.flags = cycle_flags;
+    C.omega = omega;
+    C.valid = produce;
+    return rc;
+  };
+  if (!p->use_graph) return done(body(s));
+
+  // HIP-graph replay: the launch sequence is fixed by the parameters, by what the cycle does about a carry and by which
+  // buffer of every level currently is V, T and F (`params` stays free of the carry: the cycles of one run share the
+  // eager first call)
+  snprintf(buf, sizeof(buf), "/c%d", carry_mode);
+  std::string key = params + buf;
   for (const Level& L : p->levels) {
-    snprintf(buf, sizeof(buf), "|%p,%p", (void*)L.base[MGCMT_SLOT_V], (void*)L.base[MGCMT_SLOT_T]);
+    snprintf(buf, sizeof(buf), "|%p,%p,%p", (void*)L.base[MGCMT_SLOT_V], (void*)L.base[MGCMT_SLOT_T], (void*)L.base[MGCMT_SLOT_F]);
     key += buf;
   }
   // the coarsest-level factorisation (and the tail's matrix) depend on the shift VALUES and on the per-point planes; redo them
@@ -831,10 +903,11 @@ int mgcmt_vcycle(mgcmt_plan* p, int level, int nu1, int nu2, int nu_coarse, int 
     MG_TRY(ensure_coarse_factor(p, (int)p->levels.size() - 1, k, s));
     return ensure_tail_for_cycle(p, level, nu_coarse, kind, omega, k, cycle_flags, s);
   };
-  return graph_run(p, params, key, /*swaps_buffers=*/true, prepare, body, s);
+  return done(graph_run(p, params, key, /*swaps_buffers=*/true, prepare, body, s));
 }
 
 int mgcmt_twogrid(mgcmt_plan* p, int level, int nu1, int nu2, int kind, double omega, int k, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_twogrid"));
   MG_TRY(mgcmt::unsupported_point(p, "mgcmt_twogrid"));
   MG_TRY(check_level(p, level));

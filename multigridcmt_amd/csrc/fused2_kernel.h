@@ -31,6 +31,7 @@ struct Fused2Args {
   const double* f;         // fine F
   double* vout;            // fine V' (up)
   double* f1;              // F[l+1]: written (down) / read (up)
+  double* fcarry;          // carrying up pass: the next cycle's F[l+1], written (never F[l+1] itself: other waves read it)
   double* c2;              // F[l+2] written (down) / V[l+2] read (up)
   long s0, s1, s2;         // vector strides of the three levels
   int nr, nc, cnr, cnc, c2nc;
@@ -46,16 +47,33 @@ struct Fused2Shape {
 
 // UP = false: NF = fine sweeps of the down pass.  UP = true: NF = fine sweeps recomputed in front of the correction
 // (the fine post-smoothing is 2 sweeps; level l+1 smooths 2 sweeps per leg).
-template <bool UP, int NF, bool ZERO_IN>
+//
+// CARRY (up only): the pass goes on, behind the stage that stores row rs of V', with the fine part of the NEXT cycle's
+// down pass on the rows it holds in registers — NF sweeps (not stored), the residual, the restriction — and stores that
+// cycle's F[l+1] through a.fcarry.  The stages are the down branch's (eval_a / eval_b, racc, the store predicate), their
+// input is the row just stored instead of a loaded one, so the values are the bits the next down pass would write.
+//   columns: V' is good 12 fine columns inside the window (above); a sweep and the residual reach one column further
+//   each, the restriction of the last owned coarse column reads the residual of the next lane's first column: NF + 1
+//   more columns on the left, NF + 2 on the right — within the 16 of H = 8 for NF <= 2.
+//   rows: the residual of row r_begin (the first that a coarse row of the chunk takes) needs V' from row
+//   r_begin - 1 - NF on: the march starts 4 rows earlier; the residual of row r_end is the last, NF + 2 steps behind
+//   the last stored row of V'.
+template <bool UP, int NF, bool ZERO_IN, bool CARRY = false>
 __global__ void __launch_bounds__(64) k_fused2(Fused2Args a) {
   using Shape = Fused2Shape<UP>;
   constexpr int H = Shape::H, WOUT = Shape::wout, B = Shape::B;
+  static_assert(!CARRY || (UP && !ZERO_IN), "only an up pass on a nonzero iterate carries");
+  static_assert(!CARRY || 12 + NF + 2 <= 2 * H, "the carried stages must stay inside the halo");
   constexpr int SF = UP ? NF + 2 : NF;     // fine smoothing stages
   constexpr int EF = UP ? 0 : 1;           // fine residual stage (down)
+  constexpr int TF = CARRY ? NF + 1 : 0;   // carried stages behind the store of V': NF sweeps and the residual
+  constexpr int SR = UP ? (CARRY ? SF + NF : -1) : SF;  // index of the residual stage (-1: none)
   constexpr int SC = UP ? 4 : 2;           // coarse smoothing stages
   constexpr int PC = UP ? 0 : (NF + 1) & 1;  // parity of the fine steps that carry a coarse step
   constexpr int CROW = UP ? 4 : -2;        // coarse input row of a coarse step = base / 2 + U + CROW
   // rows per prefetch batch: the up pass's seven stage windows leave room for two (three: 256 + registers, 1 wave/SIMD)
+  // (the carrying pass with NF = 2 is over 256 registers and runs 1 wave / SIMD either way; 3, 4 and 6 rows per batch
+  // measured no faster there than 2: profiles/r20_carry.md)
   constexpr int D = UP ? 2 : kDepth;
   constexpr int NS = 2;
   static_assert(B % D == 0 && (B / D) % NS == 0, "the loop body must hold whole rotations of the prefetch sets");
@@ -104,15 +122,17 @@ __global__ void __launch_bounds__(64) k_fused2(Fused2Args a) {
   double* __restrict__ vout = a.vout + q * a.s0;
   double* __restrict__ f1 = a.f1 + q * a.s1;
   double* __restrict__ c2 = a.c2 + q * a.s2;
+  double* __restrict__ fres = CARRY ? a.fcarry + q * a.s1 : f1;  // where the restricted fine residual goes
 
   const int r_begin = chunk * a.rows_per_chunk;  // (a multiple of 4)
   const int r_end = r_begin + a.rows_per_chunk < nr ? r_begin + a.rows_per_chunk : nr;
   const int crow_b = r_begin >> 1, crow_e = r_end >> 1;  // coarse rows of the chunk
   // first fine step: down — F[l+1] rows from crow_b - 2 on feed level l+1's stages, they need fine rows from r_begin - 7;
   // up — v1 rows from crow_b - 2 on, i.e. F[l+1] rows from crow_b - 6 on, loaded 4 coarse rows ahead of the fine stream
-  const int rstart = UP ? r_begin - 20 : r_begin - 8;
-  // one past the last step: down — the last level-l+2 row (coarse row crow_e + 3 in); up — the last V' row
-  const int rstop = UP ? r_end + SF : r_end + 10 + NF;
+  const int rstart = UP ? (CARRY ? r_begin - 24 : r_begin - 20) : r_begin - 8;
+  // one past the last step: down — the last level-l+2 row (coarse row crow_e + 3 in); up — the last V' row (carrying:
+  // the residual of row r_end)
+  const int rstop = UP ? (CARRY ? r_end + SF + NF + 2 : r_end + SF) : r_end + 10 + NF;
 
   const int ja_ld = ja < 0 ? 0 : (ja > nc - 2 ? nc - 2 : ja);
   const int jc_ld = jc < 0 ? 0 : (jc > cnc - 1 ? cnc - 1 : jc);
@@ -153,7 +173,8 @@ __global__ void __launch_bounds__(64) k_fused2(Fused2Args a) {
   });
 
   // fine stage windows (w[s]: input of stage s + 1; w[SF]: the residual stage's), rotating as in k_fused
-  constexpr int NW = SF + EF;
+  constexpr int NW = SF + EF + TF;
+  static_assert(NW < B, "the right-hand side ring must hold the lag of the last stage");
   double wa[NW][3], wb[NW][3];
 #pragma unroll
   for (int s = 0; s < NW; ++s)
@@ -295,8 +316,7 @@ __global__ void __launch_bounds__(64) k_fused2(Fused2Args a) {
     fb[T] = in.f.y;
     double oa = ina, ob = inb;
 #pragma unroll
-    for (int s = 0; s <= SF; ++s) {
-      if (s == SF && UP) break;
+    for (int s = 0; s < NW; ++s) {
       const int sn = mod3(T - s), sa = mod3(T - s + 1), sc = mod3(T - s + 2);
       wa[s][sn] = oa;
       wb[s][sn] = ob;
@@ -314,7 +334,7 @@ __global__ void __launch_bounds__(64) k_fused2(Fused2Args a) {
         op.template eval<1>(n, c, so, off, dg, inv);
       };
       const bool in_grid = !CHK || ((okbits >> (s + 1)) & 1u) != 0;
-      if (s < SF) {
+      if (s != SR) {
         double na = ca, nb = cb;
         if (in_grid) {
           double off, dg, inv;
@@ -344,7 +364,7 @@ __global__ void __launch_bounds__(64) k_fused2(Fused2Args a) {
         if (((T - (s + 1)) & 1) == 0) {
           const int I = (rs >> 1) - 1;
           const double v1 = racc + 0.25 * h;
-          if (own && ccol_in && (!CHK || (I >= crow_b && I < crow_e))) f1[(long)I * cnc + jc] = v1;
+          if (own && ccol_in && (!CHK || (I >= crow_b && I < crow_e))) fres[(long)I * cnc + jc] = v1;
           racc = 0.25 * h;
           if constexpr (!UP && CSTEP) coarse_step(StepIndex<U>{}, chk, I, v1, 0.0);
         } else {
@@ -371,7 +391,10 @@ __global__ void __launch_bounds__(64) k_fused2(Fused2Args a) {
   };
   // Bodies whose every row is inside both grids, off level l+1's last row, and whose every store lies inside the
   // chunk run without row tests (see k_fused)
-  const int fast_lo = UP ? r_begin + 4 : r_begin + 14;
+  // (carrying: the first coarse row stored without a test is row crow_b, restricted from the residual of row r_begin + 2)
+  const int fast_lo = UP ? (CARRY ? r_begin + SF + NF + 3 : r_begin + 4) : r_begin + 14;
+  // (carrying: fast_last does not grow with the tail's lag — the last row of V' stored without a test, r_end - 1 at step
+  // r_end - 1 + SF, bounds it as before; the carried coarse rows of such a body lie NF + 1 steps further back, below crow_e)
   int fast_last = UP ? (r_end - 12 + SF < nr - 20 ? r_end - 12 + SF : nr - 20) : (r_end - 8 < nr - 12 ? r_end - 8 : nr - 12);
   int base = rstart;
 #pragma nounroll
@@ -394,7 +417,7 @@ __global__ void __launch_bounds__(64) k_fused2(Fused2Args a) {
   }
 }
 
-template <bool UP, int NF, bool ZERO_IN>
+template <bool UP, int NF, bool ZERO_IN, bool CARRY = false>
 void launch_two(hipStream_t s, Fused2Args a, int k, long rows_override) {
   using Shape = Fused2Shape<UP>;
   const long groups = (a.nc + Shape::wout - 1) / Shape::wout;
@@ -404,7 +427,7 @@ void launch_two(hipStream_t s, Fused2Args a, int k, long rows_override) {
   if (resident_blocks == 0) {
     int per_cu = 0, dev = 0;
     hipDeviceProp_t prop;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fused2<UP, NF, ZERO_IN>, 64, 0) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fused2<UP, NF, ZERO_IN, CARRY>, 64, 0) != hipSuccess ||
         hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || per_cu < 1)
       resident_blocks = 768;
     else
@@ -424,7 +447,7 @@ void launch_two(hipStream_t s, Fused2Args a, int k, long rows_override) {
   a.n_row_chunks = (int)((nrows + rows - 1) / rows);
   a.xcd_balanced = (groups8 * 100 > groups * (100 + MGCMT_FUSED_XCD_IMBALANCE) && groups < MGCMT_FUSED_XCD_MAXGROUPS) ? 1 : 0;
   const unsigned blocks = (unsigned)(groups8 * a.n_row_chunks);
-  hipLaunchKernelGGL((k_fused2<UP, NF, ZERO_IN>), dim3(blocks, (unsigned)k), dim3(64), 0, s, a);
+  hipLaunchKernelGGL((k_fused2<UP, NF, ZERO_IN, CARRY>), dim3(blocks, (unsigned)k), dim3(64), 0, s, a);
 }
 
 }  // namespace fused

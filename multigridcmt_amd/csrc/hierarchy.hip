@@ -628,6 +628,7 @@ int mgcmt_plan_get_point_stencil(const mgcmt_plan* p, int l, double* out, int64_
 }
 
 int mgcmt_plan_set_point_diagonal(mgcmt_plan* p, int nterms, const double* coeffs, const int* slots, const int* vecs, void* stream) {
+  entry_drops_carry(p);
   if (!p) return fail(MGCMT_ERR_INVALID, "null plan");
   if (!p->has_point) return fail(MGCMT_ERR_INVALID, "plan has no point diagonal");
   if (!coeffs || !slots || !vecs || nterms < 1 || nterms > 4) return fail(MGCMT_ERR_INVALID, "set_point_diagonal: 1..4 terms, non-null arguments");
@@ -727,6 +728,7 @@ int mgcmt_plan_create3d_mass(const mgcmt_plan3d_desc* d, int32_t m_nterms, const
 }
 
 int mgcmt_plan_destroy(mgcmt_plan* p) {
+  entry_drops_carry(p);
   if (!p) return MGCMT_OK;
   comm_release(p);
   for (Level& L : p->levels) {

@@ -5,7 +5,8 @@
 namespace mgcmt {
 
 void launch_fused2(hipStream_t s, int up, int nf, int zero_in, const KOp& op0, const KOp& op1, long nr, long nc, long cnr, long cnc,
-                   long c2nc, KVec v, KVec f, KVec vout, KVec f1, KVec c2, const double* shifts, double omega, int k, long rows_override) {
+                   long c2nc, KVec v, KVec f, KVec vout, KVec f1, KVec c2, const double* shifts, double omega, int k, long rows_override,
+                   double* fcarry) {
   using namespace fused;
   Fused2Args a{};
   a.fine.c0 = op0.c0;
@@ -35,7 +36,12 @@ void launch_fused2(hipStream_t s, int up, int nf, int zero_in, const KOp& op0, c
   a.cnr = (int)cnr;
   a.cnc = (int)cnc;
   a.c2nc = (int)c2nc;
-  if (up) {
+  a.fcarry = fcarry;
+  if (fcarry) {
+    // (cycle.hip asks for a carrying pass only as an up pass on a nonzero iterate)
+    if (nf == 1) launch_two<true, 1, false, true>(s, a, k, rows_override);
+    else launch_two<true, 2, false, true>(s, a, k, rows_override);
+  } else if (up) {
     if (nf == 1) zero_in ? launch_two<true, 1, true>(s, a, k, rows_override) : launch_two<true, 1, false>(s, a, k, rows_override);
     else zero_in ? launch_two<true, 2, true>(s, a, k, rows_override) : launch_two<true, 2, false>(s, a, k, rows_override);
   } else {

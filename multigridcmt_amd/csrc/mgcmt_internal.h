@@ -200,8 +200,12 @@ void launch_fused(hipStream_t s, KGrid g, KOp op, KVec vin, KVec f, KVec vout, K
 // up = 0: nf sweeps from v (zero_in: v is zero) -> residual -> F[l+1] (f1) -> 2 sweeps of level l+1 from zero ->
 // residual -> F[l+2] (c2).  up = 1: level l+1 recomputes its 2 pre-sweeps from zero, adds P V[l+2] (c2), 2 sweeps;
 // level l recomputes nf pre-sweeps from v, adds P of that, 2 sweeps -> vout.  V[l+1] is neither read nor written.
+// fcarry (up = 1, zero_in = 0 only; null: none): the carrying up pass — behind vout it runs nf sweeps, the residual and
+// the restriction on the rows it holds, and writes what the next cycle's down pass would write to F[l+1] to fcarry
+// (same layout as f1, a different buffer: f1 is read by the same launch).
 void launch_fused2(hipStream_t s, int up, int nf, int zero_in, const KOp& op0, const KOp& op1, long nr, long nc, long cnr, long cnc,
-                   long c2nc, KVec v, KVec f, KVec vout, KVec f1, KVec c2, const double* shifts, double omega, int k, long rows_override);
+                   long c2nc, KVec v, KVec f, KVec vout, KVec f1, KVec c2, const double* shifts, double omega, int k, long rows_override,
+                   double* fcarry = nullptr);
 
 // vector algebra; scalar results / inputs live in device memory so nothing syncs with the host
 void launch_fill(hipStream_t s, double* p, long n, double value);

@@ -177,28 +177,35 @@ extern "C" {
 
 // The six entries: argument handling around the driver.  The single ones pass k = 1 and take column 0 into their scalar outputs
 int mgcmt_pcg_begin(mgcmt_plan* p, const int* vecs, double rtol, int flags, void* stream) {
+  entry_drops_carry(p);
   return pcg_begin(p, mgcmt_plan::kPcgSingle, 1, vecs, rtol, flags, stream);
 }
 int mgcmt_pcg_begin_k(mgcmt_plan* p, int k, const int* vecs, double rtol, int flags, void* stream) {
+  entry_drops_carry(p);
   return pcg_begin(p, mgcmt_plan::kPcgBatched, k, vecs, rtol, flags, stream);
 }
 int mgcmt_pcg_iterate(mgcmt_plan* p, int iterations, int nu1, int nu2, int nu_coarse, int kind, double omega, void* stream) {
+  entry_drops_carry(p);
   return pcg_iterate(p, mgcmt_plan::kPcgSingle, iterations, nu1, nu2, nu_coarse, kind, omega, stream);
 }
 int mgcmt_pcg_iterate_k(mgcmt_plan* p, int iterations, int nu1, int nu2, int nu_coarse, int kind, double omega, void* stream) {
+  entry_drops_carry(p);
   return pcg_iterate(p, mgcmt_plan::kPcgBatched, iterations, nu1, nu2, nu_coarse, kind, omega, stream);
 }
 int mgcmt_pcg_status(mgcmt_plan* p, int* iterations_done, int* status, double* fnorm, double* history, int capacity, void* stream) {
+  entry_drops_carry(p);
   if (capacity > MGCMT_RQ_HISTORY) capacity = MGCMT_RQ_HISTORY;  // (one row: what lies behind the history stays the caller's, not cleared)
   return pcg_status(p, mgcmt_plan::kPcgSingle, nullptr, iterations_done, status, fnorm, history, capacity, stream);
 }
 int mgcmt_pcg_status_k(mgcmt_plan* p, int* running, int* iterations_done, int* status, double* fnorm, double* history, int capacity, void* stream) {
+  entry_drops_carry(p);
   return pcg_status(p, mgcmt_plan::kPcgBatched, running, iterations_done, status, fnorm, history, capacity, stream);
 }
 
 // Timing for scripts/bench_pcg.py: average milliseconds of `reps` launches of ONE pass of an iteration, with the scalar kernel
 // that follows it, between two HIP events (one untimed launch first), on the vectors and the columns of the solve in progress
 int mgcmt_pcg_time_pass(mgcmt_plan* p, int pass, int reps, double* ms_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(pcg_plan_check(p, "pcg_time_pass"));
   if (!ms_out || reps < 1 || pass < 0 || pass > MGCMT_PCG_PASS_MARCH) return fail(MGCMT_ERR_INVALID, "pcg_time_pass: bad arguments");
   if (p->pcg_kind == mgcmt_plan::kPcgNone) return fail(MGCMT_ERR_INVALID, "pcg_time_pass: no mgcmt_pcg_begin on this plan");

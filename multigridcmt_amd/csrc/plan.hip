@@ -105,12 +105,16 @@ int mgcmt_device_name(int device, char* buf, int buflen) {
 int mgcmt_vec_ptr(const mgcmt_plan* p, int l, int slot, int vec, void** device_ptr) {
   MG_TRY(check_vec(p, l, slot, vec));
   if (!device_ptr) return fail(MGCMT_ERR_INVALID, "null pointer");
+  // a raw address can be written with no further call: no carried right-hand side can be vouched for from here on
+  const_cast<mgcmt_plan*>(p)->carry_drop();
+  const_cast<mgcmt_plan*>(p)->carry.disabled = true;
   MG_TRY(ensure_slot(const_cast<mgcmt_plan*>(p), l, slot));
   *device_ptr = p->kvec(l, slot, vec).p;
   return MGCMT_OK;
 }
 
 int mgcmt_set_shifts(mgcmt_plan* p, const double* shifts, int k, void* stream) {
+  entry_drops_carry(p);
   if (!p || !shifts) return fail(MGCMT_ERR_INVALID, "null argument");
   MG_TRY(check_k(p, k));
   for (int q = 0; q < k; ++q) p->h_shifts[q] = shifts[q];
@@ -121,6 +125,7 @@ int mgcmt_set_shifts(mgcmt_plan* p, const double* shifts, int k, void* stream) {
 }
 
 int mgcmt_upload(mgcmt_plan* p, int l, int slot, int vec, const double* host, int64_t count, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_vec(p, l, slot, vec));
   if (!host || count != p->interior(l)) return fail(MGCMT_ERR_INVALID, "upload: count must equal rows*cols of the level");
   MG_TRY(ensure_slot(p, l, slot));
@@ -128,6 +133,7 @@ int mgcmt_upload(mgcmt_plan* p, int l, int slot, int vec, const double* host, in
 }
 
 int mgcmt_download(mgcmt_plan* p, int l, int slot, int vec, double* host, int64_t count, void* stream) {
+  CarryKeep keep(p);  // a reader
   MG_TRY(check_vec(p, l, slot, vec));
   if (!host || count != p->interior(l)) return fail(MGCMT_ERR_INVALID, "download: count must equal rows*cols of the level");
   MG_TRY(ensure_slot(p, l, slot));
@@ -136,6 +142,7 @@ int mgcmt_download(mgcmt_plan* p, int l, int slot, int vec, double* host, int64_
 }
 
 int mgcmt_fill(mgcmt_plan* p, int l, int slot, int vec, double value, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_vec(p, l, slot, vec));
   MG_TRY(ensure_slot(p, l, slot));
   launch_fill(S(stream), p->kvec(l, slot, vec).p, p->interior(l), value);
@@ -143,6 +150,7 @@ int mgcmt_fill(mgcmt_plan* p, int l, int slot, int vec, double value, void* stre
 }
 
 int mgcmt_zero(mgcmt_plan* p, int l, int slot, int vec, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_vec(p, l, slot, vec));
   MG_TRY(ensure_slot(p, l, slot));
   const Level& L = p->levels[l];
@@ -151,6 +159,8 @@ int mgcmt_zero(mgcmt_plan* p, int l, int slot, int vec, void* stream) {
 }
 
 int mgcmt_copy(mgcmt_plan* p, int l, int src_slot, int src_vec, int dst_slot, int dst_vec, void* stream) {
+  CarryKeep keep(p);
+  keep.writes(l, dst_slot, dst_vec);
   MG_TRY(check_vec(p, l, src_slot, src_vec));
   MG_TRY(check_vec(p, l, dst_slot, dst_vec));
   MG_TRY(ensure_slot(p, l, src_slot));
@@ -161,6 +171,8 @@ int mgcmt_copy(mgcmt_plan* p, int l, int src_slot, int src_vec, int dst_slot, in
 }
 
 int mgcmt_copy_across(mgcmt_plan* src, int l, int src_slot, int src_vec, mgcmt_plan* dst, int dst_slot, int dst_vec, void* stream) {
+  entry_drops_carry(src);
+  entry_drops_carry(dst);
   MG_TRY(check_vec(src, l, src_slot, src_vec));
   MG_TRY(check_vec(dst, l, dst_slot, dst_vec));
   if (src->dim != dst->dim) return fail(MGCMT_ERR_INVALID, "copy_across: the plans differ in dimension");
@@ -184,6 +196,8 @@ int mgcmt_sync(void* stream) {
 }
 
 int mgcmt_apply(mgcmt_plan* p, int op, int l, int src_slot, int src_vec, int dst_slot, int dst_vec, int with_shift, void* stream) {
+  CarryKeep keep(p);
+  keep.writes(l, dst_slot, dst_vec);
   MG_TRY(check_vec(p, l, src_slot, src_vec));
   MG_TRY(check_vec(p, l, dst_slot, dst_vec));
   if (src_slot == dst_slot && src_vec == dst_vec) return fail(MGCMT_ERR_INVALID, "apply cannot run in place");
@@ -204,6 +218,7 @@ int mgcmt_apply(mgcmt_plan* p, int op, int l, int src_slot, int src_vec, int dst
 }
 
 int mgcmt_restrict(mgcmt_plan* p, int l, int src_slot, int src_vec, int dst_slot, int dst_vec, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_vec(p, l, src_slot, src_vec));
   MG_TRY(check_vec(p, l + 1, dst_slot, dst_vec));
   MG_TRY(ensure_slot(p, l, src_slot));
@@ -217,6 +232,7 @@ int mgcmt_restrict(mgcmt_plan* p, int l, int src_slot, int src_vec, int dst_slot
 }
 
 int mgcmt_prolong(mgcmt_plan* p, int l, int src_slot, int src_vec, int dst_slot, int dst_vec, int accumulate, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_vec(p, l + 1, src_slot, src_vec));
   MG_TRY(check_vec(p, l, dst_slot, dst_vec));
   MG_TRY(ensure_slot(p, l + 1, src_slot));
@@ -230,6 +246,7 @@ int mgcmt_prolong(mgcmt_plan* p, int l, int src_slot, int src_vec, int dst_slot,
 }
 
 int mgcmt_dot(mgcmt_plan* p, int l, int slot_a, int vec_a, int slot_b, int vec_b, double* host_out, void* stream) {
+  CarryKeep keep(p);  // a reader
   MG_TRY(check_vec(p, l, slot_a, vec_a));
   MG_TRY(check_vec(p, l, slot_b, vec_b));
   if (!host_out) return fail(MGCMT_ERR_INVALID, "null output");
@@ -243,6 +260,7 @@ int mgcmt_dot(mgcmt_plan* p, int l, int slot_a, int vec_a, int slot_b, int vec_b
 }
 
 int mgcmt_gram(mgcmt_plan* p, int l, int nv, const int* slots, const int* vecs, double* host_out, void* stream) {
+  CarryKeep keep(p);  // a reader
   MG_TRY(check_level(p, l));
   if (!slots || !vecs || !host_out || nv < 1 || nv > kGramMaxVectors) return fail(MGCMT_ERR_INVALID, "gram: 1..6 vectors, non-null arguments");
   const double* v[kGramMaxVectors];
@@ -266,6 +284,8 @@ int mgcmt_gram(mgcmt_plan* p, int l, int nv, const int* slots, const int* vecs, 
 
 int mgcmt_lincomb(mgcmt_plan* p, int l, int nterms, const double* coeffs, const int* slots, const int* vecs, int dst_slot, int dst_vec,
                   void* stream) {
+  CarryKeep keep(p);
+  keep.writes(l, dst_slot, dst_vec);
   MG_TRY(check_level(p, l));
   if (!coeffs || !slots || !vecs || nterms < 1 || nterms > 4) return fail(MGCMT_ERR_INVALID, "lincomb: 1..4 terms, non-null arguments");
   MG_TRY(check_vec(p, l, dst_slot, dst_vec));
@@ -282,6 +302,7 @@ int mgcmt_lincomb(mgcmt_plan* p, int l, int nterms, const double* coeffs, const 
 
 int mgcmt_block_gram(mgcmt_plan* p, int l, int na, const int* a_slots, const int* a_vecs, int nb, const int* b_slots, const int* b_vecs,
                      double* host_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   if (!a_slots || !a_vecs || !b_slots || !b_vecs || !host_out || na < 1 || na > kBlockMaxA || nb < 1 || nb > kBlockMaxB)
     return fail(MGCMT_ERR_INVALID, "block_gram: 1..12 by 1..4 vectors, non-null arguments");
@@ -308,6 +329,7 @@ int mgcmt_block_gram(mgcmt_plan* p, int l, int na, const int* a_slots, const int
 
 int mgcmt_block_combine(mgcmt_plan* p, int l, int nin, const int* in_slots, const int* in_vecs, int nout, const int* out_slots,
                         const int* out_vecs, const double* coeffs, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   if (!in_slots || !in_vecs || !out_slots || !out_vecs || !coeffs || nin < 1 || nin > kBlockMaxA || nout < 1 || nout > kBlockMaxB)
     return fail(MGCMT_ERR_INVALID, "block_combine: 1..12 inputs, 1..4 outputs, non-null arguments");
@@ -356,6 +378,7 @@ static int wide_scratch(mgcmt_plan* p, size_t need, hipStream_t stream) {
 
 int mgcmt_block_pencil(mgcmt_plan* p, int l, int m, const int* s_slots, const int* s_vecs, const int* as_slots, const int* as_vecs,
                        const int* ms_slots, const int* ms_vecs, double* h_out, double* g_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   if (!s_slots || !s_vecs || !as_slots || !as_vecs || !h_out || !g_out || (ms_slots == nullptr) != (ms_vecs == nullptr) || m < 1 || m > kBlockWideMax)
     return fail(MGCMT_ERR_INVALID, "block_pencil: 1..48 vectors, non-null arguments (ms_slots and ms_vecs both null: M = I)");
@@ -393,6 +416,7 @@ int mgcmt_block_pencil(mgcmt_plan* p, int l, int m, const int* s_slots, const in
 
 int mgcmt_block_combine_wide(mgcmt_plan* p, int l, int nin, const int* in_slots, const int* in_vecs, int nout, const int* out_slots,
                              const int* out_vecs, const double* coeffs, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   if (!in_slots || !in_vecs || !out_slots || !out_vecs || !coeffs || nin < 1 || nin > kBlockWideMax || nout < 1 || nout > kBlockWideOut)
     return fail(MGCMT_ERR_INVALID, "block_combine_wide: 1..48 inputs, 1..16 outputs, non-null arguments");
@@ -410,6 +434,7 @@ int mgcmt_block_combine_wide(mgcmt_plan* p, int l, int nin, const int* in_slots,
 
 int mgcmt_block_deflate(mgcmt_plan* p, int l, int nq, const int* q_slots, const int* q_vecs, int k, const int* w_slots, const int* w_vecs,
                         double* coeffs_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   if (nq < 1 || nq > kBlockLockedMax || k < 1 || k > kBlockWideOut)
     return fail(MGCMT_ERR_INVALID, "block_deflate: 1..64 vectors Q, 1..16 vectors W");
@@ -441,6 +466,7 @@ int mgcmt_block_deflate(mgcmt_plan* p, int l, int nq, const int* q_slots, const 
 
 int mgcmt_block_density(mgcmt_plan* p, int l, int nq, const int* x_slots, const int* x_vecs, const double* weights, int dst_slot, int dst_vec,
                         void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   if (nq < 1 || nq > kBlockLockedMax) return fail(MGCMT_ERR_INVALID, "block_density: 1..64 vectors X");
   if (!x_slots || !x_vecs || !weights) return fail(MGCMT_ERR_INVALID, "block_density: non-null vector lists and weights");
@@ -460,6 +486,7 @@ int mgcmt_block_density(mgcmt_plan* p, int l, int nq, const int* x_slots, const 
 
 int mgcmt_block_project(mgcmt_plan* p, int l, int nb, const int* b_slots, const int* b_vecs, const int* ab_slots, const int* ab_vecs, int k,
                         const int* w_slots, const int* w_vecs, const int* aw_slots, const int* aw_vecs, double* coeffs_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   if (nb < 1 || nb > kBlockLockedMax || k < 1 || k > kBlockWideOut)
     return fail(MGCMT_ERR_INVALID, "block_project: 1..64 vectors B, 1..16 vectors W");
@@ -506,6 +533,7 @@ int mgcmt_block_project(mgcmt_plan* p, int l, int nb, const int* b_slots, const 
 
 int mgcmt_block_orthonormalize(mgcmt_plan* p, int l, int k, const int* w_slots, const int* w_vecs, const int* aw_slots, const int* aw_vecs,
                                double drop_tol, double* t_out, unsigned* dropped_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_level(p, l));
   if (k < 1 || k > kBlockWideOut) return fail(MGCMT_ERR_INVALID, "block_orthonormalize: 1..16 vectors W");
   if (!w_slots || !w_vecs) return fail(MGCMT_ERR_INVALID, "block_orthonormalize: non-null vector lists");
@@ -545,6 +573,8 @@ int mgcmt_block_orthonormalize(mgcmt_plan* p, int l, int k, const int* w_slots, 
 }
 
 int mgcmt_axpy(mgcmt_plan* p, int l, double alpha, int x_slot, int x_vec, int y_slot, int y_vec, void* stream) {
+  CarryKeep keep(p);
+  keep.writes(l, y_slot, y_vec);
   MG_TRY(check_vec(p, l, x_slot, x_vec));
   MG_TRY(check_vec(p, l, y_slot, y_vec));
   MG_TRY(ensure_slot(p, l, x_slot));
@@ -554,6 +584,8 @@ int mgcmt_axpy(mgcmt_plan* p, int l, double alpha, int x_slot, int x_vec, int y_
 }
 
 int mgcmt_scale(mgcmt_plan* p, int l, double alpha, int slot, int vec, void* stream) {
+  CarryKeep keep(p);
+  keep.writes(l, slot, vec);
   MG_TRY(check_vec(p, l, slot, vec));
   MG_TRY(ensure_slot(p, l, slot));
   launch_scale(S(stream), p->interior(l), alpha, p->kvec(l, slot, vec).p);
@@ -561,12 +593,14 @@ int mgcmt_scale(mgcmt_plan* p, int l, double alpha, int slot, int vec, void* str
 }
 
 int mgcmt_gramschmidt(mgcmt_plan* p, int l, int slot, int k, int modified, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_vec(p, l, slot, 0));
   MG_TRY(check_k(p, k));
   return gramschmidt_impl(p, l, slot, k, modified, S(stream));
 }
 
 int mgcmt_normalize(mgcmt_plan* p, int l, int slot, int k, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(check_vec(p, l, slot, 0));
   MG_TRY(check_k(p, k));
   MG_TRY(ensure_slot(p, l, slot));
@@ -600,11 +634,13 @@ static int fused_pass_checked(mgcmt_plan* p, int l, int kind, int nsweep, double
 }
 
 int mgcmt_fused_pass(mgcmt_plan* p, int l, int kind, int nsweep, double omega, int mode, int k, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_fused_pass"));
   return fused_pass_checked(p, l, kind, nsweep, omega, mode, k, S(stream), 1);
 }
 
 int mgcmt_time_fused_pass(mgcmt_plan* p, int l, int kind, int nsweep, double omega, int mode, int reps, double* ms_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_time_fused_pass"));
   if (!ms_out || reps < 1) return fail(MGCMT_ERR_INVALID, "bad arguments");
   MG_TRY(fused_pass_checked(p, l, kind, nsweep, omega, mode, 1, S(stream), 1));  // (allocations, occupancy query: untimed)
@@ -640,7 +676,14 @@ int mgcmt_fused_max_recompute(const mgcmt_plan* p, int l, int kind, int nsweep, 
 }
 
 int mgcmt_plan_set_option(mgcmt_plan* p, int option, int value) {
+  entry_drops_carry(p);
   if (!p) return fail(MGCMT_ERR_INVALID, "null plan");
+  p->carry_drop();  // (a carried right-hand side belongs to the options it was computed under)
+  if (option == MGCMT_OPT_CARRY) {
+    p->carry_opt = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
+    p->graphs_invalidate();
+    return MGCMT_OK;
+  }
   if (option == MGCMT_OPT_FUSED) {
     p->use_fused = value != 0;
     p->graphs_invalidate();
@@ -695,7 +738,14 @@ int mgcmt_plan_set_option(mgcmt_plan* p, int option, int value) {
   return fail(MGCMT_ERR_INVALID, "unknown option");
 }
 
+int mgcmt_carry_pending(const mgcmt_plan* p, int* pending) {
+  if (!p || !pending) return fail(MGCMT_ERR_INVALID, "null argument");
+  *pending = p->carry.valid ? 1 : 0;
+  return MGCMT_OK;
+}
+
 int mgcmt_lex_wave_stats(mgcmt_plan* p, uint32_t* out, int64_t capacity) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_lex_wave_stats"));
   if (!p || !out) return fail(MGCMT_ERR_INVALID, "null argument");
   if (!p->lex_sync) return fail(MGCMT_ERR_INVALID, "no lexicographic wave sweep has run on this plan");
@@ -706,6 +756,7 @@ int mgcmt_lex_wave_stats(mgcmt_plan* p, uint32_t* out, int64_t capacity) {
 }
 
 int mgcmt_time_smoother(mgcmt_plan* p, int l, int kind, int nu, double omega, int reps, double* ms_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_time_smoother"));
   MG_TRY(check_level(p, l));
   if (!ms_out || reps < 1) return fail(MGCMT_ERR_INVALID, "bad arguments");
@@ -726,6 +777,7 @@ int mgcmt_time_smoother(mgcmt_plan* p, int l, int kind, int nu, double omega, in
 }
 
 int mgcmt_bandwidth_probe(mgcmt_plan* p, int l, int kind, int blocks, int reps, double* ms_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_bandwidth_probe"));
   MG_TRY(check_level(p, l));
   if (!ms_out || reps < 1 || blocks < 1 || kind < 0 || (kind > 17 && (kind < 20 || kind > 23))) return fail(MGCMT_ERR_INVALID, "bad arguments");

@@ -120,6 +120,28 @@ struct mgcmt_plan {
   bool use_recompute = true;  // down-leg passes skip storing V', up-leg passes recompute it (fused_kernel.h)
   int two_level = 1;  // pair a 5-point level with its Galerkin level below in one down and one up launch: 1 from 2^22 points, 2 always, 0 never
   bool force_recompute = false;  // ... on every fused level, not only the bandwidth-bound ones (tests)
+  // The carried right-hand side (cycle.hip: mgcmt_vcycle; fused2_kernel.h: CARRY).  A cycle whose last launch is the
+  // two-level up pass has that pass go on with the fine part of the NEXT cycle's down pass and leaves what it would write
+  // to F[level+1] in T[level+1]; an identical next cycle swaps the two roles and skips the pass.  The carry holds while
+  // nothing it was computed from has changed: V[level] and F[level] (columns < k), T[level+1], the shifts, the options.
+  // Every entry that takes a non-const plan drops it in its first statement (entry_drops_carry below); the exceptions
+  // keep it with a CarryKeep.  mgcmt_vec_ptr, whose handle is const by the ABI, changes this state as well (it turns
+  // carrying off): the one const entry that does.
+  int carry_opt = 1;  // MGCMT_OPT_CARRY: 0 never, 1 on fine levels of >= 2^22 points, 2 wherever eligible (tests)
+  struct Carry {
+    bool valid = false;     // T[level+1] holds the next cycle's F[level+1]
+    bool disabled = false;  // mgcmt_vec_ptr handed out a raw address: nothing can be vouched for any more
+    int level = 0, nu1 = 0, nu2 = 0, nu_coarse = 0, kind = 0, k = 0, flags = 0;  // the last cycle's parameters (k = 0: none yet)
+    double omega = 0.0;
+    int unused_drops = 0;  // carries dropped unused in a row: from two on, none is produced ...
+    std::string prev;      // ... until a cycle follows a cycle of the same parameters (those of the last cycle, "" once
+                           // another entry has touched the plan)
+  } carry;
+  void carry_drop() {
+    if (carry.valid) ++carry.unused_drops;
+    carry.valid = false;
+    carry.prev.clear();
+  }
   // HIP-graph replay of whole cycles (mgcmt_vcycle): the launch sequence of a cycle is fixed by its
   // parameters and by which of the two buffers of every level currently is "V", so it is captured once per
   // such state and replayed; small grids are launch-latency-bound otherwise.
@@ -135,7 +157,7 @@ struct mgcmt_plan {
   hipStream_t capture_stream = nullptr;
   struct CycleGraph {
     hipGraphExec_t exec = nullptr;
-    std::vector<double*> post_state;  // base pointers of slots V and T of every level after the cycle
+    std::vector<double*> post_state;  // base pointers of slots V, T and F of every level after the cycle
     bool lex_wave = false;            // the captured body runs the lexicographic wave pipeline (its error word must be checked after a replay)
   };
   std::map<std::string, CycleGraph> graphs;
@@ -145,6 +167,7 @@ struct mgcmt_plan {
       if (g.second.exec) (void)hipGraphExecDestroy(g.second.exec);
     graphs.clear();
     cycle_seen.clear();
+    carry_drop();
   }
 
   mgcmt::KGrid kgrid(int l) const {
@@ -176,6 +199,40 @@ int unsupported_point_smoother(const mgcmt_plan* p, int kind);
 int check_level(const mgcmt_plan* p, int l);
 int check_vec(const mgcmt_plan* p, int l, int slot, int vec);
 int check_k(const mgcmt_plan* p, int k);
+// The prologue of every exported entry that takes a non-const plan, i.e. may change what a carried right-hand side was
+// computed from (mgcmt_plan::carry): the first statement of the entry, once per such plan argument
+// (tests/test_carry_prologue.py reads the sources for it).  The exceptions are mgcmt_vcycle, which decides itself what
+// becomes of the carry, and the entries that provably leave those vectors alone and declare a CarryKeep instead: the carry
+// is dropped there as well, and it and its back-off state are put back when the entry returns, unless writes() found the
+// destination to be one of the vectors the carry depends on.
+inline void entry_drops_carry(mgcmt_plan* p) {
+  if (p) p->carry_drop();
+}
+struct CarryKeep {
+  mgcmt_plan* p;
+  mgcmt_plan::Carry saved;
+  bool keep = true;
+  explicit CarryKeep(mgcmt_plan* plan) : p(plan) {
+    if (p) {
+      saved = p->carry;
+      p->carry_drop();
+    }
+  }
+  // the entry writes vector (l, slot, vec): the carry goes if it depends on it (and with or without a carry, the
+  // next cycle no longer follows the last one)
+  void writes(int l, int slot, int vec) {
+    if (p && vec < saved.k &&
+        ((l == saved.level && (slot == MGCMT_SLOT_V || slot == MGCMT_SLOT_F)) || (l == saved.level + 1 && slot == MGCMT_SLOT_T)))
+      keep = false;
+  }
+  ~CarryKeep() {
+    if (p && keep) {
+      const bool disabled = p->carry.disabled;
+      p->carry = saved;
+      p->carry.disabled = disabled;
+    }
+  }
+};
 inline hipStream_t S(void* s) { return (hipStream_t)s; }
 int ensure_slot(mgcmt_plan* p, int l, int slot);
 int post_launch();

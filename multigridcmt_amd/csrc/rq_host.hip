@@ -14,6 +14,7 @@ using namespace mgcmt;
 extern "C" {
 
 int mgcmt_ritz_pair(mgcmt_plan* p, int l, int xs, int xv, int ws, int wv, int ss, int sv, double* out5, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_ritz_pair"));
   MG_TRY(mgcmt::unsupported_point(p, "mgcmt_ritz_pair"));
   MG_TRY(check_vec(p, l, xs, xv));
@@ -51,6 +52,7 @@ int mgcmt_ritz_pair(mgcmt_plan* p, int l, int xs, int xv, int ws, int wv, int ss
 }
 
 int mgcmt_rayleigh_residual(mgcmt_plan* p, int l, int slot, int k, double* rq_out, double* res_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_rayleigh_residual"));
   MG_TRY(mgcmt::unsupported_point(p, "mgcmt_rayleigh_residual"));
   MG_TRY(check_vec(p, l, slot, 0));
@@ -184,6 +186,7 @@ static int rq_result(mgcmt_plan* p, double* rho_out, hipStream_t s) {
 }
 
 int mgcmt_rqmin(mgcmt_plan* p, int l, int slot, const int* vecs, int nu, int robust, double* rho_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d_massless(p, "mgcmt_rqmin"));
   MG_TRY(mgcmt::unsupported_point(p, "mgcmt_rqmin"));
   MG_TRY(rqmin_check(p, l, slot, vecs, nu));
@@ -195,6 +198,7 @@ int mgcmt_rqmin(mgcmt_plan* p, int l, int slot, const int* vecs, int nu, int rob
 // rqmin with p = w read as it is and not stored, then x' = x + delta w and its gradient.
 int mgcmt_rq_line_step(mgcmt_plan* p, int l, const int* xv, const int* wv, const int* xoutv, const int* gv, const int* tmpv, int robust, int record,
                        void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d_massless(p, "mgcmt_rq_line_step"));
   MG_TRY(mgcmt::unsupported_point(p, "mgcmt_rq_line_step"));
   MG_TRY(check_level(p, l));
@@ -260,6 +264,7 @@ int mgcmt_rq_line_step(mgcmt_plan* p, int l, const int* xv, const int* wv, const
 }
 
 int mgcmt_rq_history(mgcmt_plan* p, int first, int count, double* out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d_massless(p, "mgcmt_rq_history"));
   if (!p || !out || first < 0 || count < 0 || first + count > MGCMT_RQ_HISTORY) return fail(MGCMT_ERR_INVALID, "rq_history: bad range");
   if (count == 0) return MGCMT_OK;
@@ -287,6 +292,7 @@ static int rqmg_body(mgcmt_plan* p, int l, int slot, const int* vecs, int nu1, i
 }
 
 int mgcmt_vcycle_rqmg(mgcmt_plan* p, int slot, const int* vecs, int nu1, int nu2, int robust, double* rho_out, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d_massless(p, "mgcmt_vcycle_rqmg"));
   MG_TRY(mgcmt::unsupported_point(p, "mgcmt_vcycle_rqmg"));
   if (!p) return fail(MGCMT_ERR_INVALID, "null plan");

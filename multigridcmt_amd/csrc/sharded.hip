@@ -530,6 +530,7 @@ static int comm_common(mgcmt_plan* p, int rank, int nranks, ShardComm** out) {
 }
 
 int mgcmt_comm_init(mgcmt_plan* p, int rank, int nranks, const void* unique_id) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_comm_init"));
   MG_TRY(mgcmt::unsupported_point(p, "mgcmt_comm_init"));
   if (!unique_id) return fail(MGCMT_ERR_INVALID, "null unique id");
@@ -550,6 +551,7 @@ int mgcmt_comm_init(mgcmt_plan* p, int rank, int nranks, const void* unique_id) 
 
 int mgcmt_comm_init_external(mgcmt_plan* p, int rank, int nranks, mgcmt_p2p_fn p2p, mgcmt_allgather_fn allgather,
                              mgcmt_allreduce_fn allreduce, void* user) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_comm_init_external"));
   MG_TRY(mgcmt::unsupported_point(p, "mgcmt_comm_init_external"));
   if (nranks > 1 && (!p2p || !allgather)) return fail(MGCMT_ERR_INVALID, "missing transport callbacks");
@@ -564,12 +566,14 @@ int mgcmt_comm_init_external(mgcmt_plan* p, int rank, int nranks, mgcmt_p2p_fn p
 }
 
 int mgcmt_comm_destroy(mgcmt_plan* p) {
+  entry_drops_carry(p);
   if (!p) return fail(MGCMT_ERR_INVALID, "null plan");
   comm_release(p);
   return MGCMT_OK;
 }
 
 int mgcmt_comm_set_option(mgcmt_plan* p, int option, int value) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_comm_set_option"));
   MG_TRY(check_comm(p));
   if (option == MGCMT_COMM_OPT_OVERLAP) p->comm->overlap = value != 0 && p->comm->nccl != nullptr;
@@ -588,6 +592,7 @@ int mgcmt_comm_set_option(mgcmt_plan* p, int option, int value) {
 }
 
 int mgcmt_halo_exchange(mgcmt_plan* p, int l, int slot_mask, void* stream) {
+  entry_drops_carry(p);
   // (a plan may store more vectors than a launch batches — the shifts and the reduction buffers hold kMaxVec —: refused first)
   if (((slot_mask >> 16) & 0xff) > kMaxVec) return fail(MGCMT_ERR_INVALID, "halo_exchange: at most 32 columns per call");
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_halo_exchange"));
@@ -606,6 +611,8 @@ int mgcmt_halo_exchange(mgcmt_plan* p, int l, int slot_mask, void* stream) {
 }
 
 int mgcmt_gather_coarse(mgcmt_plan* p, int l, int slot, mgcmt_plan* coarse, int dst_slot, int k, void* stream) {
+  entry_drops_carry(p);
+  entry_drops_carry(coarse);
   // (a plan may store more vectors than a launch batches — the shifts and the reduction buffers hold kMaxVec —: refused first)
   if (k > kMaxVec) return fail(MGCMT_ERR_INVALID, "gather_coarse: at most 32 columns per call");
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_gather_coarse"));
@@ -654,6 +661,7 @@ int mgcmt_gather_coarse(mgcmt_plan* p, int l, int slot, mgcmt_plan* coarse, int 
 }
 
 int mgcmt_allreduce_sum(mgcmt_plan* p, double* host_inout, int n, void* stream) {
+  entry_drops_carry(p);
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_allreduce_sum"));
   MG_TRY(check_comm(p));
   if (!host_inout || n < 1 || n > 2 * kMaxVec) return fail(MGCMT_ERR_INVALID, "allreduce: 1..64 values");
@@ -681,6 +689,8 @@ int mgcmt_allreduce_sum(mgcmt_plan* p, double* host_inout, int n, void* stream) 
 // arithmetic (the Gram-Schmidt's inner products are summed rank by rank: equal to rounding).
 int mgcmt_sharded_vcycle(mgcmt_plan* p, mgcmt_plan* coarse, int nu1, int nu2, int nu_coarse, int kind, double omega, int k, int flags,
                          void* stream) {
+  entry_drops_carry(p);
+  entry_drops_carry(coarse);
   // (a plan may store more vectors than a launch batches — the shifts and the reduction buffers hold kMaxVec —: refused first)
   if (k > kMaxVec) return fail(MGCMT_ERR_INVALID, "sharded_vcycle: at most 32 columns per call");
   MG_TRY(mgcmt::unsupported_3d(p, "mgcmt_sharded_vcycle"));

@@ -520,6 +520,12 @@ class Plan:
     def set_option(self, option, value):
         check(_lib.lib().mgcmt_plan_set_option(self._h, option, int(value)))
 
+    def carry_pending(self):
+        """True while the last vcycle's carried right-hand side (OPT_CARRY) is waiting for an identical next cycle."""
+        n = c_int(0)
+        check(_lib.lib().mgcmt_carry_pending(self._h, ctypes.byref(n)))
+        return bool(n.value)
+
     def bandwidth_probe(self, level, kind, blocks, reps, stream=None):
         ms = c_double(0.0)
         check(_lib.lib().mgcmt_bandwidth_probe(self._h, level, kind, blocks, reps, ctypes.byref(ms), stream))

@@ -59,6 +59,7 @@ extern "C" {
 #define MGCMT_BLOCK_WIDE_MAX 48  /* vectors of mgcmt_block_pencil, inputs of mgcmt_block_combine_wide */
 #define MGCMT_BLOCK_WIDE_OUT 16  /* outputs of mgcmt_block_combine_wide */
 #define MGCMT_BLOCK_LOCKED_MAX 64 /* vectors Q of mgcmt_block_deflate */
+#define MGCMT_MIX_MAX 9 /* pairs (x_i, r_i) of mgcmt_mix_residual / mgcmt_mix_combine: Anderson mixing of depth <= 8 */
 #define MGCMT_HALO_ROWS 16 /* rows of halo kept above and below every vector of a 2-D level (a 1-D level keeps one: its
                               "row" is the whole vector); how many of them a sharded cycle fills: mgcmt_plan_level_halo */
 
@@ -523,6 +524,27 @@ int mgcmt_block_orthonormalize(mgcmt_plan* plan, int level, int k, const int* w_
  * (the rule of the wide entries).  Writes dst and nothing else. */
 int mgcmt_block_density(mgcmt_plan* plan, int level, int nq, const int* x_slots, const int* x_vecs, const double* weights, int dst_slot,
                         int dst_vec, void* stream);
+/* Anderson (Pulay) mixing, the residual of a step (drivers.schroedinger_poisson with mixing_history > 0):
+ *     r = out - in   written to (r_slot, r_vec),   and, from the same pass,
+ *     host_out[j] = <r, prev_j> for j < nprev in the order given, host_out[nprev] = <r, r>, host_out[nprev + 1] = <out, out>
+ * for 0 <= nprev <= MGCMT_MIX_MAX - 1 earlier residuals of `level`.  out, in and every prev_j are read once, r is written
+ * once: 8 (nprev + 3) bytes per point.  Per-slice partial sums (the slices depend on the point count alone, not on the
+ * launch's grid), then one workgroup that adds them in a fixed order: r and every sum are bit-reproducible from call to call
+ * and do not depend on the grid.  Synchronises `stream` as mgcmt_dot does (nprev + 2 numbers cross to the host).
+ * MGCMT_ERR_INVALID: null lists (prev_slots / prev_vecs may be NULL only with nprev == 0) or a null host_out, nprev out of
+ * range, a vector outside the plan, r one of the vectors read, an odd number of points or a vector that is not 16-byte
+ * aligned (the rule of the wide entries).  Writes r and nothing else. */
+int mgcmt_mix_residual(mgcmt_plan* plan, int level, int out_slot, int out_vec, int in_slot, int in_vec, int r_slot, int r_vec, int nprev,
+                       const int* prev_slots, const int* prev_vecs, double* host_out, void* stream);
+/* Anderson mixing, the new iterate:  dst = sum_(i < p) alpha[i] (x_i + beta r_i)  for 1 <= p <= MGCMT_MIX_MAX pairs of vectors
+ * of `level`, in one stream-ordered pass over the 2p vectors (8 (2p + 1) bytes per point); nothing synchronises.  alpha (p host
+ * numbers) and beta are copied on entry.  The arithmetic is fixed — acc = 0; for i ascending:
+ * acc = fma(alpha[i], fma(beta, r_i, x_i), acc) —, so the result is bit-reproducible and does not depend on the grid.  dst may
+ * be x_0 (the oldest pair's x, which a ring of pairs is about to drop) and no other input.  MGCMT_ERR_INVALID: null lists, p out
+ * of range, a vector outside the plan, an alpha or beta that is not finite, dst one of the other inputs, an odd number of points
+ * or a vector that is not 16-byte aligned.  Writes dst and nothing else. */
+int mgcmt_mix_combine(mgcmt_plan* plan, int level, int p, const int* x_slots, const int* x_vecs, const int* r_slots, const int* r_vecs,
+                      const double* alpha, double beta, int dst_slot, int dst_vec, void* stream);
 /* A new per-point diagonal for a plan that has a per-point part (any of the six creators of such plans):
  *     D = sum_(t < nterms) coeffs[t] * (slots[t], vecs[t]),   1 <= nterms <= 4, level-0 vectors of this plan,
  * with the arithmetic of mgcmt_lincomb, written to level 0 — the diagonal of mgcmt_plan_create_pot / create3d_pot, plane D of

@@ -21,6 +21,7 @@ RQ_HISTORY = 4096      # MGCMT_RQ_HISTORY: Rayleigh quotients Plan.rq_line_step 
 MAX_TERMS = 4
 MAX_VEC = 32
 MAX_STORE_VEC = 80     # MGCMT_MAX_STORE_VEC: vectors a plan keeps per slot
+MIX_MAX = 9            # MGCMT_MIX_MAX: pairs (x, r) of mix_residual / mix_combine (Anderson mixing of depth <= 8)
 ABI_VERSION = 7
 OPT_FUSED = 0
 OPT_FUSED_ROWS = 1
@@ -154,6 +155,8 @@ _SIGNATURES = {
     "mgcmt_block_deflate": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int), POINTER(c_int),
                                     POINTER(c_double), c_void_p]),
     "mgcmt_block_density": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_double), c_int, c_int, c_void_p]),
+    "mgcmt_mix_residual": (c_int, [c_void_p] + [c_int] * 8 + [POINTER(c_int), POINTER(c_int), POINTER(c_double), c_void_p]),
+    "mgcmt_mix_combine": (c_int, [c_void_p, c_int, c_int] + [POINTER(c_int)] * 4 + [POINTER(c_double), c_double, c_int, c_int, c_void_p]),
     "mgcmt_plan_set_point_diagonal": (c_int, [c_void_p, c_int, _dp, POINTER(c_int), POINTER(c_int), c_void_p]),
     "mgcmt_copy_across": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "mgcmt_block_project": (c_int, [c_void_p, c_int, c_int] + [POINTER(c_int)] * 4 + [c_int] + [POINTER(c_int)] * 4 + [POINTER(c_double), c_void_p]),

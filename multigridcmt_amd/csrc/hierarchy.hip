@@ -438,6 +438,8 @@ int build_plan(const PlanSpec& d, mgcmt_plan** out) {
   if (mb && atol(mb) > 1) p->mgs_block_min = atol(mb);
   const char* db = getenv("MGCMT_DENSITY_BLOCKS");  // the grid limit of mgcmt_block_density (tests: several trips at a small size)
   if (db && atol(db) >= 1 && atol(db) <= 4096) p->density_max_blocks = (int)atol(db);
+  const char* xb = getenv("MGCMT_MIX_BLOCKS");  // the grid limit of mgcmt_mix_residual / mgcmt_mix_combine (tests, as above)
+  if (xb && atol(xb) >= 1 && atol(xb) <= 2048) p->mix_max_blocks = (int)atol(xb);
   if (d.dim != 3) {
     const char* e = getenv("MGCMT_TAIL_DENSE");  // "0": the tail as the LDS-resident launch by default (the host-only test build:
     p->use_tail_dense = !(e && e[0] == '0');     // emulating the 1024 workgroups that form the matrix takes minutes)

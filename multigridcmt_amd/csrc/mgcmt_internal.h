@@ -246,6 +246,13 @@ constexpr int kBlockLockedMax = MGCMT_BLOCK_LOCKED_MAX;  // vectors a block is d
 bool launch_block_deflate(hipStream_t s, long n, int nq, const double* const* q, int k, double* const* w, double* partials, double* out);
 // dst = sum_t w[t] x_t^2, nq <= kBlockLockedMax (mgcmt_block_density); max_blocks > 0: the grid's limit in place of the default
 bool launch_block_density(hipStream_t s, long n, int nq, const double* const* x, const double* w, double* dst, int max_blocks);
+// Anderson mixing (kernels_mix.hip; mgcmt_mix_residual, mgcmt_mix_combine): up to kMixMax pairs (x_i, r_i)
+constexpr int kMixMax = MGCMT_MIX_MAX;
+int mix_slices(long n);  // partial sums per result of the residual pass (partials: (kMixMax + 1) * mix_slices(n) doubles)
+bool launch_mix_residual(hipStream_t s, long n, const double* out, const double* in, double* r, int nprev, const double* const* prev, double* partials,
+                         double* results, int max_blocks);
+bool launch_mix_combine(hipStream_t s, long n, int p, const double* const* x, const double* const* r, const double* alpha, double beta, double* dst,
+                        int max_blocks);
 // the same with companions (mgcmt_block_project), and one Cholesky-QR step on k <= 16 vectors (mgcmt_block_orthonormalize)
 bool launch_block_project(hipStream_t s, long n, int nb, const double* const* b, const double* const* ab, int k, double* const* w, double* const* aw,
                           double* partials, double* out);

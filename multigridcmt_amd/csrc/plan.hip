@@ -484,6 +484,54 @@ int mgcmt_block_density(mgcmt_plan* p, int l, int nq, const int* x_slots, const 
   return post_launch();
 }
 
+int mgcmt_mix_residual(mgcmt_plan* p, int l, int out_slot, int out_vec, int in_slot, int in_vec, int r_slot, int r_vec, int nprev,
+                       const int* prev_slots, const int* prev_vecs, double* host_out, void* stream) {
+  entry_drops_carry(p);
+  MG_TRY(check_level(p, l));
+  if (nprev < 0 || nprev > kMixMax - 1) return fail(MGCMT_ERR_INVALID, "mix_residual: 0..8 earlier residuals");
+  if ((nprev > 0 && (!prev_slots || !prev_vecs)) || !host_out) return fail(MGCMT_ERR_INVALID, "mix_residual: non-null vector lists and output");
+  const int io_slots[3] = {out_slot, in_slot, r_slot}, io_vecs[3] = {out_vec, in_vec, r_vec};
+  double *io[3], *prev[kMixMax];
+  MG_TRY(wide_vectors(p, l, 3, io_slots, io_vecs, io));
+  MG_TRY(wide_vectors(p, l, nprev, prev_slots, prev_vecs, prev));
+  bool aliased = io[2] == io[0] || io[2] == io[1];
+  for (int j = 0; j < nprev; ++j) aliased = aliased || prev[j] == io[2];
+  if (aliased) return fail(MGCMT_ERR_INVALID, "mix_residual: the destination r is also a vector that is read");
+  if (!launch_mix_residual(S(stream), p->interior(l), io[0], io[1], io[2], nprev, prev, p->d_partials, p->d_scalars, p->mix_max_blocks))
+    return fail(MGCMT_ERR_INVALID, "mix_residual: an odd number of points or a vector that is not 16-byte aligned");
+  MG_TRY(post_launch());
+  double packed[kMixMax + 1];  // the kernel's order: <r, r>, <out, out>, <r, prev_j>
+  MG_HIP(hipMemcpyAsync(packed, p->d_scalars, sizeof(double) * (nprev + 2), hipMemcpyDeviceToHost, S(stream)));
+  MG_HIP(hipStreamSynchronize(S(stream)));
+  for (int j = 0; j < nprev; ++j) host_out[j] = packed[2 + j];
+  host_out[nprev] = packed[0];
+  host_out[nprev + 1] = packed[1];
+  return MGCMT_OK;
+}
+
+int mgcmt_mix_combine(mgcmt_plan* p, int l, int np, const int* x_slots, const int* x_vecs, const int* r_slots, const int* r_vecs,
+                      const double* alpha, double beta, int dst_slot, int dst_vec, void* stream) {
+  entry_drops_carry(p);
+  MG_TRY(check_level(p, l));
+  if (np < 1 || np > kMixMax) return fail(MGCMT_ERR_INVALID, "mix_combine: 1..9 pairs (x, r)");
+  if (!x_slots || !x_vecs || !r_slots || !r_vecs || !alpha) return fail(MGCMT_ERR_INVALID, "mix_combine: non-null vector lists and coefficients");
+  double *x[kMixMax], *r[kMixMax];
+  MG_TRY(wide_vectors(p, l, np, x_slots, x_vecs, x));
+  MG_TRY(wide_vectors(p, l, np, r_slots, r_vecs, r));
+  MG_TRY(check_vec(p, l, dst_slot, dst_vec));
+  MG_TRY(ensure_slot(p, l, dst_slot));
+  double* dst = p->kvec(l, dst_slot, dst_vec).p;
+  if (!std::isfinite(beta)) return fail(MGCMT_ERR_INVALID, "mix_combine: a coefficient that is not finite");
+  for (int i = 0; i < np; ++i) {
+    if (!std::isfinite(alpha[i])) return fail(MGCMT_ERR_INVALID, "mix_combine: a coefficient that is not finite");
+    if ((i > 0 && x[i] == dst) || r[i] == dst)
+      return fail(MGCMT_ERR_INVALID, "mix_combine: the destination is also an input other than the oldest x");
+  }
+  if (!launch_mix_combine(S(stream), p->interior(l), np, x, r, alpha, beta, dst, p->mix_max_blocks))
+    return fail(MGCMT_ERR_INVALID, "mix_combine: an odd number of points or a vector that is not 16-byte aligned");
+  return post_launch();
+}
+
 int mgcmt_block_project(mgcmt_plan* p, int l, int nb, const int* b_slots, const int* b_vecs, const int* ab_slots, const int* ab_vecs, int k,
                         const int* w_slots, const int* w_vecs, const int* aw_slots, const int* aw_vecs, double* coeffs_out, void* stream) {
   entry_drops_carry(p);

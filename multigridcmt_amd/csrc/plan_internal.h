@@ -105,6 +105,7 @@ struct mgcmt_plan {
   // remembers the count it was formed at and is formed again when the plan has moved on
   unsigned long point_version = 0;
   int density_max_blocks = 0;  // the grid limit of mgcmt_block_density, 0 = the default (MGCMT_DENSITY_BLOCKS, read at creation: tests)
+  int mix_max_blocks = 0;      // the grid limit of mgcmt_mix_residual / mgcmt_mix_combine, 0 = the default (MGCMT_MIX_BLOCKS, read at creation: tests)
   bool use_fused = true;
   bool use_tail = true;   // levels of at most 32 x 32 points as one launch (kernels_tail.hip)
   bool use_tail_dense = true;  // ... and that launch as ONE dense product with the tail's matrix (formed once per shift set)

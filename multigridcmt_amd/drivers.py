@@ -639,7 +639,37 @@ def _deflated_eigensolve_on(plan, k, kb, place, *, rtol, atol, maxiter, nu, smoo
     return vals[order], [where[j] for j in order]
 
 
-def schroedinger_poisson(op, poisson_op, k, occupations, *, coupling, mixing=1.0, tol=1e-6, maxiter=50, eigen_rtol=1e-9,
+ANDERSON_RCOND = 1e-12
+
+
+def anderson_coefficients(G):
+    """The coefficients alpha (sum alpha = 1) that minimise ||sum_i alpha_i r_i||_2 from the p x p Gram matrix G_ij = <r_i, r_j>
+    of the residuals, newest last — Anderson (type II, Pulay) mixing in the difference form: with D the (p - 1) x p
+    forward-difference matrix, (D G D^T) gamma = D G e_last, scaled symmetrically to a unit diagonal and solved by
+    numpy.linalg.lstsq with rcond = 1e-12; alpha = e_last - D^T gamma.  None where the history has to be restarted: a
+    diagonal entry of D G D^T that is not positive, or a scaled system (or a solution) that is not finite.  Host arithmetic
+    on at most 81 numbers."""
+    G = np.asarray(G, dtype=np.float64)
+    p = G.shape[0]
+    if p == 1:
+        return np.ones(1)
+    D = np.zeros((p - 1, p))
+    D[np.arange(p - 1), np.arange(p - 1)] = -1.0
+    D[np.arange(p - 1), np.arange(1, p)] = 1.0
+    A, b = D @ G @ D.T, D @ G[:, -1]
+    diag = np.diag(A)
+    if not np.all(np.isfinite(diag)) or not np.all(diag > 0.0):
+        return None
+    s = 1.0 / np.sqrt(diag)
+    As, bs = A * s[:, None] * s[None, :], b * s
+    if not (np.all(np.isfinite(As)) and np.all(np.isfinite(bs))):
+        return None
+    alpha = -(D.T @ (s * np.linalg.lstsq(As, bs, rcond=ANDERSON_RCOND)[0]))
+    alpha[-1] += 1.0
+    return alpha if np.all(np.isfinite(alpha)) else None
+
+
+def schroedinger_poisson(op, poisson_op, k, occupations, *, coupling, mixing=1.0, mixing_history=0, tol=1e-6, maxiter=50, eigen_rtol=1e-9,
                          poisson_rtol=1e-10, warm_start=True, block=None, lowest=8, poisson_lowest=None, smoother="rb", basis="scaled",
                          seed=0, info=None):
     """The self-consistent Schroedinger-Poisson loop on the device: the k lowest states of H[phi] = op + coupling diag(phi),
@@ -663,21 +693,33 @@ def schroedinger_poisson(op, poisson_op, k, occupations, *, coupling, mixing=1.0
     to the host between the upload of V_ext and the downloads at the end (with warm_start=False every step uploads its random
     start vectors, as deflated_eigensolve does).
 
+    ``mixing_history`` = m, 1 <= m <= 8: Anderson (type II, Pulay) mixing of the potential with m history vectors beyond the
+    newest (DESIGN.md par. 4.24).  With x_i the input potential of step i, g_i its Poisson solution and r_i = g_i - x_i, the
+    last p = min(m + 1, steps since the last restart) pairs (x_i, r_i) stay on the device in a ring of columns of the Poisson
+    plan; one pass writes r_i and returns its inner products with the earlier residuals, <r_i, r_i> and <g_i, g_i>
+    (mgcmt_mix_residual: d from the same pass), the host finds the alpha of anderson_coefficients from the p x p Gram matrix,
+    and one pass writes x_(i+1) = sum alpha_i (x_i + mixing r_i) (mgcmt_mix_combine).  With one pair this is the damped step;
+    a Gram matrix that cannot be used restarts the history with the newest pair.  Only scalars reach the host.  m = 0 (the
+    default) is the plain damped iteration, launch for launch what it was before the option existed.
+
     ``warm_start``: the k states of a step are copied to a pool in the plan's own columns and handed to the next step's
     iteration in order — the first kb as its start block, the others as the fresh vectors after locks —, random vectors only
     behind them.
 
     Memory: the eigen-plan holds 3 kb + ceil(k / 2) columns per slot for the iteration (deflated_eigensolve), ceil(k / 2) more
     in each of slots W and F for the pool and two for V_ext and rho / phi (slot W; a cycle exchanges the storage of V and T) —
-    at most MGCMT_MAX_STORE_VEC = 80, so k <= 30 with the default block.  The Poisson plan holds 6.
+    at most MGCMT_MAX_STORE_VEC = 80, so k <= 30 with the default block.  The Poisson plan holds 6, and 2 (m + 1) more for
+    the ring of Anderson mixing.
 
     Returns (eigenvalues[k], eigenvectors[n, k], phi[n]): the states are those of the last step's operator, phi the mixed
     potential after it.  ``info`` (a dict) receives iterations, status ("converged" / "maxiter"), changes (every d),
-    eigen_iterations, eigen_status, poisson_iterations and poisson_status per step, and density (rho of the last step, n
-    numbers).  A Poisson solve that does not reach ``poisson_rtol`` within 200 iterations, breaks down or meets an indefinite
+    eigen_iterations, eigen_status, poisson_iterations and poisson_status per step, density (rho of the last step, n
+    numbers), mixing_history, mixing_depths (the p of every step; all 1 with mixing_history = 0) and mixing_restarts (the steps,
+    counted from 1, at which the history was reset).  A Poisson solve that does not reach ``poisson_rtol`` within 200 iterations, breaks down or meets an indefinite
     operator raises RuntimeError: the loop does not go on with a potential that is not one.
     Refused with ValueError: what deflated_eigensolve refuses, an ``op`` without a per-point part, operators on different
-    grids, occupations that are not k numbers, a mixing outside (0, 1], more columns than a plan stores."""
+    grids, occupations that are not k numbers, a mixing outside (0, 1], a mixing_history that is not an integer in 0..8, more
+    columns than a plan stores."""
     from . import _lib
     from .operators import StructuredOperator
     from .plan import Plan
@@ -703,6 +745,9 @@ def schroedinger_poisson(op, poisson_op, k, occupations, *, coupling, mixing=1.0
                          % (op.dimension, op.g, poisson_op.dimension, poisson_op.g))
     if not 0.0 < float(mixing) <= 1.0:
         raise ValueError("schroedinger_poisson: mixing lies in (0, 1]")
+    if isinstance(mixing_history, bool) or not isinstance(mixing_history, (int, np.integer)) or not 0 <= mixing_history <= _lib.MIX_MAX - 1:
+        raise ValueError("schroedinger_poisson: mixing_history is an integer in 0..%d" % (_lib.MIX_MAX - 1))
+    history = int(mixing_history)
     if not callable(occupations) and np.asarray(occupations, dtype=np.float64).shape != (k,):
         raise ValueError("schroedinger_poisson: occupations are k = %d numbers (or a callable eigenvalues -> k numbers)" % k)
     half = (k + 1) // 2
@@ -717,17 +762,23 @@ def schroedinger_poisson(op, poisson_op, k, occupations, *, coupling, mixing=1.0
     POOL = [((W, F)[i % 2], 3 * kb + half + i // 2) for i in range(k)]
     VEXT, RHO = (W, nvec - 2), (W, nvec - 1)                     # (RHO holds rho on the way out and phi on the way back)
     PX, PPHI, PDIFF = (W, 0), (W, 4), (W, 5)                      # the Poisson plan: columns 0..3 of W are x, p, q, p2 of the solve
+    # Anderson mixing: a ring of history + 1 pairs (x_i, r_i) behind them, step i in place (i - 1) % (history + 1)
+    RING_X = [(W, 6 + c) for c in range(history + 1)] if history else []
+    RING_R = [(W, 7 + history + c) for c in range(history + 1)] if history else []
     v_ext = arrays[0] if part != "planes" else arrays[0][(1,) * (arrays[0].ndim // 2)]
     rng = np.random.RandomState(seed)
     changes, eig_its, eig_status, poi_its, poi_status = [], [], [], [], []
+    depths, restarts, pairs, gram = [], [], [], {}                # (pairs: the ring places in the history, oldest first; gram: <r_a, r_b> by place)
     eplan = pplan = None
     try:
         eplan = Plan(op, int(lowest), nvec=nvec)
-        pplan = Plan(poisson_op, int(lowest if poisson_lowest is None else poisson_lowest), nvec=6)
+        pplan = Plan(poisson_op, int(lowest if poisson_lowest is None else poisson_lowest), nvec=6 + (2 * (history + 1) if history else 0))
         n = eplan.size(0)
         eplan.upload(0, VEXT[0], VEXT[1], v_ext)
         pplan.set_shifts(np.zeros(6))
         pplan.fill(0, PPHI[0], PPHI[1], 0.0)
+        if history:
+            pplan.fill(0, RING_X[0][0], RING_X[0][1], 0.0)
         pooled = 0
 
         def place(j, location):
@@ -768,10 +819,33 @@ def schroedinger_poisson(op, poisson_op, k, occupations, *, coupling, mixing=1.0
             if poi_status[-1] != "converged" or indefinite:
                 raise RuntimeError("schroedinger_poisson: the Poisson solve of step %d ended with status %r%s after %d iterations "
                                    "(poisson_op must be positive definite)" % (step, poi_status[-1], ", indefinite" if indefinite else "", done))
-            pplan.lincomb(0, [(1.0, PX), (-1.0, PPHI)], PDIFF)
-            d = math.sqrt(pplan.dot(0, PDIFF, PDIFF) / pplan.dot(0, PX, PX))
-            changes.append(d)
-            pplan.lincomb(0, [(1.0 - mixing, PPHI), (mixing, PX)], PPHI)
+            if history:
+                # r = g - x into the ring and its row of the Gram matrix in one pass; alpha on the host; the next x in one pass,
+                # into the next place of the ring: a free one, or the oldest pair's, which leaves the history with the next step
+                here, nxt = (step - 1) % (history + 1), step % (history + 1)
+                if here in pairs:
+                    pairs.remove(here)                            # (the oldest pair: the last step wrote this step's x over its x)
+                sums = pplan.mix_residual(0, PX, RING_X[here], RING_R[here], [RING_R[c] for c in pairs])
+                for c, v in zip(pairs, sums):
+                    gram[(c, here)] = gram[(here, c)] = float(v)
+                gram[(here, here)] = float(sums[-2])
+                d = math.sqrt(sums[-2] / sums[-1])
+                changes.append(d)
+                pairs.append(here)
+                alpha = anderson_coefficients([[gram[(a, b)] for b in pairs] for a in pairs])
+                if alpha is None:
+                    restarts.append(step)
+                    del pairs[:-1]
+                    alpha = np.ones(1)
+                depths.append(len(pairs))
+                pplan.mix_combine(0, [RING_X[c] for c in pairs], [RING_R[c] for c in pairs], alpha, mixing, RING_X[nxt])
+                PPHI = RING_X[nxt]
+            else:
+                pplan.lincomb(0, [(1.0, PX), (-1.0, PPHI)], PDIFF)
+                d = math.sqrt(pplan.dot(0, PDIFF, PDIFF) / pplan.dot(0, PX, PX))
+                changes.append(d)
+                depths.append(1)
+                pplan.lincomb(0, [(1.0 - mixing, PPHI), (mixing, PX)], PPHI)
             if coupling != 0.0:
                 pplan.copy_across(0, PPHI, eplan, RHO)
                 eplan.set_point_diagonal([(1.0, VEXT), (coupling, RHO)])
@@ -780,7 +854,8 @@ def schroedinger_poisson(op, poisson_op, k, occupations, *, coupling, mixing=1.0
                 break
         if info is not None:
             info.update(iterations=len(changes), status=status, changes=changes, eigen_iterations=eig_its, eigen_status=eig_status,
-                        poisson_iterations=poi_its, poisson_status=poi_status)
+                        poisson_iterations=poi_its, poisson_status=poi_status, mixing_history=history, mixing_depths=depths,
+                        mixing_restarts=restarts)
             if coupling != 0.0:                                   # (RHO holds phi by now: the density once more)
                 eplan.block_density(0, where, f / norm2, RHO)
             info["density"] = np.array(eplan.download(0, *RHO))

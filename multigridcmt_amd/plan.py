@@ -428,6 +428,30 @@ class Plan:
         check(_lib.lib().mgcmt_block_density(self._h, level, nq, (ctypes.c_int * nq)(*[v[0] for v in xs]), (ctypes.c_int * nq)(*[v[1] for v in xs]),
                                              _lib.as_dp(w), dst[0], dst[1], stream))
 
+    def mix_residual(self, level, out, inp, r, prev=(), stream=None):
+        """r <- out - inp point by point ((slot, vec) pairs; r none of the vectors read) and, from the same pass over out, inp
+        and the <= 8 earlier residuals ``prev``, the inner products (<r, prev[j]> in the order given, <r, r>, <out, out>) as
+        len(prev) + 2 numbers (mgcmt_mix_residual): the residual of an Anderson-mixing step, its row of the Gram matrix and
+        the relative change sqrt(<r, r> / <out, out>).  Synchronises.  Bit-reproducible, whatever the launch's grid."""
+        nprev = len(prev)
+        res = np.zeros(nprev + 2)
+        check(_lib.lib().mgcmt_mix_residual(self._h, level, out[0], out[1], inp[0], inp[1], r[0], r[1], nprev,
+                                            (ctypes.c_int * nprev)(*[v[0] for v in prev]) if nprev else None,
+                                            (ctypes.c_int * nprev)(*[v[1] for v in prev]) if nprev else None, _lib.as_dp(res), stream))
+        return res
+
+    def mix_combine(self, level, xs, rs, alpha, beta, dst, stream=None):
+        """dst <- sum_i alpha[i] * (xs[i] + beta * rs[i]) point by point ((slot, vec) pairs; <= 9 pairs; dst may be xs[0] and no
+        other input): one stream-ordered pass over the 2 len(xs) vectors (mgcmt_mix_combine) — the new iterate of an
+        Anderson-mixing step.  Bit-reproducible."""
+        p = len(xs)
+        a = np.array([float(c) for c in alpha])
+        if len(rs) != p or a.size != p:
+            raise ValueError("mix_combine: one residual and one coefficient per vector x")
+        ints = lambda vs, i: (ctypes.c_int * p)(*[v[i] for v in vs])
+        check(_lib.lib().mgcmt_mix_combine(self._h, level, p, ints(xs, 0), ints(xs, 1), ints(rs, 0), ints(rs, 1), _lib.as_dp(a), float(beta),
+                                           dst[0], dst[1], stream))
+
     def set_point_diagonal(self, terms, stream=None):
         """The per-point diagonal of the plan's operator <- sum of coeff * (slot, vec) over `terms` = [(coeff, (slot, vec)), ...]
         (at most four level-0 vectors of this plan, the arithmetic of lincomb), and the per-point planes of every level below
